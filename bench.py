@@ -9,7 +9,12 @@ One step = one pass of the hot path over one batch of synthetic client ciphertex
 Unit of work = one client ciphertext PRE'd and folded into the aggregate (92.7 MB algorithmic).
 Weak scaling: every GPU holds its own C clients x B ciphertexts; `value` = all ranks' units / max-over-ranks time.
 
+A plain run sets up, warms up, times EXACTLY --steps steps in one block and prints the result line.  --full adds the
+extras: the timed block repeated for --min-seconds (median block reported), and the CPU baseline (unless --no-cpu).
+--dump-outputs DIR writes what the last timed step computed (see dump_outputs) for output-for-output comparisons.
+
     python bench.py --gpus 1 --steps 5 --warmup 2
+    python bench.py --gpus 1 --steps 5 --warmup 2 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus 8 --steps 5 --warmup 2
 """
@@ -187,6 +192,33 @@ def verify_exchange(torch, dist, ctx, pipe, agg, out, ct_in, evk, C, B, Bs, L, w
     log("[bench] --verify ok: reduce-scatter + reduce_mod + rescale == modular sum of the per-rank aggregates")
 
 
+DUMP_SAMPLE = 1 << 20  # output words written per rank by --dump-outputs (3 float64 arrays of 8 MiB)
+
+
+def dump_outputs(out_dir, out, world, rank):
+    """--dump-outputs: the averaged aggregate `out` ([B][2][L-1][N] u64 residues in int64 words) of the last timed step.
+    float64 holds 53 bits, so every word goes out as two exact halves: lo30 = w & (2^30 - 1), hi30 = w >> 30.
+      out_index.npy         flat indices into `out` of a fixed seeded sample of DUMP_SAMPLE / world words (sorted)
+      out_lo30.npy, out_hi30.npy   the sampled words' halves
+      out_row_sums.npy      [B][2][L-1][2]: per row of N words, the sums of all lo30 and of all hi30 halves (exact)
+    With world > 1 every rank writes its own shard under a _rank<r> suffix."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    total, n = out.numel(), DUMP_SAMPLE // world
+    if total <= n:  # small outputs: every word
+        idx = np.arange(total, dtype=np.int64)
+    else:
+        idx = np.unique(np.random.default_rng(20240917).integers(0, total, size=n, dtype=np.int64))
+    words = out.reshape(-1)[torch.from_numpy(idx).to(out.device)]
+    mask = (1 << 30) - 1
+    arrays = {"out_index": idx, "out_lo30": words & mask, "out_hi30": words >> 30,
+              "out_row_sums": torch.stack([(out & mask).sum(-1), (out >> 30).sum(-1)], dim=-1)}
+    sfx = f"_rank{rank}" if world > 1 else ""
+    for name, a in arrays.items():
+        a = a.cpu().numpy() if hasattr(a, "cpu") else a
+        np.save(os.path.join(out_dir, f"{name}{sfx}.npy"), a.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -198,12 +230,19 @@ def main():
     ap.add_argument("--dnum", type=int, default=3)
     ap.add_argument("--clients", type=int, default=8, help="clients per GPU")
     ap.add_argument("--cts", type=int, default=16, help="ciphertexts per client (multiple of --gpus)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: repeat the timed block (--min-seconds, --max-blocks) and report the "
+                         "median block, and run the CPU baseline (unless --no-cpu)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last step computed to DIR/*.npy (float64)")
     ap.add_argument("--cpu-sample", type=int, default=1536,
-                    help="ciphertexts in the CPU-baseline sample (about 17 s on 16 cores; the 1-thread leg takes 1/48 of it)")
-    ap.add_argument("--no-cpu", action="store_true")
+                    help="--full: ciphertexts in the CPU-baseline sample (about 17 s on 16 cores; the 1-thread leg takes "
+                         "1/48 of it)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--min-seconds", type=float, default=2.0,
-                    help="repeat the timed block of --steps steps until this much of it has run; report the median block")
-    ap.add_argument("--max-blocks", type=int, default=64)
+                    help="--full: repeat the timed block of --steps steps until this much of it has run; report the "
+                         "median block")
+    ap.add_argument("--max-blocks", type=int, default=64, help="--full: at most this many timed blocks")
     ap.add_argument("--verify", action="store_true",
                     help="N>1 only, after the timed region: check the integer reduce-scatter + reduce_mod + rescale "
                          "result against the modular sum of the gathered per-rank aggregates")
@@ -415,16 +454,19 @@ def main():
             dt_b, ms_b = float(t[0]), float(t[1])
         return dt_b, ms_b
 
-    # the timed block is repeated until about --min-seconds of it have run (a 20-step block is 0.1 s): the reported
-    # figures are those of the MEDIAN block, with the fastest and the slowest beside them.  Every rank derives the same
-    # repeat count from the first block's max-over-ranks time.
+    # a plain run times one block of exactly --steps steps.  --full repeats the timed block until about --min-seconds of
+    # it have run (a 20-step block is 0.1 s): the reported figures are those of the MEDIAN block, with the fastest and
+    # the slowest beside them.  Every rank derives the same repeat count from the first block's max-over-ranks time.
     blocks = [timed_block()]
-    n_blocks = max(1, min(args.max_blocks, int(np.ceil(args.min_seconds / max(blocks[0][0], 1e-6)))))
+    n_blocks = max(1, min(args.max_blocks, int(np.ceil(args.min_seconds / max(blocks[0][0], 1e-6))))) if args.full else 1
     while len(blocks) < n_blocks:
         blocks.append(timed_block())
     order = sorted(range(len(blocks)), key=lambda i: blocks[i][0])
     dt, gpu_ms = blocks[order[(len(order) - 1) // 2]]  # lower median: an actual block, never an interpolation
     dt_min, dt_max = blocks[order[0]][0], blocks[order[-1]][0]
+
+    if args.dump_outputs:  # the last timed step's result: fence() has synchronised every stream
+        dump_outputs(args.dump_outputs, pipe["out"][(pipe["k"] - 1) & 1] if pipe is not None else out, world, rank)
 
     if world > 1:
         gpu_ms = dt * 1e3  # the exchange runs on a second stream: the main-stream events miss it, wall time does not
@@ -464,7 +506,8 @@ def main():
         "value": value, "unit": "ciphertexts/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": dt * 1e3 / args.steps, "ms_per_step_min": dt_min * 1e3 / args.steps,
         "ms_per_step_max": dt_max * 1e3 / args.steps, "timed_blocks": len(blocks),
-        "timing": f"median of {len(blocks)} timed blocks of {args.steps} steps each (fence on both sides of every block)",
+        "timing": (f"median of {len(blocks)} timed blocks of {args.steps} steps each (fence on both sides of every block)"
+                   if args.full else f"one timed block of {args.steps} steps (fence on both sides)"),
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
         "dtype": "u64", "data": "synthetic",
         "config": {"workload": f"C3+C4: {C} clients x {B} ct per GPU, N=2^{args.log_n}, L={L}, K={K}, dnum={args.dnum}: "
@@ -490,7 +533,7 @@ def main():
                                                  "lanes, against 1024 SIMDs x 2.4 GHz; cycle figures: "
                                                  "profiles/r02_ubench_intmul.txt, profiles/r02_ubench_fpmod.txt"}},
     }
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         try:
             result["cpu_baseline"] = cpu_baseline(args, log)
         except Exception as e:  # the baseline is a reported extra, never a reason to lose the GPU number

@@ -109,17 +109,34 @@ typedef struct {
     u64 *coef, *digits, *til0, *til1, *pc, *conv;
 } fast_ws;
 
+/* workspaces keyed by (context, level); a slot with c == NULL is free.  fcpu_ctx_free drops a context's slots before the
+ * context goes: a later context allocated at the same address must not find tables built for other parameters. */
 static fast_ws g_ws[8];
-static int g_nws = 0;
+static int g_next = 0;
 
 static uint32_t limb_of(const orc_ctx *c, uint32_t nl, uint32_t slot) { return slot < nl ? slot : c->L + (slot - nl); }
 
-static fast_ws *fast_prepare(const orc_ctx *c, uint32_t nl) {
-    for (int i = 0; i < g_nws; i++)
-        if (g_ws[i].c == c && g_ws[i].nl == nl) return &g_ws[i];
-    if (g_nws == 8) g_nws = 0; /* bench and tests use a handful of levels */
-    fast_ws *w = &g_ws[g_nws++];
+static void fast_release(fast_ws *w) {
+    for (uint32_t p = 0; p < w->nparts; p++) {
+        free(w->hat[p]);
+        free(w->hatp[p]);
+    }
+    free(w->phat); free(w->phatp); free(w->pinv); free(w->pinvp); free(w->bar);
+    free(w->coef); free(w->digits); free(w->til0); free(w->til1); free(w->pc); free(w->conv);
     memset(w, 0, sizeof *w);
+}
+
+static fast_ws *fast_prepare(const orc_ctx *c, uint32_t nl) {
+    fast_ws *w = NULL;
+    for (int i = 0; i < 8; i++)
+        if (g_ws[i].c == c && g_ws[i].nl == nl) return &g_ws[i];
+    for (int i = 0; i < 8 && !w; i++)
+        if (!g_ws[i].c) w = &g_ws[i];
+    if (!w) { /* bench and tests use a handful of levels: evict round-robin */
+        w = &g_ws[g_next];
+        g_next = (g_next + 1) % 8;
+    }
+    fast_release(w);
     const uint32_t n = c->n, K = c->K, L = c->L, alpha = c->alpha;
     w->c = c;
     w->nl = nl;
@@ -285,6 +302,12 @@ void fcpu_reencrypt(const orc_ctx *c, uint32_t nl, const u64 *ct, const u64 *evk
         const u64 m = c->mod[i];
         for (uint32_t r = 0; r < n; r++) o0[(size_t)i * n + r] = addmod(o0[(size_t)i * n + r], c0[(size_t)i * n + r], m);
     }
+}
+
+void fcpu_ctx_free(orc_ctx *c) {
+    for (int i = 0; i < 8; i++)
+        if (g_ws[i].c == c) fast_release(&g_ws[i]);
+    orc_ctx_free(c);
 }
 
 void fcpu_ntt_fwd(const orc_ctx *c, uint32_t limb, u64 *a) { fast_ntt_fwd(c, limb, a); }

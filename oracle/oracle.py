@@ -70,6 +70,7 @@ def lib(path=None):
         L.orc_decrypt_core.argtypes = [vp, u32, vp, vp, vp]
         if hasattr(L, "fcpu_reencrypt"):
             L.fcpu_reencrypt.argtypes = [vp, u32, vp, vp, vp]
+            L.fcpu_ctx_free.argtypes = [vp]
             L.fcpu_ntt_fwd.argtypes = [vp, u32, vp]
             L.fcpu_ntt_inv.argtypes = [vp, u32, vp]
         _libs[path] = L
@@ -245,6 +246,12 @@ class FastCpuContext(OracleContext):
     native backend carries it out (lazy butterflies, Shoup/Barrett constants, tables built once).  bench.py's cpu_baseline
     times this one; tests compare it with OracleContext.reencrypt word for word."""
     _lib_path = _FAST_PATH
+
+    def __del__(self):
+        try:
+            self.L_.fcpu_ctx_free(self.h)  # its cached ReEncrypt workspaces go with it
+        except Exception:
+            pass
 
     def reencrypt(self, ct, evk):
         ct, evk = _u64(ct), _u64(evk)

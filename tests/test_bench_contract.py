@@ -54,3 +54,31 @@ def test_secondary_ceiling_terms():
 def test_cpu_model_string():
     b = load_bench()
     assert isinstance(b.cpu_model(), str) and b.cpu_model()
+
+
+def test_dump_outputs_are_exact_float64_halves(tmp_path):
+    """--dump-outputs: every sampled u64 word comes back exactly as hi30 * 2^30 + lo30, the sample is fixed by its seed,
+    the row sums cover every word, and the files stay far below 64 MB."""
+    import numpy as np
+    import torch
+    b = load_bench()
+    g = torch.Generator().manual_seed(5)
+    out = torch.randint(0, 1 << 60, (3, 2, 4, 1 << 16), generator=g, dtype=torch.int64)  # 1.5 M words > the sample
+    b.dump_outputs(str(tmp_path / "a"), out, 1, 0)
+    b.dump_outputs(str(tmp_path / "b"), out, 1, 0)
+    ld = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in ("out_index", "out_lo30", "out_hi30", "out_row_sums")}
+    assert all(a.dtype == np.float64 for a in ld.values())
+    for n, a in ld.items():
+        assert np.array_equal(a, np.load(tmp_path / "b" / f"{n}.npy")), n
+    idx = ld["out_index"].astype(np.int64)
+    assert 0.5 * b.DUMP_SAMPLE < idx.size <= b.DUMP_SAMPLE and np.all(np.diff(idx) > 0)
+    words = out.reshape(-1).numpy()[idx]
+    assert np.array_equal(ld["out_hi30"].astype(np.int64) * (1 << 30) + ld["out_lo30"].astype(np.int64), words)
+    w = out.numpy()
+    assert ld["out_row_sums"].shape == (3, 2, 4, 2)
+    assert np.array_equal(ld["out_row_sums"][..., 0].astype(np.int64), (w & ((1 << 30) - 1)).sum(-1))
+    assert np.array_equal(ld["out_row_sums"][..., 1].astype(np.int64), (w >> 30).sum(-1))
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) < 64 << 20
+    small = out[:1, :, :1, :8]                                                          # fewer words than the sample: all
+    b.dump_outputs(str(tmp_path / "c"), small, 2, 1)
+    assert np.array_equal(np.load(tmp_path / "c" / "out_index_rank1.npy"), np.arange(16, dtype=np.float64))

@@ -958,6 +958,37 @@ def test_bench_two_ranks_sharded_by_ciphertext_index():
     assert "no collective" in line["config"]["workload"]
 
 
+def test_bench_plain_run_times_its_steps_and_dumps_the_same_outputs(tmp_path):
+    """A plain bench.py run: exactly --steps timed steps in one block, no CPU baseline, and --dump-outputs writes the
+    last step's result; two runs with the same arguments write identical arrays of canonical residues."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    lines = []
+    for run in ("a", "b"):
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+               "--log-n", "12", "--depth", "1", "--scaling-bits", "40", "--dnum", "2", "--clients", "3", "--cts", "4",
+               "--dump-outputs", str(tmp_path / run)]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines.append(json.loads(r.stdout.strip().splitlines()[-1]))
+    line = lines[0]
+    assert line["steps"] == 3 and line["timed_blocks"] == 1 and "cpu_baseline" not in line
+    assert line["ms_per_step"] > 0 and line["value"] > 0 and line["unit"] == "ciphertexts/s" and line["dtype"] == "u64"
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["out_hi30.npy", "out_index.npy", "out_lo30.npy", "out_row_sums.npy"]
+    for n in names:
+        assert np.array_equal(np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)), n
+    words = np.load(tmp_path / "a" / "out_hi30.npy").astype(np.uint64) * np.uint64(1 << 30) \
+        + np.load(tmp_path / "a" / "out_lo30.npy").astype(np.uint64)
+    L = line["config"]["limbs"]
+    words = words.reshape(4, 2, L - 1, 1 << 12)                                # [B][2][L-1][N]: every word of it
+    moduli = np.array(OracleContext(12, 1, 40, 60, dnum=2).moduli[:L - 1], dtype=np.uint64)
+    assert np.all(words < moduli[:, None]) and words.any()
+
+
 def _chacha20_block_py(key, counter, nonce):
     """RFC 8439 2.3 in plain Python (test-side restatement of the generator)."""
     def rotl(v, c):

@@ -202,3 +202,22 @@ def test_fast_cpu_reencrypt_equals_the_restatement(cfg):
         x[:4] = int(o.moduli[limb]) - 1
         assert np.array_equal(o.ntt_fwd(limb, x), f.ntt_fwd(limb, x))
         assert np.array_equal(o.ntt_inv(limb, x), f.ntt_inv(limb, x))
+
+
+def test_fast_cpu_workspaces_die_with_their_context():
+    """cpu_fast.c caches its ReEncrypt tables per (context, level).  Contexts of different parameters created and freed
+    in turn soon land at a freed one's address: each must still get its own tables, word for word the restatement's."""
+    from oracle.oracle import FastCpuContext, OracleContext
+    cfgs = [(14, 2, 40, 60, 2), (12, 18, 50, 60, 3), (10, 3, 40, 60, 2)]
+    oracles = [OracleContext(*c[:4], dnum=c[4]) for c in cfgs]
+    rng = np.random.default_rng(9)
+    for it in range(12):
+        o, c = oracles[it % 3], cfgs[it % 3]
+        f = FastCpuContext(*c[:4], dnum=c[4])
+        evk = np.empty((o.beta, 2, o.D, o.N), dtype=np.uint64)
+        for l in range(o.D):
+            evk[:, :, l, :] = rng.integers(0, int(o.moduli[l]), (o.beta, 2, o.N), dtype=np.uint64)
+        ct = np.stack([np.stack([rng.integers(0, int(o.moduli[l]), o.N, dtype=np.uint64) for l in range(2)])
+                       for _ in range(2)])
+        assert np.array_equal(o.reencrypt(ct, evk), f.reencrypt(ct, evk)), (it, c)
+        del f

@@ -17,4 +17,4 @@ cp profiles/hbm_traffic.json $out/hbm_traffic.json
 python tools/kernel_bw.py $out/${tag}_fetch $out/${tag}_write $out/${tag}_trace 7 > $out/${tag}_kernel_bw.txt
 rocprofv3 --pmc SQ_ACTIVE_INST_VALU SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY --output-format csv -d $out/${tag}_sq -o run -- python3 bench.py --steps 1 --warmup 0 --no-cpu --max-blocks 1 > $out/${tag}_sq.err 2>&1
 python tools/sqsum.py $out/${tag}_sq > $out/${tag}_sq_counters.txt
-python bench.py --steps 20 --warmup 3 > $out/${tag}_bench.json 2> $out/${tag}_bench.err
+python bench.py --full --steps 20 --warmup 3 > $out/${tag}_bench.json 2> $out/${tag}_bench.err
