@@ -42,6 +42,7 @@ extern "C" {
 #define MKCKKS_E_HIP (-3)       /* HIP runtime error (message has the detail) */
 #define MKCKKS_E_NOMEM (-4)
 #define MKCKKS_E_INTERNAL (-5)
+#define MKCKKS_E_PRECISION (-6)  /* decode: approximation error too high (log2 sigma > scaling_bits - 5) */
 
 typedef struct mkckks_ctx mkckks_ctx;
 
@@ -216,13 +217,36 @@ int mkckks_lift_ntt_batch(mkckks_ctx *c, const double *d_coef, uint64_t *d_out, 
 int mkckks_encode_batch(mkckks_ctx *c, const double *d_vals, uint64_t *d_pt, uint32_t n, uint32_t nl, double scale);
 /* ---- pt->GetRealPackedValue()  (decryptModelWeights.cpp:83,92,109) ------------
  * CRT interpolation of d_m u64[n][nl][N] (output of mkckks_decrypt_batch), / scale,
- * canonical embedding -> d_vals double[n][N/2].  Upstream Decode's noise flooding is
- * not applied. */
+ * canonical embedding -> d_vals double[n][N/2]: the exact embedding, without upstream
+ * Decode's noise estimate and flooding (those: mkckks_decode_flood_batch). */
 int mkckks_decode_batch(mkckks_ctx *c, const uint64_t *d_m, double *d_vals, uint32_t n, uint32_t nl, double scale);
+/* ---- pt->GetRealPackedValue() after cc->Decrypt with upstream's decode-time noise flooding
+ * (CKKSPackedEncoding::Decode as reached from decryptModelWeights.cpp:81-83,90-92,108-110; the defence against
+ * key recovery from shared CKKS decryptions, Li-Micciancio, ePrint 2022/816).  Layout and limits of
+ * mkckks_decode_batch; full packing (N/2 slots).  Per item, with m the centred lift of d_m in integer units,
+ * p = scaling_bits and u = scale / 2^p (upstream Decode brings the scaling factor to 2^p before it estimates; u = 1
+ * when scale = 2^p; a noiseScaleDeg-2 aggregate decoded at scale ~ 2^(2p) has u ~ 2^p):
+ *   m'_0 = m_0, m'_j = -m_{N-j}                      (coefficients of m(X^-1) mod X^N + 1)
+ *   d_j = m_j + m_{N-j}, j = 1..N-1;  mu = sum d / (N-1);
+ *   sigma = sqrt(sum (d - mu)^2 / (N-2)) / u         (fp64, fixed reduction order: the bits repeat)
+ *   log2 sigma > p - 5  -> the item fails ("The decryption failed because the approximation error is too high.
+ *                          Check the parameters.")
+ *   sigma_flood = sqrt(2) * max(sigma, sqrt(N) / 8)  (upstream CKKS_M_FACTOR = 1)
+ *   work position i < N/2: re = ((m_i + m'_i) / 2 + u sigma_flood z0) / scale,
+ *                          im = ((m_{i+N/2} + m'_{i+N/2}) / 2 + u sigma_flood z1) / scale, then the embedding.
+ * z0, z1: N(0,1) by Box-Muller from the ChaCha20 stream `stream_id` under h_key32 (32 HOST bytes; give flooding a
+ * key of its own): a pure function of (key, stream_id, item, i); mapping in csrc/sampler_kernels.hpp.
+ * Writes every output, then returns MKCKKS_E_PRECISION if any item failed (the first one is named in
+ * mkckks_last_error()).  h_log2_sigma (nullable, HOST, [n]) gets log2 sigma of every item (before the floor).
+ * Synchronous: downloads the per-item estimates once, which synchronises the context's stream. */
+int mkckks_decode_flood_batch(mkckks_ctx *c, const uint64_t *d_m, double *d_vals, uint32_t n, uint32_t nl,
+                              double scale, const uint8_t *h_key32, uint32_t stream_id,
+                              double *h_log2_sigma /* nullable, [n] */);
 
 /* ---- cc->Decrypt(sk, ct, &pt)  (client/src/decryptModelWeights.cpp:81,90,108)
  * DecryptCore: m = INTT(c0 + c1*s); d_m out u64[n_ct][nl][N] (COEFFICIENT).
- * CRT interpolation + Decode follow on the GPU: mkckks_decode_batch. */
+ * CRT interpolation + Decode follow on the GPU: mkckks_decode_batch (exact) or mkckks_decode_flood_batch
+ * (upstream's decode-time noise flooding). */
 int mkckks_decrypt_batch(mkckks_ctx *c, const uint64_t *d_ct, const uint64_t *d_sk, uint64_t *d_m,
                          uint32_t n_ct, uint32_t nl);
 

@@ -86,6 +86,7 @@ SYMBOLS = {
     "mkckks_chacha20_block": (_int, [_vp, _vp, C.c_char_p, _u32, C.POINTER(_u32)]),
     "mkckks_encode_batch": (_int, [_vp, _vp, _vp, _u32, _u32, _dbl]),
     "mkckks_decode_batch": (_int, [_vp, _vp, _vp, _u32, _u32, _dbl]),
+    "mkckks_decode_flood_batch": (_int, [_vp, _vp, _vp, _u32, _u32, _dbl, C.c_char_p, _u32, _vp]),
     "mkckks_reduce_mod_batch": (_int, [_vp, _vp, _u32, _u32, _u32]),
     "mkckks_comm_unique_id": (_int, [_vp]),
     "mkckks_comm_create": (_int, [_vp, _vp, _int, _int, C.POINTER(_vp)]),
@@ -95,6 +96,7 @@ SYMBOLS = {
     "mkckks_ctx_twiddles": (_int, [_vp, _u32, _int, _u64p]),
 }
 COMM_ID_BYTES = 128
+E_PRECISION = -6  # MKCKKS_E_PRECISION: decode_flood's noise estimate exceeds the context's precision
 
 _lib = None
 
@@ -436,6 +438,20 @@ class Context:
 
     def decode(self, m, vals, n, nl, scale):
         self._check(self._L.mkckks_decode_batch(self._h, _ptr(m), _ptr(vals), n, nl, float(scale)))
+
+    def decode_flood(self, m, vals, n, nl, scale, key, stream_id=0):
+        """decode with upstream Decode's noise estimate + flooding (include/mkckks.h: mkckks_decode_flood_batch);
+        `key`: the 32-byte ChaCha20 key of the flooding normals.  Returns log2 sigma_hat per item (float64[n]).  An
+        item over the precision limit raises MkckksError with code E_PRECISION after every output was written; the
+        array is then on the exception as `log2_sigma`."""
+        log2 = np.zeros(n, dtype=np.float64)
+        rc = self._L.mkckks_decode_flood_batch(self._h, _ptr(m), _ptr(vals), n, nl, float(scale), sampler_key(key),
+                                               stream_id, log2.ctypes.data)
+        if rc != 0:
+            err = MkckksError(rc, self._L.mkckks_last_error().decode())
+            err.log2_sigma = log2
+            raise err
+        return log2
 
     def decrypt(self, ct, sk, m, n_ct, nl):
         self._check(self._L.mkckks_decrypt_batch(self._h, _ptr(ct), _ptr(sk), _ptr(m), n_ct, nl))

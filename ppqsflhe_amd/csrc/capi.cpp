@@ -20,6 +20,9 @@ int guarded(F &&f) {
     try {
         f();
         return MKCKKS_OK;
+    } catch (const mk::PrecisionError &e) {
+        g_err = e.what();
+        return MKCKKS_E_PRECISION;
     } catch (const mk::NoDevice &e) {
         g_err = e.what();
         return MKCKKS_E_NODEVICE;
@@ -377,6 +380,14 @@ int mkckks_decode_batch(mkckks_ctx *c, const uint64_t *m, double *vals, uint32_t
         need(c && m && vals, "null argument");
         need(scale > 0, "scale must be positive");
         c->eng->decode(m, vals, n, nl, scale);
+    });
+}
+int mkckks_decode_flood_batch(mkckks_ctx *c, const uint64_t *m, double *vals, uint32_t n, uint32_t nl, double scale,
+                              const uint8_t *h_key32, uint32_t stream_id, double *h_log2_sigma) {
+    return guarded([&] {
+        need(c && m && vals && h_key32, "null argument");
+        need(scale > 0, "scale must be positive");
+        c->eng->decode_flood(m, vals, n, nl, scale, h_key32, stream_id, h_log2_sigma);
     });
 }
 int mkckks_decrypt_batch(mkckks_ctx *c, const uint64_t *ct, const uint64_t *sk, uint64_t *m, uint32_t n_ct,

@@ -20,6 +20,7 @@
 #include "sampler_kernels.hpp"
 
 #include <cmath>
+#include <cstdio>
 #include <type_traits>
 #include <cstdlib>
 #include <cstring>
@@ -1996,13 +1997,7 @@ void Engine::encode(const double *vals, u64 *pt, uint32_t cnt, uint32_t nl, doub
     ntt_launch(pt, cnt, nl, nl, false, nullptr, nullptr);
 }
 
-void Engine::decode(const u64 *m, double *vals, uint32_t cnt, uint32_t nl, double scale) {
-    need_device();
-    check_nl(nl);
-    if (!cnt) return;
-    if (nl > (uint32_t)CRT_MAX_LIMBS) throw std::invalid_argument("decode supports at most 32 limbs");
-    const uint32_t n = ps_.n, slots = n / 2;
-    CodecTables t{d_rot_, reinterpret_cast<const double2 *>(d_ksi_), slots, ps_.log_n - 1, 2 * n};
+const u64 *Engine::garner_table(uint32_t nl) {
     // Garner constants for the first nl limbs: inv[a] = (q_0..q_{a-1})^-1 mod q_a, G[a][k] = q_k mod q_a
     std::vector<u64> gar((size_t)nl + (size_t)nl * nl, 0);
     for (uint32_t a = 1; a < nl; ++a) {
@@ -2014,13 +2009,64 @@ void Engine::decode(const u64 *m, double *vals, uint32_t cnt, uint32_t nl, doubl
         }
         gar[a] = h_invmod(prod, qa);
     }
-    const u64 *d_gar = limb_vector("garner_" + std::to_string(nl), gar);
+    return limb_vector("garner_" + std::to_string(nl), gar);
+}
+
+void Engine::decode(const u64 *m, double *vals, uint32_t cnt, uint32_t nl, double scale) {
+    need_device();
+    check_nl(nl);
+    if (!cnt) return;
+    if (nl > (uint32_t)CRT_MAX_LIMBS) throw std::invalid_argument("decode supports at most 32 limbs");
+    const uint32_t n = ps_.n, slots = n / 2;
+    CodecTables t{d_rot_, reinterpret_cast<const double2 *>(d_ksi_), slots, ps_.log_n - 1, 2 * n};
+    const u64 *d_gar = garner_table(nl);
     double2 *v = reinterpret_cast<double2 *>(workspace((size_t)cnt * n * 2));
     const dim3 gs((slots + 255) / 256, cnt), gh((slots / 2 + 255) / 256, cnt);
     k_crt_to_complex<<<gs, 256, 0, stream_>>>(m, v, t, d_limb_, d_gar, nl, scale);
     for (uint32_t len = 2; len <= slots; len <<= 1) k_fft_special_stage<<<gh, 256, 0, stream_>>>(v, t, len);
     k_codec_store_real<<<gs, 256, 0, stream_>>>(v, vals, slots);
     MK_HIP(hipGetLastError());
+}
+
+void Engine::decode_flood(const u64 *m, double *vals, uint32_t cnt, uint32_t nl, double scale, const uint8_t *key32,
+                          uint32_t sid, double *h_log2) {
+    need_device();
+    check_nl(nl);
+    const ChaChaKey key = load_key(key32);
+    if (!cnt) return;
+    if (nl > (uint32_t)CRT_MAX_LIMBS) throw std::invalid_argument("decode supports at most 32 limbs");
+    const uint32_t n = ps_.n, slots = n / 2, nb = (n / 4 + FLOOD_THREADS - 1) / FLOOD_THREADS;
+    CodecTables t{d_rot_, reinterpret_cast<const double2 *>(d_ksi_), slots, ps_.log_n - 1, 2 * n};
+    const u64 *d_gar = garner_table(nl);
+    // arena: complex work array [cnt][slots], per-block partials [cnt][nb][3], per-item statistics [cnt][4]
+    u64 *ws = workspace((size_t)cnt * n + (size_t)cnt * nb * 3 + (size_t)cnt * 4);
+    double2 *v = reinterpret_cast<double2 *>(ws);
+    double *part = reinterpret_cast<double *>(ws + (size_t)cnt * n);
+    double *stats = part + (size_t)cnt * nb * 3;
+    const dim3 gs((slots + 255) / 256, cnt), gh((slots / 2 + 255) / 256, cnt);
+    k_crt_symmetrise<<<dim3(nb, cnt), FLOOD_THREADS, (size_t)nl * FLOOD_THREADS * sizeof(u64), stream_>>>(
+        m, v, part, t, d_limb_, d_gar, nl);
+    const double max_log2 = (double)ps_.scaling_bits - 5.0;
+    const double unit = scale / std::ldexp(1.0, (int)ps_.scaling_bits);  // estimate in units of scale / 2^p
+    k_flood_stats<<<(cnt + 63) / 64, 64, 0, stream_>>>(part, stats, cnt, nb, n, std::sqrt((double)n) / 8.0, max_log2,
+                                                       unit);
+    k_flood<<<gs, 256, 0, stream_>>>(v, stats, t, key, sid, scale);
+    for (uint32_t len = 2; len <= slots; len <<= 1) k_fft_special_stage<<<gh, 256, 0, stream_>>>(v, t, len);
+    k_codec_store_real<<<gs, 256, 0, stream_>>>(v, vals, slots);
+    MK_HIP(hipGetLastError());
+    std::vector<double> h((size_t)cnt * 4);
+    MK_HIP(hipMemcpyAsync(h.data(), stats, h.size() * sizeof(double), hipMemcpyDeviceToHost, stream_));
+    MK_HIP(hipStreamSynchronize(stream_));
+    if (h_log2)
+        for (uint32_t i = 0; i < cnt; ++i) h_log2[i] = h[(size_t)i * 4 + 1];
+    for (uint32_t i = 0; i < cnt; ++i)
+        if (h[(size_t)i * 4 + 3] != 0.0) {
+            char detail[160];
+            std::snprintf(detail, sizeof detail, " (item %u: log2 sigma = %.3f > scaling_bits - 5 = %.0f)", i,
+                          h[(size_t)i * 4 + 1], max_log2);
+            throw PrecisionError(std::string("The decryption failed because the approximation error is too high. "
+                                             "Check the parameters.") + detail);
+        }
 }
 
 void Engine::host_twiddles(uint32_t limb, bool inverse, std::vector<u64> &out) const {

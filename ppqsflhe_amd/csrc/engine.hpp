@@ -20,6 +20,10 @@ struct HipError : std::runtime_error {
 struct NoDevice : std::runtime_error {
     using std::runtime_error::runtime_error;
 };
+// decode_flood: an item's decryption-noise estimate exceeds the context's precision (log2 sigma > scaling_bits - 5)
+struct PrecisionError : std::runtime_error {
+    using std::runtime_error::runtime_error;
+};
 
 #define MK_HIP(expr)                                                                              \
     do {                                                                                          \
@@ -131,6 +135,11 @@ public:
     // CKKS canonical embedding on the device: vals [n][N/2] reals <-> plaintexts / decrypted polynomials
     void encode(const double *vals, u64 *pt, uint32_t n, uint32_t nl, double scale);
     void decode(const u64 *m, double *vals, uint32_t n, uint32_t nl, double scale);
+    // decode with upstream Decode's noise estimate + flooding (normals: ChaCha20 stream sid under key32); downloads the
+    // per-item estimates once, which synchronises the stream; h_log2 (nullable) [n] gets log2 sigma_hat per item.
+    // Throws PrecisionError naming the first failing item after all outputs are written.
+    void decode_flood(const u64 *m, double *vals, uint32_t n, uint32_t nl, double scale, const uint8_t *key32,
+                      uint32_t sid, double *h_log2);
 
     void host_twiddles(uint32_t limb, bool inverse, std::vector<u64> &out) const;
     // diagnostic builds (-DMK_STAMP=1, MKCKKS_STAMPS=1): copy one region of in-kernel phase stamps (2^20 words) to the
@@ -145,6 +154,7 @@ private:
     const DevConv &modup_conv(uint32_t nl, uint32_t part);
     const DevConv &moddown_conv(uint32_t nl);
     const u64 *limb_vector(const std::string &key, const std::vector<u64> &vals);  // cached small device arrays
+    const u64 *garner_table(uint32_t nl);  // CRT interpolation constants of the first nl limbs (decode)
     void ntt_launch(u64 *d, uint32_t n_polys, uint32_t nl, uint32_t ext, bool inverse, const u64 *scale,
                     const u64 *scale_sh);
     void reencrypt_chunk(const u64 *ct, const u64 *evk, u64 *out, uint32_t n_ct, uint32_t nl, bool accumulate);

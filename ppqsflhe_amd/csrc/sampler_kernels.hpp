@@ -9,6 +9,10 @@
 // streams.  Counter based: block b of stream `sid`, attempt `att` is ChaCha20(key, counter = b mod 2^32,
 // nonce = (b >> 32, sid, att)); element i takes 64-bit word i % 8 of block i / 8 -- a pure function of (key, sid, i),
 // independent of launch geometry.
+// Decode-time flooding normals (chacha_normal_pair, used by k_flood in codec_kernels.hpp): the pair of work-array
+// position i of item t is z0, z1 from 64-bit words 2(k%4) and 2(k%4)+1 of block k/4, k = t*N/2 + i, nonce
+// (b >> 32, sid, 0) -- Box-Muller on 53-bit uniforms u1 = ((w0 >> 11) + 1) * 2^-53 in (0, 1] (finite log),
+// u2 = (w1 >> 11) * 2^-53: z0 = sqrt(-2 ln u1) cos(2 pi u2), z1 = sqrt(-2 ln u1) sin(2 pi u2).
 #pragma once
 #include "modarith.hpp"
 
@@ -60,6 +64,25 @@ __global__ void k_chacha_block(uint32_t *out, ChaChaKey key, uint32_t counter, u
     chacha20_block(key, counter, n0, n1, n2, o);
     if (threadIdx.x == 0 && blockIdx.x == 0)
         for (int i = 0; i < 16; ++i) out[i] = o[i];
+}
+
+// two independent N(0,1) samples for element k of stream sid (mapping in the header comment)
+MK_D double2 chacha_normal_pair(const ChaChaKey &key, uint32_t sid, uint64_t k) {
+    uint32_t o[16];
+    const uint64_t b = k >> 2;
+    chacha20_block(key, (uint32_t)b, (uint32_t)(b >> 32), sid, 0, o);
+    u64 w0 = 0, w1 = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (j == (int)(k & 3)) {
+            w0 = ((u64)o[4 * j + 1] << 32) | o[4 * j];
+            w1 = ((u64)o[4 * j + 3] << 32) | o[4 * j + 2];
+        }
+    const double u1 = (double)((w0 >> 11) + 1) * 0x1p-53, u2 = (double)(w1 >> 11) * 0x1p-53;
+    const double r = sqrt(-2.0 * log(u1));
+    double s, c;
+    sincospi(2.0 * u2, &s, &c);
+    return double2{r * c, r * s};
 }
 
 // uniform over {-1, 0, 1}: 64-bit multiply-shift (bias < 2^-62)

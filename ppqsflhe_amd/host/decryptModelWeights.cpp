@@ -2,6 +2,8 @@
 // `decryptModelWeights <cc_path> <privkey_path> <input_encfile> <output_file>` (:28-38; caller client_fns.sh:100).
 // Decrypt (:81,90,108) -> mkckks_decrypt_batch (c0 + c1*s, INTT) + mkckks_decode_batch (CRT interpolation, embedding);
 // mean/std_dev keep slot 0 (SetLength(1), :82-83,91-92); values are concatenated and trimmed to prod(shape) (:100-116).
+// MKCKKS_DECRYPT_NOISE=flood (opt-in): upstream Decode's noise estimate + flooding (mkckks_decode_flood_batch) under a
+// fresh OS-drawn key; unset or "off": the exact embedding (mkckks_decode_batch); anything else: exit 1.
 #include "hostlib.hpp"
 using namespace mkh;
 
@@ -11,6 +13,17 @@ int main(int argc, char *argv[]) {
         return 1;
     }
     const std::string cc_path = argv[1], privkey_path = argv[2], input_encfile = argv[3], output_file = argv[4];
+    bool flood = false;
+    if (const char *e = std::getenv("MKCKKS_DECRYPT_NOISE")) {
+        const std::string mode = e;
+        if (mode == "flood") {
+            flood = true;
+        } else if (!mode.empty() && mode != "off") {
+            std::cerr << "[decrypt] ERROR: MKCKKS_DECRYPT_NOISE must be \"flood\" or \"off\", not \"" << mode << "\""
+                      << std::endl;
+            return 1;
+        }
+    }
     CcFile cc;
     try {
         cc = read_cc(cc_path);
@@ -55,7 +68,20 @@ int main(int argc, char *argv[]) {
                 if (c.scale != cts[0].scale) throw std::runtime_error("ciphertexts of one file must share a scaling factor");
             const size_t slots = s.slots();
             double *d_vals = s.alloc<double>(B * slots);
-            Session::check(mkckks_decode_batch(s.ctx(), d_m, d_vals, (uint32_t)B, nl, cts[0].scale));
+            if (flood) {
+                const SamplerKey key = fresh_key();
+                const int rc = mkckks_decode_flood_batch(s.ctx(), d_m, d_vals, (uint32_t)B, nl, cts[0].scale, key.bytes,
+                                                         0, nullptr);
+                if (rc == MKCKKS_E_PRECISION) {  // upstream's Decode throws; no output file
+                    std::cerr << "[decrypt] ERROR: The decryption failed because the approximation error is too high. "
+                                 "Check the parameters."
+                              << std::endl;
+                    return 1;
+                }
+                Session::check(rc);
+            } else {
+                Session::check(mkckks_decode_batch(s.ctx(), d_m, d_vals, (uint32_t)B, nl, cts[0].scale));
+            }
             std::vector<double> vals(B * slots);
             s.to_host(vals.data(), d_vals, vals.size());
             for (size_t i = 0; i < B; ++i) decoded[i].assign(vals.begin() + i * slots, vals.begin() + (i + 1) * slots);
