@@ -202,6 +202,28 @@ int mkckks_rekeygen(mkckks_ctx *c, const int8_t *d_s_old, const uint64_t *d_pk_n
  * e0,e1 int32[n_ct][N]; out u64[n_ct][2][nl][N]. */
 int mkckks_encrypt_batch(mkckks_ctx *c, const uint64_t *d_pk, const uint64_t *d_pt, const int8_t *d_v,
                          const int32_t *d_e0, const int32_t *d_e1, uint64_t *d_ct, uint32_t n_ct, uint32_t nl);
+
+/* ---- seeded secret-key ciphertexts (new: half the bytes of a client ciphertext) ---------------------------------
+ * A seeded ciphertext is (c0, seed): c1 = a is not sent but regenerated from a 32-byte ChaCha20 key K and a u32
+ * stream id sid as
+ *     a := mkckks_sample_uniform(d, n_polys = 1, nl, with_p = 0, K, sid)
+ * i.e. limb i, coefficient j is word i*N + j of stream sid, taken as EVALUATION (rejection as k_sample_uniform: attempt
+ * counter in nonce word 2, at most 64 attempts).  A lower level is a prefix of limbs.  Security rules: K reveals a
+ * only (a is public in RLWE); K must key nothing else (sharing it with the stream of e would reveal e and, with it,
+ * s); a client choosing its own K gains nothing, it could send any c1 anyway.
+ * cc->Encrypt(privateKey, pt) with a seeded a (replaces cc->Encrypt(publicKey, pt), encryptModelWeights.cpp:83,91,110):
+ * item t: a = stream (h_seed32, stream_base + t); d_c0 out u64[n_ct][nl][N] = pt + NTT(e) - a*s mod q_i;
+ * d_sk u64[D][N] EVALUATION (first nl limbs); d_pt u64[n_ct][nl][N] EVALUATION; d_e int32[n_ct][N] COEFFICIENT.
+ * stream_base + n_ct - 1 must fit in 32 bits.  n_ct == 0 is a no-op. */
+int mkckks_encrypt_seeded_batch(mkckks_ctx *c, const uint64_t *d_sk, const uint64_t *d_pt, const int32_t *d_e,
+                                uint64_t *d_c0, uint32_t n_ct, uint32_t nl, const uint8_t *h_seed32,
+                                uint32_t stream_base);
+/* new: rebuild c1 of seeded ciphertexts in place.  d_ct u64[n_ct][2][nl][N] (component 0 untouched);
+ * h_seeds32 [n_ct][32] and h_stream_ids [n_ct] are HOST arrays, read before return.  Any n_ct (the keys travel in the
+ * kernel arguments, 64 ciphertexts per launch); n_ct == 0 is a no-op.  What the server hosts call after the upload of
+ * c0 and before mkckks_reencrypt_sum_batch / mkckks_eval_sum_batch. */
+int mkckks_expand_seeded_batch(mkckks_ctx *c, uint64_t *d_ct, uint32_t n_ct, uint32_t nl,
+                               const uint8_t *h_seeds32, const uint32_t *h_stream_ids);
 /* scaled real coefficient vectors -> residues in EVALUATION format over nl limbs
  * (the integer half of CKKSPackedEncoding::Encode; the fp64 canonical embedding
  * runs on the GPU too: mkckks_encode_batch).  Each double (|x| < 2^120) is

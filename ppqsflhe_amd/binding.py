@@ -84,6 +84,8 @@ SYMBOLS = {
     "mkckks_sample_gauss": (_int, [_vp, _vp, _sz, _dbl, C.c_char_p, _u32]),
     "mkckks_sample_uniform": (_int, [_vp, _vp, _u32, _u32, _int, C.c_char_p, _u32]),
     "mkckks_chacha20_block": (_int, [_vp, _vp, C.c_char_p, _u32, C.POINTER(_u32)]),
+    "mkckks_encrypt_seeded_batch": (_int, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, C.c_char_p, _u32]),
+    "mkckks_expand_seeded_batch": (_int, [_vp, _vp, _u32, _u32, C.c_char_p, C.POINTER(_u32)]),
     "mkckks_encode_batch": (_int, [_vp, _vp, _vp, _u32, _u32, _dbl]),
     "mkckks_decode_batch": (_int, [_vp, _vp, _vp, _u32, _u32, _dbl]),
     "mkckks_decode_flood_batch": (_int, [_vp, _vp, _vp, _u32, _u32, _dbl, C.c_char_p, _u32, _vp]),
@@ -412,6 +414,22 @@ class Context:
     def encrypt(self, pk, pt, v, e0, e1, ct, n_ct, nl):
         self._check(self._L.mkckks_encrypt_batch(self._h, _ptr(pk), _ptr(pt), _ptr(v), _ptr(e0), _ptr(e1), _ptr(ct),
                                                  n_ct, nl))
+
+    def encrypt_seeded(self, sk, pt, e, c0, n_ct, nl, seed, stream_base=0):
+        """cc->Encrypt(privateKey, pt) with a seeded a (include/mkckks.h: mkckks_encrypt_seeded_batch): item t's a is
+        sample_uniform(1, nl, 0, seed, stream_base + t); writes c0 u64[n_ct][nl][N] only."""
+        self._check(self._L.mkckks_encrypt_seeded_batch(self._h, _ptr(sk), _ptr(pt), _ptr(e), _ptr(c0), n_ct, nl,
+                                                        sampler_key(seed), stream_base))
+
+    def expand_seeded(self, ct, n_ct, nl, seeds, stream_ids):
+        """rebuild c1 of seeded ciphertexts in place (mkckks_expand_seeded_batch): ct u64[n_ct][2][nl][N]; `seeds`: n_ct
+        32-byte keys (bytes, or ints as for the samplers), `stream_ids`: n_ct stream ids."""
+        keys = b"".join(sampler_key(k) for k in seeds)
+        sids = np.ascontiguousarray(stream_ids, dtype=np.uint32)
+        if len(keys) != 32 * n_ct or sids.size != n_ct:
+            raise ValueError("expand_seeded: need one seed and one stream id per ciphertext")
+        self._check(self._L.mkckks_expand_seeded_batch(self._h, _ptr(ct), n_ct, nl, keys,
+                                                       sids.ctypes.data_as(C.POINTER(_u32))))
 
     def lift_ntt(self, coef, out, n, nl):
         self._check(self._L.mkckks_lift_ntt_batch(self._h, _ptr(coef), _ptr(out), n, nl))

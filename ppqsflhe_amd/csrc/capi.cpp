@@ -335,6 +335,20 @@ int mkckks_encrypt_batch(mkckks_ctx *c, const uint64_t *pk, const uint64_t *pt, 
         c->eng->encrypt(pk, pt, v, e0, e1, ct, n_ct, nl);
     });
 }
+int mkckks_encrypt_seeded_batch(mkckks_ctx *c, const uint64_t *sk, const uint64_t *pt, const int32_t *e, uint64_t *c0,
+                                uint32_t n_ct, uint32_t nl, const uint8_t *h_seed32, uint32_t stream_base) {
+    return guarded([&] {
+        need(c && sk && pt && e && c0 && h_seed32, "null argument");
+        c->eng->encrypt_seeded(sk, pt, e, c0, n_ct, nl, h_seed32, stream_base);
+    });
+}
+int mkckks_expand_seeded_batch(mkckks_ctx *c, uint64_t *ct, uint32_t n_ct, uint32_t nl, const uint8_t *h_seeds32,
+                               const uint32_t *h_stream_ids) {
+    return guarded([&] {
+        need(c && ct && h_seeds32 && h_stream_ids, "null argument");
+        c->eng->expand_seeded(ct, n_ct, nl, h_seeds32, h_stream_ids);
+    });
+}
 int mkckks_lift_ntt_batch(mkckks_ctx *c, const double *coef, uint64_t *out, uint32_t n, uint32_t nl) {
     return guarded([&] {
         need(c && coef && out, "null argument");

@@ -1974,6 +1974,42 @@ void Engine::sample_uniform(u64 *out, uint32_t items, uint32_t nl, bool with_p, 
     MK_HIP(hipGetLastError());
 }
 
+void Engine::encrypt_seeded(const u64 *sk, const u64 *pt, const int32_t *e, u64 *c0, uint32_t n_ct, uint32_t nl,
+                            const uint8_t *key32, uint32_t sid0) {
+    need_device();
+    check_nl(nl);
+    const ChaChaKey key = load_key(key32);
+    if (!n_ct) return;
+    if ((uint64_t)sid0 + n_ct - 1 > 0xFFFFFFFFull) throw std::invalid_argument("stream ids overflow 32 bits");
+    const uint32_t n = ps_.n;
+    u64 *ee = workspace((size_t)n_ct * nl * n);
+    EwGeom g{n, nl, ps_.L};
+    k_lift<int32_t><<<ew_grid(n, nl, n_ct), EW_THREADS, 0, stream_>>>(e, ee, g, d_limb_, nl);
+    MK_HIP(hipGetLastError());
+    ntt_launch(ee, n_ct, nl, nl, false, nullptr, nullptr);
+    k_encrypt_seeded<<<dim3((n / 8 + 255) / 256, nl, n_ct), 256, 0, stream_>>>(pt, ee, sk, c0, n, nl, d_limb_, key, sid0);
+    MK_HIP(hipGetLastError());
+}
+
+void Engine::expand_seeded(u64 *ct, uint32_t n_ct, uint32_t nl, const uint8_t *keys32, const uint32_t *sids) {
+    need_device();
+    check_nl(nl);
+    if (!n_ct) return;
+    if (!keys32 || !sids) throw std::invalid_argument("null seed array");
+    const uint32_t n = ps_.n;
+    for (uint32_t t0 = 0; t0 < n_ct; t0 += SEED_ITEMS) {
+        const uint32_t cnt = std::min(SEED_ITEMS, n_ct - t0);
+        SeedTable t{};
+        for (uint32_t i = 0; i < cnt; ++i) {
+            t.key[i] = load_key(keys32 + (size_t)(t0 + i) * 32);
+            t.sid[i] = sids[t0 + i];
+        }
+        k_expand_seeded<<<dim3((n / 8 + 255) / 256, nl, cnt), 256, 0, stream_>>>(ct + (size_t)t0 * 2 * nl * n, n, nl,
+                                                                                d_limb_, t);
+        MK_HIP(hipGetLastError());
+    }
+}
+
 // ---- CKKS encode / decode (fp64 canonical embedding on the device) ---------------------------------
 
 void Engine::encode(const double *vals, u64 *pt, uint32_t cnt, uint32_t nl, double scale) {

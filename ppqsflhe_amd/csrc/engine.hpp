@@ -132,6 +132,13 @@ public:
     void sample_gauss(int32_t *out, size_t count, double sigma, const uint8_t *key32, uint32_t sid);
     void sample_uniform(u64 *out, uint32_t items, uint32_t nl, bool with_p, const uint8_t *key32, uint32_t sid);
     void chacha_block(uint32_t *d_out16, const uint8_t *key32, uint32_t counter, const uint32_t nonce[3]);  // KAT hook
+    // seeded ciphertexts: a = sample_uniform(1 poly, nl, Q only) of stream (key, sid).  encrypt_seeded: item t of
+    // pt u64[n_ct][nl][N] (EVALUATION), e int32[n_ct][N] (COEFFICIENT) -> c0 = pt + NTT(e) - a*s with a of stream
+    // (key32, sid0 + t), sk u64[.][N] (first nl limbs).  expand_seeded: c1 of ct u64[n_ct][2][nl][N] in place from
+    // the host arrays keys32 [n_ct][32] and sids [n_ct] (read before return)
+    void encrypt_seeded(const u64 *sk, const u64 *pt, const int32_t *e, u64 *c0, uint32_t n_ct, uint32_t nl,
+                        const uint8_t *key32, uint32_t sid0);
+    void expand_seeded(u64 *ct, uint32_t n_ct, uint32_t nl, const uint8_t *keys32, const uint32_t *sids);
     // CKKS canonical embedding on the device: vals [n][N/2] reals <-> plaintexts / decrypted polynomials
     void encode(const double *vals, u64 *pt, uint32_t n, uint32_t nl, double scale);
     void decode(const u64 *m, double *vals, uint32_t n, uint32_t nl, double scale);

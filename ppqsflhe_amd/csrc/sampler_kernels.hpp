@@ -136,4 +136,75 @@ __global__ void k_sample_uniform(u64 *out, uint32_t n, uint32_t nl, uint32_t L, 
     out[pos] = reduce_word(r, lc);
 }
 
+// ---- seeded ciphertexts: c1 = a is word i*N + j of stream (key, sid), i.e. k_sample_uniform(n_polys = 1) -------------
+// One lane = one ChaCha20 block = 8 consecutive words of one limb (N % 8 == 0: a block never spans two limbs), computed
+// once; a rejected word (r >= 2^64 - (2^64 mod q), probability (2^64 mod q) / 2^64: rare) recomputes only its own
+// block at attempts 1..63, as k_sample_uniform does.  The 64 B of a lane go out as four 16-B stores: a wave writes
+// 4 KiB, whole lines.
+constexpr uint32_t SEED_ITEMS = 64;  // items per launch: keys + stream ids by value in the kernel arguments (2.3 KiB)
+struct SeedTable {
+    ChaChaKey key[SEED_ITEMS];
+    uint32_t sid[SEED_ITEMS];
+};
+MK_D void uniform_block8(const ChaChaKey &key, uint32_t sid, uint64_t b, const LimbConst &lc, u64 (&w)[8]) {
+    const u64 limit = 0 - lc.c64;  // floor(2^64 / q) * q
+    uint32_t o[16];
+    chacha20_block(key, (uint32_t)b, (uint32_t)(b >> 32), sid, 0, o);
+    uint32_t rej = 0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        w[k] = ((u64)o[2 * k + 1] << 32) | o[2 * k];
+        rej |= (uint32_t)(w[k] >= limit) << k;
+    }
+    while (rej) {
+        const int k = __ffs(rej) - 1;
+        rej &= rej - 1;
+        u64 r = 0;
+        for (uint32_t attempt = 1; attempt < 64; ++attempt) {
+            r = chacha_u64(key, sid, b, attempt, k);
+            if (r < limit) break;
+        }
+#pragma unroll
+        for (int m = 0; m < 8; ++m)
+            if (m == k) w[m] = r;
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) w[k] = reduce_word(w[k], lc);
+}
+
+// c1 of a batch u64[n][2][nl][N] in place (component 0 untouched); item blockIdx.z uses (t.key[z], t.sid[z])
+__global__ __launch_bounds__(256) void k_expand_seeded(u64 *ct, uint32_t n, uint32_t nl, const LimbConst *limb, SeedTable t) {
+    const uint32_t item = blockIdx.z, slot = blockIdx.y, j8 = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j8 >= n / 8) return;
+    const LimbConst lc = limb[slot];
+    u64 w[8];
+    uniform_block8(t.key[item], t.sid[item], (uint64_t)slot * (n / 8) + j8, lc, w);
+    u64 *dst = ct + ((size_t)(2 * item + 1) * nl + slot) * n + (size_t)j8 * 8;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) *reinterpret_cast<ulong2 *>(dst + 2 * k) = ulong2{w[2 * k], w[2 * k + 1]};
+}
+
+// secret-key encryption with a seeded a: c0 = pt + ee - a*s mod q_i (the products of k_fma: mul_mod), where item t's a is
+// stream (key, sid0 + t); pt, ee, c0 u64[n_items][nl][N], s u64[.][N] (first nl limbs)
+__global__ __launch_bounds__(256) void k_encrypt_seeded(const u64 *pt, const u64 *ee, const u64 *s, u64 *c0, uint32_t n,
+                                                        uint32_t nl, const LimbConst *limb, ChaChaKey key, uint32_t sid0) {
+    const uint32_t item = blockIdx.z, slot = blockIdx.y, j8 = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j8 >= n / 8) return;
+    const LimbConst lc = limb[slot];
+    u64 a[8];
+    uniform_block8(key, sid0 + item, (uint64_t)slot * (n / 8) + j8, lc, a);
+    const size_t off = ((size_t)item * nl + slot) * n + (size_t)j8 * 8, soff = (size_t)slot * n + (size_t)j8 * 8;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const ulong2 m = *reinterpret_cast<const ulong2 *>(pt + off + 2 * k);
+        const ulong2 e = *reinterpret_cast<const ulong2 *>(ee + off + 2 * k);
+        const ulong2 sk = *reinterpret_cast<const ulong2 *>(s + soff + 2 * k);
+        const u64 p0 = mul_mod(a[2 * k], sk.x, lc), p1 = mul_mod(a[2 * k + 1], sk.y, lc);
+        ulong2 r;
+        r.x = sub_mod(add_mod(m.x, e.x, lc.q), p0, lc.q);
+        r.y = sub_mod(add_mod(m.y, e.y, lc.q), p1, lc.q);
+        *reinterpret_cast<ulong2 *>(c0 + off + 2 * k) = r;
+    }
+}
+
 }  // namespace mk

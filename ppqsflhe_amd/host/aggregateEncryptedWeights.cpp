@@ -4,7 +4,8 @@
 // on mean, std_dev and the first min(|v1|,|v2|) value ciphertexts (:80-109).
 // n-client generalisation: any number of further encfiles may follow the output path; every
 // matching ciphertext is summed with one mkckks_eval_sum_batch and scaled by 1/n_files.  (serverRound does the
-// re-encryptions and this aggregation in one program.)
+// re-encryptions and this aggregation in one program.)  Seeded inputs (encryptModelWeights --seeded) are accepted per
+// blob: c1 is rebuilt on the device before the sum.
 #include "hostlib.hpp"
 using namespace mkh;
 
@@ -42,9 +43,11 @@ int main(int argc, char *argv[]) {
         const std::vector<AggItem> items = build_agg_items(files, outputJson);
         if (!items.empty()) {
             std::vector<uint64_t> flat;  // [client][ct][2][nl][N]
-            const Ciphertext first = gather_agg_inputs(items, n_files, s, flat);
+            SeedList seeds;
+            const Ciphertext first = gather_agg_inputs(items, n_files, s, flat, seeds);
             const size_t B = items.size(), words = (size_t)2 * first.nl * N;
             uint64_t *d_in = s.to_device(flat.data(), flat.size());
+            seeds.expand(s, d_in, first.nl, 0, n_files * B);
             uint64_t *d_sum = s.alloc<uint64_t>(B * words);
             Session::check(mkckks_eval_sum_batch(s.ctx(), d_in, d_sum, (uint32_t)n_files, (uint32_t)B, first.nl));
             finish_aggregate(s, items, d_sum, first, n_files, outputJson);

@@ -1,7 +1,8 @@
 // changeCipherDomain -- drop-in for server/src/changeCipherDomain.cpp:
 // `changeCipherDomain <cc_path> <rekey_path> <input_encfile> <output_encfile>` (:19-29; caller server_fns.sh:65,79).
 // The reference loops cc->ReEncrypt(ct, reKey) over mean / std_dev / values[] of every layer (:61-117); here all
-// ciphertexts of the file go to HBM once and are re-encrypted by ONE mkckks_reencrypt_batch call.
+// ciphertexts of the file go to HBM once and are re-encrypted by ONE mkckks_reencrypt_batch call.  Seeded ciphertexts
+// (encryptModelWeights --seeded) are accepted per blob: c1 is rebuilt on the device; the output is full ciphertexts.
 #include "hostlib.hpp"
 using namespace mkh;
 
@@ -47,14 +48,21 @@ int main(int argc, char *argv[]) {
             for (const Ciphertext &c : cts)
                 if (c.nl != nl) throw std::runtime_error("ciphertexts of one file must share a level");
             const size_t words = (size_t)2 * nl * N;
-            std::vector<uint64_t> flat(cts.size() * words);
-            for (size_t i = 0; i < cts.size(); ++i) std::memcpy(&flat[i * words], cts[i].data.data(), words * 8);
+            std::vector<uint64_t> flat(cts.size() * words, 0);
+            SeedList seeds;
+            seeds.resize(cts.size());
+            for (size_t i = 0; i < cts.size(); ++i) {
+                put_payload(&flat[i * words], cts[i]);
+                seeds.set(i, cts[i]);
+            }
             uint64_t *d_ct = s.to_device(flat.data(), flat.size());
+            seeds.expand(s, d_ct, nl, 0, cts.size());
             uint64_t *d_evk = s.to_device(evk.data(), evk.size());
             Session::check(mkckks_reencrypt_batch(s.ctx(), d_ct, d_evk, d_ct, (uint32_t)cts.size(), nl));
             s.to_host(flat.data(), d_ct, flat.size());
             for (size_t i = 0; i < cts.size(); ++i) {
                 cts[i].data.assign(flat.begin() + i * words, flat.begin() + (i + 1) * words);
+                cts[i].seeded = false;
                 Json &lay = outputJson["weights_summary"].a[refs[i].layer];
                 std::string b64 = encode_ct(cts[i], N);
                 if (refs[i].field == 0) lay["mean"] = std::move(b64);

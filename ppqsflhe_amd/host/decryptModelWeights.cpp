@@ -4,6 +4,7 @@
 // mean/std_dev keep slot 0 (SetLength(1), :82-83,91-92); values are concatenated and trimmed to prod(shape) (:100-116).
 // MKCKKS_DECRYPT_NOISE=flood (opt-in): upstream Decode's noise estimate + flooding (mkckks_decode_flood_batch) under a
 // fresh OS-drawn key; unset or "off": the exact embedding (mkckks_decode_batch); anything else: exit 1.
+// Seeded ciphertexts (encryptModelWeights --seeded) are accepted per blob: c1 is rebuilt on the device first.
 #include "hostlib.hpp"
 using namespace mkh;
 
@@ -59,11 +60,16 @@ int main(int argc, char *argv[]) {
             for (const Ciphertext &c : cts)
                 if (c.nl != nl) throw std::runtime_error("ciphertexts of one file must share a level");
             const size_t words = (size_t)2 * nl * N, B = cts.size();
-            std::vector<uint64_t> flat(B * words);
-            for (size_t i = 0; i < B; ++i) std::memcpy(&flat[i * words], cts[i].data.data(), words * 8);
-            uint64_t *d_m = s.alloc<uint64_t>(B * (size_t)nl * N);
-            Session::check(mkckks_decrypt_batch(s.ctx(), s.to_device(flat.data(), flat.size()),
-                                                s.to_device(sk.data(), sk.size()), d_m, (uint32_t)B, nl));
+            std::vector<uint64_t> flat(B * words, 0);
+            SeedList seeds;
+            seeds.resize(B);
+            for (size_t i = 0; i < B; ++i) {
+                put_payload(&flat[i * words], cts[i]);
+                seeds.set(i, cts[i]);
+            }
+            uint64_t *d_m = s.alloc<uint64_t>(B * (size_t)nl * N), *d_ct = s.to_device(flat.data(), flat.size());
+            seeds.expand(s, d_ct, nl, 0, B);
+            Session::check(mkckks_decrypt_batch(s.ctx(), d_ct, s.to_device(sk.data(), sk.size()), d_m, (uint32_t)B, nl));
             for (const Ciphertext &c : cts)
                 if (c.scale != cts[0].scale) throw std::runtime_error("ciphertexts of one file must share a scaling factor");
             const size_t slots = s.slots();

@@ -99,10 +99,10 @@ inline CcFile read_cc(const std::string &path) {
 struct BlobHeader {
     char magic[4];       // "MKCK"
     uint32_t version;    // 1
-    uint32_t kind;       // 1 ciphertext, 2 public key, 3 secret key, 4 re-encryption key
+    uint32_t kind;       // 1 ciphertext, 2 public key, 3 secret key, 4 re-encryption key, 5 seeded ciphertext
     uint32_t ring_dim;
     uint32_t limbs;      // ciphertext: nl; keys: D
-    uint32_t parts;      // ciphertext: 2; pk: 2; sk: 1; rekey: 2*beta
+    uint32_t parts;      // ciphertext: 2; seeded ciphertext: 1; pk: 2; sk: 1; rekey: 2*beta
     uint32_t level;      // ciphertext: #dropped limbs
     uint32_t noise_deg;  // ciphertext: noiseScaleDeg
     double scale;        // ciphertext: scaling factor
@@ -111,12 +111,24 @@ struct BlobHeader {
 };
 static_assert(sizeof(BlobHeader) == 48, "blob header layout");
 
-enum : uint32_t { KIND_CT = 1, KIND_PK = 2, KIND_SK = 3, KIND_RK = 4 };
+enum : uint32_t { KIND_CT = 1, KIND_PK = 2, KIND_SK = 3, KIND_RK = 4, KIND_CT_SEEDED = 5 };
+
+// Seeded ciphertext (KIND_CT_SEEDED, written by encryptModelWeights --seeded): the header of a full ciphertext with
+// parts = 1, then this trailer, then c0 as u64[nl][N] -- 48 + 40 + 8 nl N bytes.  c1 is regenerated on the device from
+// (key, sid) by mkckks_expand_seeded_batch (stream definition: include/mkckks.h).
+struct SeedTrailer {
+    uint8_t key[32];
+    uint32_t sid;
+    uint32_t pad;  // 0
+};
+static_assert(sizeof(SeedTrailer) == 40, "seed trailer layout");
 
 struct Ciphertext {
     uint32_t nl = 0, level = 0, noise_deg = 0, slots = 0;
     double scale = 0;
-    std::vector<uint64_t> data;  // [2][nl][N]
+    std::vector<uint64_t> data;  // [2][nl][N]; seeded: c0 only, [nl][N]
+    bool seeded = false;
+    SeedTrailer seed{};
 };
 
 // Binary envelope: when set, ciphertext fields hold the raw container bytes in memory (no
@@ -129,11 +141,18 @@ inline bool &raw_blobs() {
 inline std::string encode_ct(const Ciphertext &ct, uint32_t ring_dim) {
     BlobHeader h{};
     std::memcpy(h.magic, "MKCK", 4);
-    h.version = 1; h.kind = KIND_CT; h.ring_dim = ring_dim; h.limbs = ct.nl; h.parts = 2;
+    h.version = 1; h.kind = ct.seeded ? KIND_CT_SEEDED : KIND_CT; h.ring_dim = ring_dim; h.limbs = ct.nl;
+    h.parts = ct.seeded ? 1 : 2;
     h.level = ct.level; h.noise_deg = ct.noise_deg; h.scale = ct.scale; h.slots = ct.slots;
-    std::string bin(sizeof h + ct.data.size() * 8, '\0');
+    const size_t trailer = ct.seeded ? sizeof(SeedTrailer) : 0;
+    std::string bin(sizeof h + trailer + ct.data.size() * 8, '\0');
     std::memcpy(&bin[0], &h, sizeof h);
-    std::memcpy(&bin[sizeof h], ct.data.data(), ct.data.size() * 8);
+    if (ct.seeded) {
+        SeedTrailer t = ct.seed;
+        t.pad = 0;
+        std::memcpy(&bin[sizeof h], &t, sizeof t);
+    }
+    std::memcpy(&bin[sizeof h + trailer], ct.data.data(), ct.data.size() * 8);
     return raw_blobs() ? bin : Base64Encode(bin);
 }
 
@@ -145,15 +164,22 @@ inline Ciphertext decode_ct(const std::string &b64, uint32_t ring_dim) {
     if (bin.size() < sizeof(BlobHeader)) throw std::runtime_error("ciphertext blob too short");
     BlobHeader h;
     std::memcpy(&h, bin.data(), sizeof h);
-    if (std::memcmp(h.magic, "MKCK", 4) || h.version != 1 || h.kind != KIND_CT)
+    if (std::memcmp(h.magic, "MKCK", 4) || h.version != 1 || (h.kind != KIND_CT && h.kind != KIND_CT_SEEDED))
         throw std::runtime_error("not a mkckks ciphertext blob");
-    if (h.ring_dim != ring_dim || h.parts != 2) throw std::runtime_error("ciphertext does not match the CryptoContext");
+    const bool seeded = h.kind == KIND_CT_SEEDED;
+    if (h.ring_dim != ring_dim || h.parts != (seeded ? 1u : 2u))
+        throw std::runtime_error("ciphertext does not match the CryptoContext");
     Ciphertext ct;
     ct.nl = h.limbs; ct.level = h.level; ct.noise_deg = h.noise_deg; ct.scale = h.scale; ct.slots = h.slots;
-    const size_t words = (size_t)2 * h.limbs * ring_dim;
-    if (bin.size() != sizeof h + words * 8) throw std::runtime_error("ciphertext blob has the wrong size");
+    ct.seeded = seeded;
+    const size_t words = (size_t)h.parts * h.limbs * ring_dim, trailer = seeded ? sizeof(SeedTrailer) : 0;
+    if (bin.size() != sizeof h + trailer + words * 8) throw std::runtime_error("ciphertext blob has the wrong size");
+    if (seeded) {
+        std::memcpy(&ct.seed, bin.data() + sizeof h, sizeof ct.seed);
+        if (ct.seed.pad != 0) throw std::runtime_error("seeded ciphertext: non-zero pad after the stream id");
+    }
     ct.data.resize(words);
-    std::memcpy(ct.data.data(), bin.data() + sizeof h, words * 8);
+    std::memcpy(ct.data.data(), bin.data() + sizeof h + trailer, words * 8);
     return ct;
 }
 
@@ -572,8 +598,9 @@ inline void validate_ct(const Ciphertext &ct, const Session &s) {
     if (ct.noise_deg != 1 && ct.noise_deg != 2) throw std::runtime_error("ciphertext: noiseScaleDeg must be 1 or 2");
     if (!(ct.scale > 0) || !std::isfinite(ct.scale)) throw std::runtime_error("ciphertext: bad scaling factor");
     if (ct.slots > N / 2) throw std::runtime_error("ciphertext: slot count exceeds N/2");
-    if (ct.data.size() != (size_t)2 * ct.nl * N) throw std::runtime_error("ciphertext: wrong payload size");
-    for (uint32_t comp = 0; comp < 2; ++comp)
+    const uint32_t parts = ct.seeded ? 1 : 2;
+    if (ct.data.size() != (size_t)parts * ct.nl * N) throw std::runtime_error("ciphertext: wrong payload size");
+    for (uint32_t comp = 0; comp < parts; ++comp)
         for (uint32_t i = 0; i < ct.nl; ++i) {
             const uint64_t q = s.moduli()[i];
             const uint64_t *p = &ct.data[((size_t)comp * ct.nl + i) * N];
@@ -587,6 +614,47 @@ inline Ciphertext decode_ct_checked(const std::string &blob, const Session &s) {
     validate_ct(ct, s);
     return ct;
 }
+
+// payload of ct into dst [2][nl][N]: a seeded ciphertext fills component 0 and leaves component 1 to expand_seeded()
+inline void put_payload(uint64_t *dst, const Ciphertext &ct) { std::memcpy(dst, ct.data.data(), ct.data.size() * 8); }
+
+// Seeds of a flat [count][2][nl][N] batch, by position; expand() rebuilds c1 of the seeded positions in HBM
+// (mkckks_expand_seeded_batch, one call per contiguous run) once their c0 has been uploaded.
+struct SeedList {
+    std::vector<uint8_t> seeded;     // per position: 1 = seeded
+    std::vector<SeedTrailer> seeds;  // per position (meaningful where seeded)
+    void resize(size_t n) {
+        seeded.assign(n, 0);
+        seeds.assign(n, SeedTrailer{});
+    }
+    void set(size_t i, const Ciphertext &ct) {
+        seeded[i] = ct.seeded ? 1 : 0;
+        if (ct.seeded) seeds[i] = ct.seed;
+    }
+    bool any() const { return std::find(seeded.begin(), seeded.end(), 1) != seeded.end(); }
+    // positions [first, first + count) of the list live at d_ct (position first at d_ct[0])
+    void expand(Session &s, uint64_t *d_ct, uint32_t nl, size_t first, size_t count) const {
+        const size_t words = (size_t)2 * nl * s.N();
+        std::vector<uint8_t> keys;
+        std::vector<uint32_t> sids;
+        for (size_t i = first; i < first + count;) {
+            if (!seeded[i]) {
+                ++i;
+                continue;
+            }
+            size_t j = i;
+            keys.clear();
+            sids.clear();
+            for (; j < first + count && seeded[j]; ++j) {
+                keys.insert(keys.end(), seeds[j].key, seeds[j].key + 32);
+                sids.push_back(seeds[j].sid);
+            }
+            Session::check(mkckks_expand_seeded_batch(s.ctx(), d_ct + (i - first) * words, (uint32_t)(j - i), nl,
+                                                      keys.data(), sids.data()));
+            i = j;
+        }
+    }
+};
 
 // ------------------------------------------------------------------------------------------------
 // Aggregation over n encrypted-weights files (aggregateEncryptedWeights.cpp:68-115): one output entry per tuple of
@@ -645,22 +713,26 @@ inline std::vector<AggItem> build_agg_items(const std::vector<Json> &files, Json
     }
     return items;
 }
-// the ciphertexts of every item, file-major: flat [file][item][2][nl][N]; all must share level and scale
+// the ciphertexts of every item, file-major: flat [file][item][2][nl][N]; all must share level and scale.  Seeded ones
+// have a zero c1 in `flat` and their seeds in `seeds` (same positions): SeedList::expand after the upload.
 inline Ciphertext gather_agg_inputs(const std::vector<AggItem> &items, size_t n_files, const Session &s,
-                                    std::vector<uint64_t> &flat) {
+                                    std::vector<uint64_t> &flat, SeedList &seeds) {
     const uint32_t N = s.N();
     Ciphertext first = decode_ct_checked(*items[0].blobs[0], s);
     const uint32_t nl = first.nl;
     const size_t words = (size_t)2 * nl * N, B = items.size();
-    flat.resize(n_files * B * words);
+    flat.assign(n_files * B * words, 0);
+    seeds.resize(n_files * B);
     for (size_t b = 0; b < B; ++b)
         for (size_t f = 0; f < n_files; ++f) {
             Ciphertext ct = decode_ct_checked(*items[b].blobs[f], s);
             if (ct.nl != nl || ct.noise_deg != first.noise_deg || ct.scale != first.scale)
                 throw std::runtime_error("EvalAdd operands differ in level or scale");
-            std::memcpy(&flat[(f * B + b) * words], ct.data.data(), words * 8);
+            put_payload(&flat[(f * B + b) * words], ct);
+            seeds.set(f * B + b, ct);
         }
     first.data.clear();
+    first.seeded = false;
     return first;
 }
 // EvalMult(sum, 1/n) (aggregateEncryptedWeights.cpp:83,92,107) on d_sum [B][2][nl][N] and the output document

@@ -15,7 +15,9 @@
 //   * results come back into a pinned buffer on the download stream (mkckks_fence_compute, mkckks_download_async) and are
 //     written with pwrite() by writer threads at offsets known in advance -- the output file is byte-identical to what
 //     write_envelope() produces;
-//   * residues are range-checked on the DEVICE (mkckks_count_noncanonical) instead of in a host loop, headers on the host.
+//   * residues are range-checked on the DEVICE (mkckks_count_noncanonical) instead of in a host loop, headers on the host;
+//   * a seeded ciphertext (KIND_CT_SEEDED) brings only c0 and its seed: c0 goes to component 0 of its slot and c1 is
+//     rebuilt in HBM (mkckks_expand_seeded_batch) behind the chunk's upload fence, before the re-encryption.
 // One host thread drives the context; the other threads only touch file descriptors and pinned memory.
 #pragma once
 #include <fcntl.h>
@@ -187,9 +189,10 @@ private:
 
 // header checks of validate_ct() for a container that went straight to the device; residues are checked there
 inline Ciphertext meta_of(const BlobHeader &h, const Session &s) {
-    if (std::memcmp(h.magic, "MKCK", 4) || h.version != 1 || h.kind != KIND_CT)
+    if (std::memcmp(h.magic, "MKCK", 4) || h.version != 1 || (h.kind != KIND_CT && h.kind != KIND_CT_SEEDED))
         throw std::runtime_error("not a mkckks ciphertext blob");
-    if (h.ring_dim != s.N() || h.parts != 2) throw std::runtime_error("ciphertext does not match the CryptoContext");
+    if (h.ring_dim != s.N() || h.parts != (h.kind == KIND_CT_SEEDED ? 1u : 2u))
+        throw std::runtime_error("ciphertext does not match the CryptoContext");
     Ciphertext ct;
     ct.nl = h.limbs; ct.level = h.level; ct.noise_deg = h.noise_deg; ct.scale = h.scale; ct.slots = h.slots;
     const uint32_t L = s.L();
@@ -286,6 +289,8 @@ struct RoundTimes {
     double setup = 0, round = 0;                  // ms: buffers + keys (once per process) | first read -> last byte written
     double last_upload = 0, last_download = 0;    // ms since the round started
     double read_busy = 0, write_busy = 0;         // ms summed over the reader / writer threads
+    double in_bytes = 0;                          // bytes of ciphertext containers read from the input files
+    size_t n_seeded = 0;                          // of which seeded (c1 rebuilt on the device)
     unsigned chunk = 0;
 };
 
@@ -435,6 +440,9 @@ inline AggResult run_round_pipeline(Session &s, const RoundPlan &plan, Json doc,
         uint64_t ticket = 0;
         Session::check(mkckks_upload_async(s.ctx(), d_all, ring->slot(0), in_bytes, &ticket));  // full-size copies: the first large one of a direction costs ~8 ms
         Session::check(mkckks_fence_uploads(s.ctx()));
+        const uint8_t warm_key[32] = {0};
+        const uint32_t warm_sid = 0;
+        Session::check(mkckks_expand_seeded_batch(s.ctx(), d_all, 1, nl, warm_key, &warm_sid));
         const size_t cnt = std::min<size_t>(Bc, B);
         uint64_t *slot = d_all + n_pre * cnt * words;
         if (n_pre) Session::check(mkckks_reencrypt_sum_batch(s.ctx(), d_all, d_evk, n_plain ? slot : d_sum, (uint32_t)n_pre, (uint32_t)cnt, nl));
@@ -478,21 +486,24 @@ inline AggResult run_round_pipeline(Session &s, const RoundPlan &plan, Json doc,
         BlobHeader hdr;
         unsigned chunk;
         double t_read0 = 0, t_read1 = 0, t_enq = 0, t_done = 0;  // MKCKKS_IO_TRACE
+        bool seeded = false;    // set by the reader from the header: only c0 (in_bytes / 2) is uploaded
+        SeedTrailer seed{};
     };
     std::vector<Job> jobs;
     jobs.reserve(n_clients * B);
-    std::vector<size_t> chunk_b0;
+    std::vector<size_t> chunk_b0, chunk_j0;  // first index, first job of every chunk
     for (size_t b0 = 0; b0 < B; b0 += Bc) chunk_b0.push_back(b0);
     const size_t n_chunks = chunk_b0.size();
     auto chunk_cnt = [&](size_t c) { return std::min<size_t>(Bc, B - chunk_b0[c]); };
     auto chunk_base = [&](size_t c) { return d_all + (n_clients + 1) * chunk_b0[c] * words; };
     for (size_t c = 0; c < n_chunks; ++c) {
         const size_t cnt = chunk_cnt(c);
+        chunk_j0.push_back(jobs.size());
         for (size_t k = 0; k < n_clients; ++k)
             for (size_t i = 0; i < cnt; ++i) {
                 const size_t b = chunk_b0[c] + i, bi = blob_index(*items[b].blobs[k]);
                 const size_t slot_k = k < n_pre ? k : k + 1;  // position n_pre is the sum slot
-                jobs.push_back(Job{idx[k].fd, idx[k].blobs.at(bi), chunk_base(c) + (slot_k * cnt + i) * words, BlobHeader{}, (unsigned)c, 0, 0, 0, 0});
+                jobs.push_back(Job{idx[k].fd, idx[k].blobs.at(bi), chunk_base(c) + (slot_k * cnt + i) * words, BlobHeader{}, (unsigned)c, 0, 0, 0, 0, false, SeedTrailer{}});
             }
     }
 
@@ -528,9 +539,16 @@ inline AggResult run_round_pipeline(Session &s, const RoundPlan &plan, Json doc,
                 }
                 const double tb = now_ms();
                 Job &job = jobs[j];
-                if (job.blob.size != sizeof(BlobHeader) + in_bytes) throw std::runtime_error("ciphertext blob has the wrong size");
+                if (job.blob.size < sizeof(BlobHeader)) throw std::runtime_error("ciphertext blob too short");
                 pread_all(job.fd, &job.hdr, sizeof(BlobHeader), job.blob.offset);
-                pread_all(job.fd, ring->slot(slot), in_bytes, job.blob.offset + sizeof(BlobHeader));
+                job.seeded = job.hdr.kind == KIND_CT_SEEDED;  // the other header fields are checked by meta_of below
+                const size_t trailer = job.seeded ? sizeof(SeedTrailer) : 0, payload = job.seeded ? in_bytes / 2 : in_bytes;
+                if (job.blob.size != sizeof(BlobHeader) + trailer + payload) throw std::runtime_error("ciphertext blob has the wrong size");
+                if (job.seeded) {
+                    pread_all(job.fd, &job.seed, sizeof job.seed, job.blob.offset + sizeof(BlobHeader));
+                    if (job.seed.pad != 0) throw std::runtime_error("seeded ciphertext: non-zero pad after the stream id");
+                }
+                pread_all(job.fd, ring->slot(slot), payload, job.blob.offset + sizeof(BlobHeader) + trailer);
                 busy += now_ms() - tb;
                 job.t_read0 = tb - t0;
                 job.t_read1 = now_ms() - t0;
@@ -606,6 +624,8 @@ inline AggResult run_round_pipeline(Session &s, const RoundPlan &plan, Json doc,
         double call_ms[6] = {0, 0, 0, 0, 0, 0};  // chunk 0's calls, for the trace
         std::deque<std::pair<uint64_t, size_t>> down_flight;   // (ticket, output index)
         std::vector<size_t> enq(n_chunks, 0);
+        std::vector<uint8_t> seed_keys;
+        std::vector<uint32_t> seed_sids;
         size_t uploaded = 0, computed = 0, downloaded = 0;
         const double operand = 1.0 / (double)n_clients;
         while (downloaded < B) {
@@ -623,7 +643,10 @@ inline AggResult run_round_pipeline(Session &s, const RoundPlan &plan, Json doc,
             }
             if (have) {
                 uint64_t ticket = 0;
-                Session::check(mkckks_upload_async(s.ctx(), jobs[got.second].d_dst, ring->slot(got.first), in_bytes, &ticket));
+                const Job &job = jobs[got.second];
+                Session::check(mkckks_upload_async(s.ctx(), job.d_dst, ring->slot(got.first), job.seeded ? in_bytes / 2 : in_bytes, &ticket));
+                tm.in_bytes += (double)job.blob.size;
+                tm.n_seeded += job.seeded ? 1 : 0;
                 up_flight.emplace_back(ticket, got.first);
                 up_jobs.push_back(got.second);
                 jobs[got.second].t_enq = now_ms() - t0;
@@ -657,6 +680,22 @@ inline AggResult run_round_pipeline(Session &s, const RoundPlan &plan, Json doc,
                     tc = now_ms();
                 };
                 Session::check(mkckks_fence_uploads(s.ctx()));
+                // seeded inputs: c1 from the seed, one call per run of seeded jobs in adjacent device slots
+                for (size_t j = chunk_j0[c], j_end = j + n_clients * cnt; j < j_end;) {
+                    if (!jobs[j].seeded) {
+                        ++j;
+                        continue;
+                    }
+                    seed_keys.clear();
+                    seed_sids.clear();
+                    size_t e = j;
+                    for (; e < j_end && jobs[e].seeded && jobs[e].d_dst == jobs[j].d_dst + (e - j) * words; ++e) {
+                        seed_keys.insert(seed_keys.end(), jobs[e].seed.key, jobs[e].seed.key + 32);
+                        seed_sids.push_back(jobs[e].seed.sid);
+                    }
+                    Session::check(mkckks_expand_seeded_batch(s.ctx(), jobs[j].d_dst, (uint32_t)(e - j), nl, seed_keys.data(), seed_sids.data()));
+                    j = e;
+                }
                 lap(0);
                 if (n_pre)  // with clients already in the domain the re-encrypted sum is one more term of their EvalAdd
                     Session::check(mkckks_reencrypt_sum_batch(s.ctx(), base, d_evk, n_plain ? slot : sum, (uint32_t)n_pre, (uint32_t)cnt, nl));
@@ -717,7 +756,7 @@ inline AggResult run_round_pipeline(Session &s, const RoundPlan &plan, Json doc,
                     std::fprintf(f, "%zu %u %.3f %.3f %.3f %.3f\n", j, jobs[j].chunk, jobs[j].t_read0, jobs[j].t_read1, jobs[j].t_enq, jobs[j].t_done);
                 std::fprintf(f, "# chunk compute_enqueue_start compute_enqueue_end\n");
                 for (size_t c = 0; c < n_chunks; ++c) std::fprintf(f, "c%zu %.3f %.3f\n", c, chunk_enq[c].first, chunk_enq[c].second);
-                std::fprintf(f, "# chunk 0 calls: fence_uploads %.3f, reencrypt_sum(+eval_sum) %.3f, scale %.3f, fence_compute %.3f, download_async %.3f ms\n",
+                std::fprintf(f, "# chunk 0 calls: fence_uploads (+expand_seeded) %.3f, reencrypt_sum(+eval_sum) %.3f, scale %.3f, fence_compute %.3f, download_async %.3f ms\n",
                              call_ms[0], call_ms[1], call_ms[2], call_ms[3], call_ms[4]);
                 std::fclose(f);
             }

@@ -18,6 +18,8 @@
 // slots, uploads run beside the reads, residues are range-checked on the device, results are written by pwrite() from
 // pinned slots.  MKCKKS_SYNC_IO=1 forces the synchronous path (every ciphertext through read_envelope / decode_ct /
 // mkckks_upload); both write the same bytes (tests/test_cli_hosts.py).  A "[round] timing" line reports the phases.
+// Seeded client ciphertexts (encryptModelWeights --seeded) are accepted per blob on both paths: only c0 is read and
+// uploaded, c1 is rebuilt on the device (mkckks_expand_seeded_batch); every output is a full ciphertext.
 //   serverRound <cc_path> --rounds <file>
 // runs one round per line of <file> (a line = the arguments after <cc_path> above) in ONE process -- what the loop of
 // orchestration/run.sh:37-43 does with one process per step: the context, the re-encryption keys (by file name), the
@@ -150,7 +152,8 @@ static int run_round(Session &s, ServerState &st, const RoundArgs &a) {
         const double n_ct = (double)(n_clients * items.size());
         std::cout << "[round] timing: " << n_clients << " clients x " << items.size() << " ciphertexts, chunks of " << tm.chunk
                   << " indices, " << threads << " I/O threads: files to file " << tm.round << " ms -> " << n_ct / tm.round * 1e3
-                  << " ciphertexts/s (last upload done at " << tm.last_upload << " ms, last download at " << tm.last_download
+                  << " ciphertexts/s, input " << tm.in_bytes / 1048576.0 << " MiB (" << tm.n_seeded << " seeded ciphertexts) = "
+                  << tm.in_bytes / tm.round * 1e-6 << " GB/s (last upload done at " << tm.last_upload << " ms, last download at " << tm.last_download
                   << " ms; reader threads busy " << tm.read_busy << " ms, writer threads " << tm.write_busy
                   << " ms in total); before it: context (HIP start-up, tables; once per process) " << st.t_ctx
                   << " ms, re-encryption key file(s) not yet loaded " << t_keys << " ms, index + buffers + key upload + warm-up "
@@ -159,7 +162,8 @@ static int run_round(Session &s, ServerState &st, const RoundArgs &a) {
         const size_t B = items.size();
         const size_t n_plain = n_clients - n_pre;
         std::vector<uint64_t> flat;  // [client in `order`][ct][2][nl][N]
-        const Ciphertext first = gather_agg_inputs(items, n_clients, s, flat);
+        SeedList seeds;              // seeded inputs: c1 rebuilt on the device after the upload of c0
+        const Ciphertext first = gather_agg_inputs(items, n_clients, s, flat, seeds);
         const size_t words = (size_t)2 * first.nl * N, blk = B * words;
         // device layout: [re-keyed clients][one slot for their re-encrypted sum][clients already in the domain]:
         // the slot and what follows it are the terms of the final n-ary EvalAdd, no copy in between
@@ -167,6 +171,8 @@ static int run_round(Session &s, ServerState &st, const RoundArgs &a) {
         if (n_pre) Session::check(mkckks_upload(s.ctx(), d_all, flat.data(), n_pre * blk * 8));
         if (n_plain) Session::check(mkckks_upload(s.ctx(), d_slot + blk, flat.data() + n_pre * blk, n_plain * blk * 8));
         const uint32_t nl = first.nl;
+        seeds.expand(s, d_all, nl, 0, n_pre * B);
+        seeds.expand(s, d_slot + blk, nl, n_pre * B, n_plain * B);
         uint64_t *d_sum = d_slot;
         if (n_pre) {
             uint64_t *d_evk = st.cache.grow(st.cache.evk, n_pre * evk_words);

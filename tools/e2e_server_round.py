@@ -13,7 +13,9 @@ Every arm's aggregate file must have the same bytes.  Per arm, over --reps runs:
 min / median / max, and the whole process's wall time (context tables, JSON keys, pinned buffers, HIP start-up: paid once
 per process).  Last: `serverRound --rounds` with 10 and 40 rounds over the same inputs in ONE process, timed from outside
 (whole process) and per round (wall).  encryptModelWeights packs the layer's mean and std_dev as two more ciphertexts: 18 per client.
-usage: python tools/e2e_server_round.py [--dir /dev/shm/mkckks_e2e] [--clients 8] [--cts 16] [--keep]"""
+--seeded: every client also encrypts with `encryptModelWeights <cc> <sk> ... --seeded` (c0 + 40 bytes per ciphertext); the
+arms are then full and seeded inputs, 8 I/O threads, alternating run by run (--reps pairs), without the --rounds legs.
+usage: python tools/e2e_server_round.py [--dir /dev/shm/mkckks_e2e] [--clients 8] [--cts 16] [--keep] [--seeded]"""
 import argparse
 import hashlib
 import json
@@ -59,6 +61,7 @@ def main():
     ap.add_argument("--clients", type=int, default=8)
     ap.add_argument("--cts", type=int, default=16)
     ap.add_argument("--keep", action="store_true")
+    ap.add_argument("--seeded", action="store_true", help="full vs seeded client ciphertexts, alternating")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--rounds", type=int, nargs="*", default=[10, 40], help="rounds per process for the --rounds legs")
     ap.add_argument("--arms", default="", help="instead of the default arms: 'K=V,K=V;K=V;...' (environment of serverRound per arm)")
@@ -76,7 +79,7 @@ def main():
         rng = np.random.default_rng(5)
         t_prep = time.perf_counter()
         run("keyGen", p("CC.json"), p("pkT"), p("skT"))
-        pairs = []
+        pairs, pairs_s = [], []
         mean = np.zeros(B * 32768)
         for c in range(C):
             run("keyGen", p("CC.json"), p(f"pk{c}"), p(f"sk{c}"))
@@ -86,6 +89,9 @@ def main():
                 json.dump({"weights_summary": [{"layer": "dense", "shape": [len(vals)], "mean": float(vals.mean()),
                                                 "std_dev": float(vals.std()), "values": vals.tolist()}]}, f)
             run("encryptModelWeights", p("CC.json"), p(f"pk{c}"), p(f"w{c}.json"), p(f"enc{c}.mkws"))
+            if args.seeded:
+                run("encryptModelWeights", p("CC.json"), p(f"sk{c}"), p(f"w{c}.json"), p(f"encS{c}.mkws"), "--seeded")
+                pairs_s += [p(f"rk{c}"), p(f"encS{c}.mkws")]
             os.remove(p(f"w{c}.json"))
             run("REkeyGen", p("CC.json"), p(f"sk{c}"), p("pkT"), p(f"rk{c}"))
             pairs += [p(f"rk{c}"), p(f"enc{c}.mkws")]
@@ -100,16 +106,21 @@ def main():
         arms.append(("synchronous (MKCKKS_SYNC_IO=1)", {"MKCKKS_SYNC_IO": "1"}))
         if args.arms:
             arms = [(a, dict(kv.split("=", 1) for kv in a.split(",") if kv)) for a in args.arms.split(";")]
-        digest = None
+        if args.seeded:
+            arms = [("full inputs, 8 I/O threads", {"MKCKKS_IO_THREADS": "8"}),
+                    ("seeded inputs, 8 I/O threads", {"MKCKKS_IO_THREADS": "8"})] * args.reps
+            args.reps, args.rounds = 1, []
+        digest = {}  # per input set: full / seeded inputs carry different encryption randomness
         n_total = None
         print(f"{'arm':34s} {'round ms: min / median / max':>30s} {'ct/s (median)':>14s} {'process wall s':>15s}   last line of the median run")
         for name, env in arms:
+            seeded = name.startswith("seeded")
             runs = []
             for rep in range(args.reps):
                 out = p("agg.mkws")
                 if os.path.exists(out):
                     os.remove(out)
-                r, dt = run("serverRound", p("CC.json"), out, *pairs, env=env)
+                r, dt = run("serverRound", p("CC.json"), out, *(pairs_s if seeded else pairs), env=env)
                 line = [ln for ln in r.stdout.splitlines() if "[round] timing:" in ln]
                 ms = None
                 if line:
@@ -117,9 +128,7 @@ def main():
                     n_total, ms = int(m.group(1)) * int(m.group(2)), float(m.group(3))
                 runs.append((ms if ms is not None else dt * 1e3, dt, line[0] if line else ""))
                 h = sha(out)
-                if digest is None:
-                    digest = h
-                if h != digest:
+                if digest.setdefault(seeded, h) != h:
                     raise SystemExit(f"arm '{name}' wrote different bytes")
             runs.sort()
             med = runs[len(runs) // 2]
@@ -138,7 +147,7 @@ def main():
             per = [float(m) for m in re.findall(r"round \d+ of \d+: ([0-9.]+) ms wall", r.stdout)]
             last = [ln for ln in r.stdout.splitlines() if " rounds, " in ln][-1]
             for k in range(n_rounds):
-                if sha(p(f"agg_r{k}.mkws")) != digest:
+                if sha(p(f"agg_r{k}.mkws")) != digest[False]:
                     raise SystemExit(f"round {k} of the {n_rounds}-round process wrote different bytes")
                 os.remove(p(f"agg_r{k}.mkws"))
             print(f"one process, {n_rounds:3d} rounds (8 I/O threads): whole process {dt:6.2f} s = {n_rounds * n_total / dt:6.0f} ct/s; per round "
@@ -152,7 +161,7 @@ def main():
         if dec.size != mean.size or not err < 2.0 ** -25:
             raise SystemExit(f"decrypted aggregate differs from the plaintext mean: {dec.size} values, max error {err:g}")
         print(f"# decrypted aggregate = plaintext mean of the {C} clients: {dec.size} values, max |error| {err:.3g}")
-        print(f"# every arm wrote the same aggregate: sha256 {digest[:16]}..., {os.path.getsize(p('agg.mkws')) / 1048576.0:.1f} MiB")
+        print(f"# every arm wrote the same aggregate: sha256 {digest[seeded][:16]}..., {os.path.getsize(p('agg.mkws')) / 1048576.0:.1f} MiB")
     finally:
         if not args.keep:
             shutil.rmtree(d, ignore_errors=True)
