@@ -160,6 +160,15 @@ int mkckks_reencrypt_accumulate_batch(mkckks_ctx *c, const uint64_t *d_ct, const
  * adding them in any order; the last ModDown pass of all clients and the sum are one kernel. */
 int mkckks_reencrypt_sum_batch(mkckks_ctx *c, const uint64_t *d_cts, const uint64_t *d_evks, uint64_t *d_out,
                                uint32_t n_clients, uint32_t n_ct, uint32_t nl);
+/* fan-out form of the distribution leg (orchestration/server_fns.sh:76-80: changeCipherDomain.cpp:74 run n-1 times
+ * on ONE input file, once per client key): d_out[k][b] = ReEncrypt(d_ct[b], d_evks[k]).
+ * d_ct u64[n_ct][2][nl][N] (read-only), d_evks u64[n_keys][beta][2][D][N] (layout of mkckks_reencrypt_sum_batch),
+ * d_out u64[n_keys][n_ct][2][nl][N].  The key-independent half of the key switch (INTT of c1, ModUp conversions,
+ * forward transform of every converted digit) runs once per ciphertext instead of once per (ciphertext, key).
+ * Bit-identical, for every k, to mkckks_reencrypt_batch(c, d_ct, d_evks + k * evk_words, d_out + k * n_ct * ct_words,
+ * n_ct, nl).  d_out must not overlap d_ct (MKCKKS_E_INVALID); n_keys == 0 or n_ct == 0 is a no-op. */
+int mkckks_reencrypt_fanout_batch(mkckks_ctx *c, const uint64_t *d_ct, const uint64_t *d_evks, uint64_t *d_out,
+                                  uint32_t n_keys, uint32_t n_ct, uint32_t nl);
 /* stages of the above, exposed for parity tests and profiling:
  * KeySwitchHYBRID::EvalKeySwitchPrecomputeCore: c1 u64[n][nl][N] ->
  * digits u64[n][nparts][nl+K][N]; ApproxModDown: u64[n][nl+K][N] -> u64[n][nl][N]. */

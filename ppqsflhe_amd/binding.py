@@ -73,6 +73,7 @@ SYMBOLS = {
     "mkckks_reencrypt_batch": (_int, [_vp, _vp, _vp, _vp, _u32, _u32]),
     "mkckks_reencrypt_accumulate_batch": (_int, [_vp, _vp, _vp, _vp, _u32, _u32]),
     "mkckks_reencrypt_sum_batch": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u32]),
+    "mkckks_reencrypt_fanout_batch": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u32]),
     "mkckks_modup_batch": (_int, [_vp, _vp, _vp, _u32, _u32]),
     "mkckks_moddown_batch": (_int, [_vp, _vp, _vp, _u32, _u32]),
     "mkckks_keygen": (_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
@@ -397,6 +398,10 @@ class Context:
 
     def reencrypt_sum(self, cts, evks, out, n_clients, n_ct, nl):
         self._check(self._L.mkckks_reencrypt_sum_batch(self._h, _ptr(cts), _ptr(evks), _ptr(out), n_clients, n_ct, nl))
+
+    def reencrypt_fanout(self, ct, evks, out, n_keys, n_ct, nl):
+        """out[k][b] = ReEncrypt(ct[b], evks[k]): one ciphertext batch into n_keys key domains (ModUp shared)."""
+        self._check(self._L.mkckks_reencrypt_fanout_batch(self._h, _ptr(ct), _ptr(evks), _ptr(out), n_keys, n_ct, nl))
 
     def modup(self, c1, digits, n, nl):
         self._check(self._L.mkckks_modup_batch(self._h, _ptr(c1), _ptr(digits), n, nl))

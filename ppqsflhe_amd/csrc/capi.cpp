@@ -302,6 +302,15 @@ int mkckks_reencrypt_sum_batch(mkckks_ctx *c, const uint64_t *cts, const uint64_
         c->eng->reencrypt_sum(cts, evks, out, n_clients, n_ct, nl);
     });
 }
+int mkckks_reencrypt_fanout_batch(mkckks_ctx *c, const uint64_t *ct, const uint64_t *evks, uint64_t *out, uint32_t n_keys,
+                                  uint32_t n_ct, uint32_t nl) {
+    return guarded([&] {
+        need(c && ct && evks && out, "null argument");
+        need(nl >= 1 && nl <= c->eng->params().L, "nl out of range");
+        if (!n_keys || !n_ct) return;
+        c->eng->reencrypt_fanout(ct, evks, out, n_keys, n_ct, nl);
+    });
+}
 int mkckks_modup_batch(mkckks_ctx *c, const uint64_t *c1, uint64_t *digits, uint32_t n, uint32_t nl) {
     return guarded([&] {
         need(c && c1 && digits, "null argument");

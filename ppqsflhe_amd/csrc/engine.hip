@@ -16,6 +16,7 @@
 #include "comm.hpp"
 #include "ntt_radix.hpp"
 #include "qsum_kernels.hpp"
+#include "fanout_kernels.hpp"
 #include "codec_kernels.hpp"
 #include "sampler_kernels.hpp"
 
@@ -480,6 +481,10 @@ Knobs Knobs::from_env() {
     if (const char *e = std::getenv("MKCKKS_QSUM_GROUP")) {
         const int v = std::atoi(e);
         if (v >= 1 && v <= 64) k.qsum_group = (uint32_t)v;
+    }
+    if (const char *e = std::getenv("MKCKKS_FANOUT_GROUP")) {
+        const int v = std::atoi(e);
+        if (v >= 1 && v <= 64) k.fanout_group = (uint32_t)v;
     }
     k.cu_affine = env_flag("MKCKKS_CU_AFFINE", k.cu_affine);
     k.generic_ntt = env_flag("MKCKKS_GENERIC_NTT", k.generic_ntt);
@@ -1419,7 +1424,8 @@ void Engine::moddown_convert(const u64 *til, u64 *pc, u64 *conv, uint32_t cnt, u
 // ApproxModDown on `cnt` polynomials til[item][ext][N] -> out[item] (items out_stride apart, nl limbs each);
 // add (optional): ciphertext array whose c0 is added on even items (KeySwitchInPlace: c0 += ...).
 void Engine::moddown_core(const u64 *til, u64 *pc, u64 *conv, u64 *out, size_t out_stride, const u64 *add,
-                          size_t add_stride, uint32_t cnt, uint32_t nl, bool accumulate, bool p_rows_done) {
+                          size_t add_stride, uint32_t cnt, uint32_t nl, bool accumulate, bool p_rows_done, uint32_t group,
+                          size_t out_gstride) {
     const uint32_t n = ps_.n, K = ps_.K, ext = nl + K, D = ps_.D;
     const u64 *fold = folded_scale(nl), *pinv = p_inverse(nl);
     const bool conv_fused = fast_log_h(tabs_.log_r1, 1u << tabs_.log_r2) != 0;  // conversion inside the column pass
@@ -1430,11 +1436,12 @@ void Engine::moddown_core(const u64 *til, u64 *pc, u64 *conv, u64 *out, size_t o
         moddown_convert(til, pc, conv, cnt, nl, p_rows_done);
         // row pass of the converted limbs with the (ctilde_Q - conv) * P^-1 (+ c0) tail in its copy-out
         NttIo row{conv, out, (size_t)nl * n, out_stride, 0, 0, 0, nl, nl};
-        TailArgs tail{til, add, pinv, pinv + nl, add_stride, ext, 1, accumulate ? 1u : 0u};
+        TailArgs tail{til, add, pinv, pinv + nl, add_stride, ext, 1, accumulate ? 1u : 0u, group, out_gstride};
         launch_row<false>(row, tabs_, cnt, tail, lanes());
         MK_HIP(hipGetLastError());
         return;
     }
+    if (group) throw std::logic_error("grouped ModDown needs the fused tail");
     if (conv_fused) {  // fused conversion + column pass, plain row pass, tail as its own kernel
         moddown_convert(til, pc, conv, cnt, nl, p_rows_done);
         NttIo row{conv, conv, (size_t)nl * n, (size_t)nl * n, 0, 0, 0, nl, nl};
@@ -1583,7 +1590,7 @@ static void launch_row3_inner_int_n(const InnerArgs &a, const NttTables &T, uint
 // integer limbs (q0, P) take k_row3_inner_int, or the row pass + k_inner_product_b on ring sizes without it.
 bool Engine::keyswitch_digits(const u64 *c1, size_t ct_stride, const u64 *evk, u64 *coef, u64 *dig, u64 *til, u64 *pc,
                               uint32_t cnt, uint32_t nl) {
-    const uint32_t n = ps_.n, ext = nl + ps_.K, nparts = ps_.num_parts(nl), D = ps_.D;
+    const uint32_t ext = nl + ps_.K, nparts = ps_.num_parts(nl), D = ps_.D;
     const int row_h = fast_row(tabs_.log_r2, 1u << tabs_.log_r1);
     unsigned long long fp_mask = 0, all_mask = ext >= 64 ? ~0ull : ((1ull << ext) - 1);
     for (uint32_t i = 0; i < nl; ++i)
@@ -1615,6 +1622,14 @@ bool Engine::keyswitch_digits(const u64 *c1, size_t ct_stride, const u64 *evk, u
         MK_HIP(hipGetLastError());
         return pc_fused != nullptr;
     }
+    inner_product_all(c1, ct_stride, evk, dig, til, cnt, nl, mask);
+    return false;
+}
+
+// EvalFastKeySwitchCoreExt on fully transformed digits (k_inner_product_b) over the slots of `mask`
+void Engine::inner_product_all(const u64 *c1, size_t ct_stride, const u64 *evk, const u64 *dig, u64 *til, uint32_t cnt,
+                               uint32_t nl, unsigned long long mask) {
+    const uint32_t n = ps_.n, ext = nl + ps_.K, nparts = ps_.num_parts(nl), D = ps_.D;
     EwGeom g{n, nl, ps_.L};
     switch (nparts) {
         case 1: launch_inner<1>(dig, c1, ct_stride, evk, til, g, d_limb_, ext, D, ps_.alpha, cnt, mask, stream_); break;
@@ -1626,7 +1641,6 @@ bool Engine::keyswitch_digits(const u64 *c1, size_t ct_stride, const u64 *evk, u
         default: throw std::invalid_argument("more than 6 key-switch digits unsupported");
     }
     MK_HIP(hipGetLastError());
-    return false;
 }
 
 void Engine::reencrypt_chunk(const u64 *ct, const u64 *evk, u64 *out, uint32_t cnt, uint32_t nl, bool accumulate) {
@@ -1812,6 +1826,122 @@ void Engine::reencrypt(const u64 *ct, const u64 *evk, u64 *out, uint32_t n_ct, u
     for (uint32_t done = 0; done < n_ct; done += knobs_.chunk) {
         const uint32_t cnt = n_ct - done < knobs_.chunk ? n_ct - done : knobs_.chunk;
         reencrypt_chunk(ct + done * ct_stride, evk, out + done * ct_stride, cnt, nl, accumulate);
+    }
+}
+
+// the three instances of the fused fan-out kernels over one chunk of ciphertexts and one group of keys
+template <int NPARTS, int LOGC>
+static void launch_fan3(const FanArgs &a0, const NttTables &T, uint32_t L, unsigned long long fp_mask,
+                        unsigned long long intq_mask, unsigned long long p_mask, hipStream_t s) {
+    const uint32_t tiles = (1u << T.log_r1) / RowT<LOGC>::ROWS;
+    auto select = [&](unsigned long long m) {
+        FanArgs a = a0;
+        a.slot_mask = m;
+        a.nsel = (uint32_t)__builtin_popcountll(m);
+        return a;
+    };
+    if (p_mask) {  // first: ModDown starts from their output
+        const FanArgs a = select(p_mask);
+        with_int_arith(T, [&](auto ar) {
+            k_fan3_inner_int<NPARTS, LOGC, true, decltype(ar)::value>
+                <<<dim3(tiles * a.nsel * a.items), NTT_THREADS, 0, s>>>(a, T, L);
+        });
+    }
+    if (intq_mask) {
+        const FanArgs a = select(intq_mask);
+        with_int_arith(T, [&](auto ar) {
+            k_fan3_inner_int<NPARTS, LOGC, false, decltype(ar)::value>
+                <<<dim3(tiles * a.nsel * a.items), NTT_THREADS, 0, s>>>(a, T, L);
+        });
+    }
+    if (fp_mask) {
+        const FanArgs a = select(fp_mask);
+        k_fan3_inner_fp<NPARTS, LOGC><<<dim3(tiles * a.nsel * a.items), NTT_THREADS, 0, s>>>(a, T);
+    }
+}
+template <int LOGC>
+static void launch_fan3_n(const FanArgs &a, const NttTables &T, uint32_t nparts, uint32_t L, unsigned long long fp_mask,
+                          unsigned long long intq_mask, unsigned long long p_mask, hipStream_t s) {
+    switch (nparts) {
+        case 1: launch_fan3<1, LOGC>(a, T, L, fp_mask, intq_mask, p_mask, s); break;
+        case 2: launch_fan3<2, LOGC>(a, T, L, fp_mask, intq_mask, p_mask, s); break;
+        case 3: launch_fan3<3, LOGC>(a, T, L, fp_mask, intq_mask, p_mask, s); break;
+        case 4: launch_fan3<4, LOGC>(a, T, L, fp_mask, intq_mask, p_mask, s); break;
+        case 5: launch_fan3<5, LOGC>(a, T, L, fp_mask, intq_mask, p_mask, s); break;
+        case 6: launch_fan3<6, LOGC>(a, T, L, fp_mask, intq_mask, p_mask, s); break;
+        default: throw std::invalid_argument("more than 6 key-switch digits unsupported");
+    }
+}
+
+// the fused fan-out kernels need what keyswitch_digits needs for its fully fused form: radix column kernels, 256- or
+// 512-point rows, fp64-class Q limbs; and integer-class P limbs (their accumulators run through row3_inverse_int)
+bool Engine::fanout_fused(uint32_t nl) const {
+    const int row_h = fast_row(tabs_.log_r2, 1u << tabs_.log_r1);
+    if ((row_h != 4 && row_h != 9) || fast_log_h(tabs_.log_r1, 1u << tabs_.log_r2) == 0) return false;
+    for (uint32_t k = 0; k < ps_.K; ++k)
+        if (tabs_.h_fp_of[ps_.L + k]) return false;
+    for (uint32_t i = 0; i < nl; ++i)
+        if (tabs_.h_fp_of[i]) return true;
+    return false;
+}
+
+// out[k][b] = ReEncrypt(ct[b], evks[k]).  Per chunk of ciphertexts the key-independent half of the key switch runs
+// once: INTT of c1 + ModUp conversions + forward column pass (modup_core).  Fused path (N = 2^14, 2^16, 2^17 with
+// fp64-class Q limbs), per group of keys:
+//   row pass of every converted digit once per (ciphertext, limb, row tile), then per key the inner product
+//   (+ inverse row pass on the P limbs)                                        k_fan3_inner_fp, k_fan3_inner_int
+//   ApproxModDown of all (key, ciphertext, component) polynomials at once      moddown_core (grouped tail)
+// Other ring sizes / arithmetic classes: ModUp with its row pass once, then k_inner_product_b + ModDown per key.
+void Engine::reencrypt_fanout(const u64 *ct, const u64 *evks, u64 *out, uint32_t n_keys, uint32_t n_ct, uint32_t nl) {
+    need_device();
+    check_nl(nl);
+    if (!n_keys || !n_ct) return;
+    const uint32_t n = ps_.n, K = ps_.K, ext = nl + K, nparts = ps_.num_parts(nl), D = ps_.D;
+    const size_t ct_words = (size_t)2 * nl * n, evk_words = (size_t)ps_.beta * 2 * D * n;
+    {
+        const uintptr_t c_lo = (uintptr_t)ct, c_hi = c_lo + (size_t)n_ct * ct_words * sizeof(u64);
+        const uintptr_t o_lo = (uintptr_t)out, o_hi = o_lo + (size_t)n_keys * n_ct * ct_words * sizeof(u64);
+        if (o_lo < c_hi && c_lo < o_hi) throw std::invalid_argument("fan-out re-encryption cannot write over its input");
+    }
+    const bool fused = fanout_fused(nl);
+    unsigned long long fp_mask = 0, intq_mask = 0, p_mask = 0, all_mask = ext >= 64 ? ~0ull : ((1ull << ext) - 1);
+    for (uint32_t i = 0; i < nl; ++i) (tabs_.h_fp_of[i] ? fp_mask : intq_mask) |= 1ull << i;
+    for (uint32_t i = nl; i < ext; ++i) p_mask |= 1ull << i;
+    const uint32_t chunk = std::min(knobs_.chunk, n_ct), group = fused ? std::min(knobs_.fanout_group, n_keys) : 1u;
+    const size_t w_coef = (size_t)chunk * nl * n, w_dig = (size_t)chunk * nparts * ext * n;
+    const size_t w_til = (size_t)group * chunk * 2 * ext * n, w_pc = (size_t)group * chunk * 2 * K * n;
+    const size_t w_conv = (size_t)group * chunk * 2 * nl * n;
+    u64 *ws = workspace(w_coef + w_dig + w_til + w_pc + w_conv);
+    u64 *coef = ws, *dig = coef + w_coef, *til = dig + w_dig, *pc = til + w_til, *conv = pc + w_pc;
+    const bool wide_rows = fast_row(tabs_.log_r2, 1u << tabs_.log_r1) == 9;
+    for (uint32_t b0 = 0; b0 < n_ct; b0 += chunk) {
+        const uint32_t cnt = std::min(chunk, n_ct - b0);
+        const u64 *ct0 = ct + (size_t)b0 * ct_words, *c1 = ct0 + (size_t)nl * n;
+        {   // the shared half; on the fused path the row passes are left to the fan-out kernels
+            struct Reset {
+                bool &flag;
+                ~Reset() { flag = false; }
+            } reset{skip_rows_};
+            skip_rows_ = fused;
+            modup_core(c1, ct_words, coef, dig, cnt, nl, fused);
+        }
+        for (uint32_t k0 = 0; k0 < n_keys; k0 += group) {
+            const uint32_t gk = std::min(group, n_keys - k0);
+            const u64 *evk0 = evks + (size_t)k0 * evk_words;
+            u64 *out0 = out + ((size_t)k0 * n_ct + b0) * ct_words;
+            if (fused) {
+                FanArgs a{dig, c1, evk0, til, pc, ct_words, evk_words, nl, ext, D, ps_.alpha, cnt, gk, K, 0, 0};
+                if (wide_rows) launch_fan3_n<3>(a, tabs_, nparts, ps_.L, fp_mask, intq_mask, p_mask, stream_);
+                else launch_fan3_n<2>(a, tabs_, nparts, ps_.L, fp_mask, intq_mask, p_mask, stream_);
+                MK_HIP(hipGetLastError());
+                // polynomial p = (key * cnt + b) * 2 + comp: c0 of ciphertext b, output of key k0 + key
+                moddown_core(til, pc, conv, out0, (size_t)nl * n, ct0, ct_words, gk * 2 * cnt, nl, false, true, 2 * cnt,
+                             (size_t)n_ct * ct_words);
+            } else {
+                inner_product_all(c1, ct_words, evk0, dig, til, cnt, nl, all_mask);
+                moddown_core(til, pc, conv, out0, (size_t)nl * n, ct0, ct_words, 2 * cnt, nl, false, false);
+            }
+        }
     }
 }
 

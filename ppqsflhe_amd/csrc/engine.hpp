@@ -58,6 +58,9 @@ struct Lanes {
 // measured best; every non-default value has a parity test (tests/test_gpu_parity.py).
 struct Knobs {
     uint32_t chunk = 16;         // MKCKKS_CHUNK: ciphertexts per workspace chunk
+    uint32_t fanout_group = 7;   // MKCKKS_FANOUT_GROUP: keys per pass of the fan-out re-encryption (bounds the til / ModDown
+                                 // workspace; ModUp is shared by all keys whatever the group; 7 is the best of 1, 2, 4, 7 at both
+                                 // measured shapes, profiles/fanout_ab.txt)
     uint32_t qsum_group = 8;     // MKCKKS_QSUM_GROUP: clients per pass of the merged n-client flow (one forward transform of
                                  // the summed ModDown conversions per group: 8 is +2.7 % against 4, 2 is -6.6 %)
     bool cu_affine = true;       // MKCKKS_CU_AFFINE=0: plain XCD-aware placement; default: workgroups that share operand tiles on the same CU (group_member)
@@ -114,6 +117,9 @@ public:
 
     // out[b] = sum over clients of ReEncrypt(cts[c][b], evks[c]); cts [C][n_ct][2][nl][N], evks [C][beta][2][D][N]
     void reencrypt_sum(const u64 *cts, const u64 *evks, u64 *out, uint32_t n_clients, uint32_t n_ct, uint32_t nl);
+    // out[k][b] = ReEncrypt(ct[b], evks[k]): ModUp (and, on the fused path, the digits' row transforms) once per
+    // ciphertext; ct [n_ct][2][nl][N] read-only, evks [n_keys][beta][2][D][N], out [n_keys][n_ct][2][nl][N]
+    void reencrypt_fanout(const u64 *ct, const u64 *evks, u64 *out, uint32_t n_keys, uint32_t n_ct, uint32_t nl);
     void modup(const u64 *c1, u64 *digits, uint32_t n, uint32_t nl);
     void moddown(const u64 *in, u64 *out, uint32_t n, uint32_t nl);
     // accumulate: out[b] += ReEncrypt(ct[b]) (coefficient-wise, mod q) -- the fold into a running aggregate
@@ -177,7 +183,11 @@ private:
     bool keyswitch_digits(const u64 *c1, size_t ct_stride, const u64 *evk, u64 *coef, u64 *dig, u64 *til, u64 *pc,
                           uint32_t cnt, uint32_t nl);
     void moddown_core(const u64 *til, u64 *pc, u64 *conv, u64 *out, size_t out_stride, const u64 *add,
-                      size_t add_stride, uint32_t cnt, uint32_t nl, bool accumulate, bool p_rows_done = false);
+                      size_t add_stride, uint32_t cnt, uint32_t nl, bool accumulate, bool p_rows_done = false,
+                      uint32_t group = 0, size_t out_gstride = 0);
+    void inner_product_all(const u64 *c1, size_t ct_stride, const u64 *evk, const u64 *dig, u64 *til, uint32_t cnt,
+                           uint32_t nl, unsigned long long mask);
+    bool fanout_fused(uint32_t nl) const;
     void moddown_convert(const u64 *til, u64 *pc, u64 *conv, uint32_t cnt, uint32_t nl, bool rows_done);
     int conv_src_mode(const DevConv &cv) const;
 

@@ -1191,7 +1191,15 @@ struct TailArgs {
     uint32_t ext;        // nl + K
     uint32_t enabled;
     uint32_t accumulate; // out += result (running aggregate over clients) instead of out = result
+    // fan-out (one ciphertext batch, many keys): polynomial p belongs to key p / group; it takes the c0 of ciphertext
+    // (p % group) / 2 and goes to out + (p / group) * out_gstride + (p % group) * out_stride.  0: plain indexing
+    uint32_t group = 0;
+    size_t out_gstride = 0;
 };
+MK_D uint32_t tail_add_item(const TailArgs &t, uint32_t poly) { return (t.group ? poly % t.group : poly) >> 1; }
+MK_D size_t tail_out_offset(const TailArgs &t, size_t out_stride, uint32_t poly) {
+    return t.group ? (size_t)(poly / t.group) * t.out_gstride + (size_t)(poly % t.group) * out_stride : (size_t)poly * out_stride;
+}
 
 // Row pass over rows of R2 = H*H contiguous words: one workgroup = S consecutive rows (S*R2 contiguous
 // words).  The side that needs per-thread contiguous runs goes through LDS with coalesced 16-B accesses.
@@ -1254,8 +1262,9 @@ __global__ __launch_bounds__(NTT_THREADS) void k_ntt_row_r(NttIo io, NttTables T
             const u64 pi = tail.pinv[sl], pi_sh = tail.pinv_sh[sl];
             const u64 *tq = tail.til + ((size_t)poly * tail.ext + sl) * n + (size_t)row0 * R;
             const u64 *c0 = (tail.add && (poly & 1) == 0)
-                                ? tail.add + (size_t)(poly >> 1) * tail.add_stride + (size_t)sl * n + (size_t)row0 * R
+                                ? tail.add + (size_t)tail_add_item(tail, poly) * tail.add_stride + (size_t)sl * n + (size_t)row0 * R
                                 : nullptr;
+            if (tail.group) dst = io.out + tail_out_offset(tail, io.out_stride, poly) + (size_t)(io.out_slot0 + sl) * n + (size_t)row0 * R;
             for (int i = 0; i < PAIRS; ++i) {
                 const int e = wave_pair<LOG_H>(i);
                 const int gg = (2 * e) / R, xx = (2 * e) % R;
@@ -1545,8 +1554,9 @@ __global__ __launch_bounds__(NTT_THREADS) void k_ntt_row3(NttIo io, NttTables T,
             const u64 pi = tail.pinv[sl], pi_sh = tail.pinv_sh[sl];
             const u64 *tq = tail.til + ((size_t)poly * tail.ext + sl) * n + (size_t)row0 * R;
             const u64 *c0 = (tail.add && (poly & 1) == 0)
-                                ? tail.add + (size_t)(poly >> 1) * tail.add_stride + (size_t)sl * n + (size_t)row0 * R
+                                ? tail.add + (size_t)tail_add_item(tail, poly) * tail.add_stride + (size_t)sl * n + (size_t)row0 * R
                                 : nullptr;
+            if (tail.group) dst = io.out + tail_out_offset(tail, io.out_stride, poly) + (size_t)(io.out_slot0 + sl) * n + (size_t)row0 * R;
             for (int e = threadIdx.x; e < S * R / 2; e += NTT_THREADS) {
                 const int gg = (2 * e) / R, xx = (2 * e) % R;
                 const ulong2 tt = reinterpret_cast<const ulong2 *>(tq)[e];

@@ -13,7 +13,8 @@
 // per-client programs produce (PRE is deterministic; tests/test_cli_hosts.py).
 // After --back: the n-1 re-encryptions of the aggregate into the other clients' key domains (the reference's
 // s_changeCipherDomain_c2_c1, server_fns.sh:76-80: changeCipherDomain <cc> <rekey_back_c> <aggfile> <out_c>) -- the
-// aggregate stays in HBM, one mkckks_reencrypt_batch per key; each file equals changeCipherDomain run on <output_aggfile>.
+// aggregate stays in HBM, ONE mkckks_reencrypt_fanout_batch over all back keys (which stay resident by file name under
+// --rounds); each file equals changeCipherDomain run on <output_aggfile>.  MKCKKS_BACK_LOOP=1: one call per key.
 // Binary (MKWS) envelopes take the I/O pipeline of iopipe.hpp: files are indexed, not loaded; reader threads fill pinned
 // slots, uploads run beside the reads, residues are range-checked on the device, results are written by pwrite() from
 // pinned slots.  MKCKKS_SYNC_IO=1 forces the synchronous path (every ciphertext through read_envelope / decode_ct /
@@ -62,6 +63,7 @@ struct ServerState {
     explicit ServerState(Session &s) : cache(s) {}
     std::map<std::string, std::vector<uint64_t>> keys;  // re-encryption keys by file name, loaded once per process
     RoundCache cache;
+    std::vector<std::string> back_names;  // back keys resident in cache.back_evk, slot by slot (by file name)
     double t_ctx = 0;      // ms: context creation
     size_t n_ct = 0;       // ciphertexts re-encrypted / aggregated so far
 };
@@ -73,6 +75,9 @@ static const std::vector<uint64_t> *cached_key(Session &s, ServerState &st, cons
     if (!load_eval_key(s, path, evk)) return nullptr;
     return &(st.keys[path] = std::move(evk));
 }
+
+static int run_back_leg(Session &s, ServerState &st, const RoundArgs &a, const std::vector<AggItem> &items, const AggResult &agg,
+                        const Json &outputJson, bool binary, bool pinned_out, unsigned threads);
 
 // one round; 0 on success, 1 after an "[round] ERROR" line
 static int run_round(Session &s, ServerState &st, const RoundArgs &a) {
@@ -189,18 +194,37 @@ static int run_round(Session &s, ServerState &st, const RoundArgs &a) {
         agg = finish_aggregate(s, items, d_sum, first, n_clients, outputJson);
     }
     if (!pinned_out) write_envelope(outputJson, a.output_file, binary);
+    if (int rc = run_back_leg(s, st, a, items, agg, outputJson, binary, pinned_out, threads)) return rc;
+    st.n_ct += n_clients * items.size();
+    std::cout << "[round] Re-encryption and aggregation completed successfully. Output: " << a.output_file << std::endl;
+    return 0;
+}
+
+// The distribution leg (--back): the aggregate, still in HBM, re-encrypted into every other client's key domain.  All
+// back keys of the round live in ONE device array and the leg is one mkckks_reencrypt_fanout_batch call per group of
+// keys (the key-independent half of the key switch runs once per ciphertext instead of once per key).  The keys stay
+// resident from round to round by FILE NAME, slot by slot, under the same assumption as the inbound keys: a file that
+// keeps its name keeps its content for the life of the process (keys rotated in place need a new process or a new name).
+// MKCKKS_BACK_LOOP=1 keeps the per-key loop (one upload + one mkckks_reencrypt_batch per key); both write the same bytes.
+static int run_back_leg(Session &s, ServerState &st, const RoundArgs &a, const std::vector<AggItem> &items, const AggResult &agg,
+                        const Json &outputJson, bool binary, bool pinned_out, unsigned threads) {
+    if (a.back_keys.empty()) return 0;
+    const double t_leg = now_ms();
+    const uint32_t N = s.N();
+    const size_t evk_words = (size_t)s.beta() * 2 * s.D() * N, B = items.size();
+    const bool loop = std::getenv("MKCKKS_BACK_LOOP") && std::atoi(std::getenv("MKCKKS_BACK_LOOP")) != 0;
+    // keys in order up to the first one that does not load: the files before it are written, then the error (as the loop did)
+    std::vector<const std::vector<uint64_t> *> keys;
     for (size_t k = 0; k < a.back_keys.size(); ++k) {
         const std::vector<uint64_t> *evk = cached_key(s, st, a.back_keys[k]);
-        if (!evk) {
-            std::cerr << "[round] ERROR: Failed to load ReKey from " << a.back_keys[k] << std::endl;
-            return 1;
-        }
+        if (!evk) break;
+        keys.push_back(evk);
+    }
+    const size_t n_keys = keys.size();
+    size_t uploaded = 0;
+    auto write_one = [&](size_t k, uint64_t *d_back) {
         Json backJson = outputJson;  // layer / shape carried over; blobs replaced below
-        if (!items.empty()) {
-            const size_t words = items.size() * (size_t)2 * agg.meta.nl * N;
-            uint64_t *d_back = st.cache.grow(st.cache.back, words), *d_back_evk = st.cache.grow(st.cache.back_evk, evk_words);
-            Session::check(mkckks_upload(s.ctx(), d_back_evk, evk->data(), evk_words * 8));
-            Session::check(mkckks_reencrypt_batch(s.ctx(), agg.d_out, d_back_evk, d_back, (uint32_t)items.size(), agg.meta.nl));
+        if (B) {
             if (pinned_out) {
                 write_envelope_from_device(s, *st.cache.ring, items, d_back, agg.meta, backJson, a.back_outs[k], threads);
             } else {
@@ -211,9 +235,52 @@ static int run_round(Session &s, ServerState &st, const RoundArgs &a) {
             write_envelope(backJson, a.back_outs[k], binary);
         }
         std::cout << "[round] aggregate re-encrypted with " << a.back_keys[k] << " -> " << a.back_outs[k] << "\n";
+    };
+    if (!loop && B && n_keys) {
+        const size_t words = B * (size_t)2 * agg.meta.nl * N;
+        // keys per call: the outputs of one call are bounded (MKCKKS_BACK_MAX_MIB, default 16 GiB) beside the round's buffers
+        size_t max_mib = 16384;
+        if (const char *e = std::getenv("MKCKKS_BACK_MAX_MIB")) max_mib = (size_t)std::max(1, std::atoi(e));
+        const size_t per_call = std::max<size_t>(1, std::min(n_keys, (max_mib << 20) / (words * 8)));
+        if (n_keys * evk_words > st.cache.back_evk.words) st.back_names.clear();  // the array moves: nothing is resident
+        uint64_t *d_evks = st.cache.grow(st.cache.back_evk, n_keys * evk_words);
+        uint64_t *d_back = st.cache.grow(st.cache.back, per_call * words);
+        st.back_names.resize(std::max(st.back_names.size(), n_keys));
+        for (size_t k = 0; k < n_keys; ++k) {
+            if (st.back_names[k] == a.back_keys[k]) continue;  // resident in its slot
+            st.back_names[k].clear();
+            Session::check(mkckks_upload(s.ctx(), d_evks + k * evk_words, keys[k]->data(), evk_words * 8));
+            st.back_names[k] = a.back_keys[k];
+            ++uploaded;
+        }
+        for (size_t k0 = 0; k0 < n_keys; k0 += per_call) {
+            const size_t gk = std::min(per_call, n_keys - k0);
+            Session::check(mkckks_reencrypt_fanout_batch(s.ctx(), agg.d_out, d_evks + k0 * evk_words, d_back, (uint32_t)gk,
+                                                         (uint32_t)B, agg.meta.nl));
+            for (size_t k = 0; k < gk; ++k) write_one(k0 + k, d_back + k * words);
+        }
+    } else {
+        for (size_t k = 0; k < n_keys; ++k) {  // one key at a time through slot 0 of the key array
+            uint64_t *d_back = nullptr;
+            if (B) {
+                const size_t words = B * (size_t)2 * agg.meta.nl * N;
+                st.back_names.clear();
+                d_back = st.cache.grow(st.cache.back, words);
+                uint64_t *d_back_evk = st.cache.grow(st.cache.back_evk, evk_words);
+                Session::check(mkckks_upload(s.ctx(), d_back_evk, keys[k]->data(), evk_words * 8));
+                ++uploaded;
+                Session::check(mkckks_reencrypt_batch(s.ctx(), agg.d_out, d_back_evk, d_back, (uint32_t)B, agg.meta.nl));
+            }
+            write_one(k, d_back);
+        }
     }
-    st.n_ct += n_clients * items.size();
-    std::cout << "[round] Re-encryption and aggregation completed successfully. Output: " << a.output_file << std::endl;
+    if (n_keys < a.back_keys.size()) {
+        std::cerr << "[round] ERROR: Failed to load ReKey from " << a.back_keys[n_keys] << std::endl;
+        return 1;
+    }
+    const double ms = now_ms() - t_leg;
+    std::cout << "[round] back leg: " << n_keys << " keys x " << B << " ciphertexts in " << ms << " ms -> "
+              << (double)(n_keys * B) / ms * 1e3 << " ciphertexts/s, " << uploaded << " key(s) uploaded\n";
     return 0;
 }
 
