@@ -169,6 +169,37 @@ int mkckks_reencrypt_sum_batch(mkckks_ctx *c, const uint64_t *d_cts, const uint6
  * n_ct, nl).  d_out must not overlap d_ct (MKCKKS_E_INVALID); n_keys == 0 or n_ct == 0 is a no-op. */
 int mkckks_reencrypt_fanout_batch(mkckks_ctx *c, const uint64_t *d_ct, const uint64_t *d_evks, uint64_t *d_out,
                                   uint32_t n_keys, uint32_t n_ct, uint32_t nl);
+/* ---- compact ciphertexts for the distribution leg ------------------------------
+ * What goes back to a client is only ever decrypted, and a ciphertext that will only be decrypted needs enough modulus
+ * for scale * |value| + noise and nothing more (OpenFHE: cc->Compress(ct, towersLeft), "before sending the encrypted
+ * result for decryption").  prefix(ct, m) = the first m limbs of both components: a lower level of the same RNS
+ * ciphertext, valid while the encrypted coefficients stay below q_0 * ... * q_{m-1} / 2.
+ * Order: the prefix is cut while the ciphertext is at noiseScaleDeg 2 (after EvalMult(., 1/n)), the key switch runs at
+ * the low level, the rescale comes last -- the key-switch noise is added at scale ~ 2^(2p) and divided away by the
+ * closing rescale.  (Rescale first, then cut, then key switch -- OpenFHE's Compress + ReEncrypt -- costs 5-8 bits.)
+ * Headroom: for slot values bounded by A every plaintext coefficient is bounded by S * A (S the input's scaling factor,
+ * ~ 2^(2p)), so nl_out = k is enough when q_0 * ... * q_k / 2 > S * A + noise.  With a 60-bit q_0 and p-bit scaling
+ * limbs: k = 1 holds |values| < 2^(58-p) (256 at p = 50, 2^18 at p = 40; one bit is kept for noise and for sums that
+ * exceed A), every further limb adds p bits.  The bound is on coefficients, so constant vectors reach it; beyond it
+ * decryption wraps and returns garbage, not a small error.  The library cannot check it (the values are encrypted): it
+ * is the deployment's choice, like the scaling size.
+ *
+ * compress for decryption: d_out[b] = Rescale(prefix(d_in[b], nl_out + 1)) -- drops limb nl_out with rounding
+ * (ModReduceInternalInPlace on the truncated ciphertext).  d_in u64[n_ct][2][nl_in][N] (read in place, strided),
+ * d_out u64[n_ct][2][nl_out][N], 1 <= nl_out < nl_in <= L.  Bit-identical to mkckks_rescale_batch at nl_out + 1 on a
+ * packed copy of the prefix.  New scaling factor: old / q_{nl_out}; noiseScaleDeg 2 -> 1.  d_out must not overlap d_in
+ * (MKCKKS_E_INVALID); n_ct == 0 is a no-op. */
+int mkckks_compress_batch(mkckks_ctx *c, const uint64_t *d_in, uint64_t *d_out, uint32_t n_ct, uint32_t nl_in,
+                          uint32_t nl_out);
+/* compact fan-out: d_out[k][b] = Rescale(ReEncrypt(prefix(d_ct[b], nl_out + 1), d_evks[k])).
+ * d_ct u64[n_ct][2][nl_in][N] read-only (the prefix is read in place), d_evks as mkckks_reencrypt_fanout_batch, d_out
+ * u64[n_keys][n_ct][2][nl_out][N].  Bit-identical, for every k, to: packed copy of the prefix ->
+ * mkckks_reencrypt_fanout_batch at nl_out + 1 -> mkckks_rescale_batch at nl_out + 1.  The key switch has
+ * ceil((nl_out + 1) / alpha) digits over nl_out + 1 + K limbs instead of the full level's; the closing rescale is one
+ * pass over all (key, ciphertext, component) polynomials of a key group.  d_out must not overlap d_ct
+ * (MKCKKS_E_INVALID); n_keys == 0 or n_ct == 0 is a no-op. */
+int mkckks_reencrypt_fanout_compact_batch(mkckks_ctx *c, const uint64_t *d_ct, const uint64_t *d_evks, uint64_t *d_out,
+                                          uint32_t n_keys, uint32_t n_ct, uint32_t nl_in, uint32_t nl_out);
 /* stages of the above, exposed for parity tests and profiling:
  * KeySwitchHYBRID::EvalKeySwitchPrecomputeCore: c1 u64[n][nl][N] ->
  * digits u64[n][nparts][nl+K][N]; ApproxModDown: u64[n][nl+K][N] -> u64[n][nl][N]. */

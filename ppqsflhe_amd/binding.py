@@ -74,6 +74,8 @@ SYMBOLS = {
     "mkckks_reencrypt_accumulate_batch": (_int, [_vp, _vp, _vp, _vp, _u32, _u32]),
     "mkckks_reencrypt_sum_batch": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u32]),
     "mkckks_reencrypt_fanout_batch": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u32]),
+    "mkckks_compress_batch": (_int, [_vp, _vp, _vp, _u32, _u32, _u32]),
+    "mkckks_reencrypt_fanout_compact_batch": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32]),
     "mkckks_modup_batch": (_int, [_vp, _vp, _vp, _u32, _u32]),
     "mkckks_moddown_batch": (_int, [_vp, _vp, _vp, _u32, _u32]),
     "mkckks_keygen": (_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
@@ -402,6 +404,15 @@ class Context:
     def reencrypt_fanout(self, ct, evks, out, n_keys, n_ct, nl):
         """out[k][b] = ReEncrypt(ct[b], evks[k]): one ciphertext batch into n_keys key domains (ModUp shared)."""
         self._check(self._L.mkckks_reencrypt_fanout_batch(self._h, _ptr(ct), _ptr(evks), _ptr(out), n_keys, n_ct, nl))
+
+    def compress(self, inp, out, n_ct, nl_in, nl_out):
+        """out[b] = Rescale(first nl_out + 1 limbs of inp[b]): a ciphertext that will only be decrypted, at nl_out limbs."""
+        self._check(self._L.mkckks_compress_batch(self._h, _ptr(inp), _ptr(out), n_ct, nl_in, nl_out))
+
+    def reencrypt_fanout_compact(self, ct, evks, out, n_keys, n_ct, nl_in, nl_out):
+        """out[k][b] = Rescale(ReEncrypt(first nl_out + 1 limbs of ct[b], evks[k])): the fan-out written at nl_out limbs."""
+        self._check(self._L.mkckks_reencrypt_fanout_compact_batch(self._h, _ptr(ct), _ptr(evks), _ptr(out), n_keys, n_ct,
+                                                                  nl_in, nl_out))
 
     def modup(self, c1, digits, n, nl):
         self._check(self._L.mkckks_modup_batch(self._h, _ptr(c1), _ptr(digits), n, nl))

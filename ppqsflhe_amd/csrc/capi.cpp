@@ -311,6 +311,32 @@ int mkckks_reencrypt_fanout_batch(mkckks_ctx *c, const uint64_t *ct, const uint6
         c->eng->reencrypt_fanout(ct, evks, out, n_keys, n_ct, nl);
     });
 }
+// argument rules shared by the two compact entry points; the overlap test works on addresses only
+static void need_compact_args(const mk::ParamSet &ps, const uint64_t *in, const uint64_t *out, uint32_t n_keys, uint32_t n_ct,
+                              uint32_t nl_in, uint32_t nl_out) {
+    need(nl_out >= 1 && nl_out < nl_in && nl_in <= ps.L, "need 1 <= nl_out < nl_in <= L");
+    const size_t poly_bytes = (size_t)n_ct * 2 * ps.n * sizeof(uint64_t);
+    const uintptr_t i_lo = (uintptr_t)in, i_hi = i_lo + poly_bytes * nl_in;
+    const uintptr_t o_lo = (uintptr_t)out, o_hi = o_lo + (size_t)n_keys * poly_bytes * nl_out;
+    need(!(o_lo < i_hi && i_lo < o_hi), "output overlaps input");
+}
+int mkckks_compress_batch(mkckks_ctx *c, const uint64_t *in, uint64_t *out, uint32_t n_ct, uint32_t nl_in, uint32_t nl_out) {
+    return guarded([&] {
+        need(c && in && out, "null argument");
+        need_compact_args(c->eng->params(), in, out, 1, n_ct, nl_in, nl_out);
+        if (!n_ct) return;
+        c->eng->compress(in, out, n_ct, nl_in, nl_out);
+    });
+}
+int mkckks_reencrypt_fanout_compact_batch(mkckks_ctx *c, const uint64_t *ct, const uint64_t *evks, uint64_t *out,
+                                          uint32_t n_keys, uint32_t n_ct, uint32_t nl_in, uint32_t nl_out) {
+    return guarded([&] {
+        need(c && ct && evks && out, "null argument");
+        need_compact_args(c->eng->params(), ct, out, n_keys, n_ct, nl_in, nl_out);
+        if (!n_keys || !n_ct) return;
+        c->eng->reencrypt_fanout_compact(ct, evks, out, n_keys, n_ct, nl_in, nl_out);
+    });
+}
 int mkckks_modup_batch(mkckks_ctx *c, const uint64_t *c1, uint64_t *digits, uint32_t n, uint32_t nl) {
     return guarded([&] {
         need(c && c1 && digits, "null argument");

@@ -204,18 +204,21 @@ __global__ void k_switch_modulus(const u64 *last, u64 *out, EwGeom g, const Limb
 }
 
 // DropLastElementAndScale tail: out[item][i] = (in[item][i] - tmp[item][i]) * c[i],
-// c = q_last^-1 (times the EvalMult constant when the two are fused).  in has nl slots, out nl-1.
-__global__ void k_sub_mul(const u64 *in, const u64 *tmp, u64 *out, EwGeom g, const LimbConst *limb,
-                          const u64 *c, const u64 *c_sh) {
+// c = q_last^-1 (times the EvalMult constant when the two are fused).  in: items in_ext slots apart (the first nl are
+// this level's), tmp nl-1 slots; out nl-1 slots, item p at (p / group) * out_gstride + (p % group) * (nl-1) * N
+// (group 0: packed).
+__global__ void k_sub_mul(const u64 *in, uint32_t in_ext, const u64 *tmp, u64 *out, EwGeom g, const LimbConst *limb,
+                          const u64 *c, const u64 *c_sh, uint32_t group, size_t out_gstride) {
     EW_PROLOGUE(g.nl - 1)
     const u64 q = limb[slot].q;
-    const ulong2 x = ld2(in + ((size_t)item * g.nl + slot) * g.n + idx);
+    const ulong2 x = ld2(in + ((size_t)item * in_ext + slot) * g.n + idx);
     const size_t off = ((size_t)item * (g.nl - 1) + slot) * g.n + idx;
     const ulong2 t = ld2(tmp + off);
     ulong2 r;
     r.x = shoup_mul(sub_mod(x.x, t.x, q), c[slot], c_sh[slot], q);
     r.y = shoup_mul(sub_mod(x.y, t.y, q), c[slot], c_sh[slot], q);
-    st2(out + off, r);
+    const size_t o = group ? (size_t)(item / group) * out_gstride + ((size_t)(item % group) * (g.nl - 1) + slot) * g.n + idx : off;
+    st2(out + o, r);
 }
 
 // ApproxModDown tail: out[item][i] = (in[item][i] - conv[item][i]) * Pinv[i] (+ add[item/2][i] on even items).
@@ -1244,39 +1247,31 @@ static void launch_switch_col(const u64 *last, u64 *out, const NttTables &T, uin
     if (nf) k_switch_col<LOG_H, AR_FP><<<dim3(tiles, nf, items), NTT_THREADS, 0, s>>>(last, out, T, n_targets, q_last, mf);
 }
 
-void Engine::rescale(const u64 *in, u64 *out, uint32_t n_ct, uint32_t nl, const std::vector<u64> *factors) {
-    need_device();
-    check_nl(nl);
-    if (nl < 2) throw std::invalid_argument("rescale needs at least 2 limbs");
-    if (!n_ct) return;
-    const uint32_t n = ps_.n, last = nl - 1, items = 2 * n_ct;
+const u64 *Engine::rescale_consts(uint32_t nl, const std::vector<u64> *factors) {
     // constants c_i = q_last^-1 (* EvalMult constant) mod q_i, cached on the device per (level, constant): no host
     // synchronisation inside a server step
+    const uint32_t last = nl - 1;
     std::string key = "resc_" + std::to_string(nl);
     if (factors)
         for (uint32_t i = 0; i < last; ++i) key += "_" + std::to_string((*factors)[i]);
-    const u64 *d_c = nullptr;
-    {
-        auto it = vec_cache_.find(key);
-        if (it != vec_cache_.end()) {
-            d_c = it->second;
-        } else {
-            std::vector<u64> c(2 * last);
-            for (uint32_t i = 0; i < last; ++i) {
-                u64 v = ps_.q_inv_mod(last, i);
-                if (factors) v = h_mulmod(v, (*factors)[i], ps_.moduli[i]);
-                c[i] = v;
-                c[last + i] = h_shoup(v, ps_.moduli[i]);
-            }
-            if (vec_cache_.size() > 4096) throw std::runtime_error("too many distinct rescale constants cached");
-            d_c = limb_vector(key, c);
-        }
+    auto it = vec_cache_.find(key);
+    if (it != vec_cache_.end()) return it->second;
+    std::vector<u64> c(2 * last);
+    for (uint32_t i = 0; i < last; ++i) {
+        u64 v = ps_.q_inv_mod(last, i);
+        if (factors) v = h_mulmod(v, (*factors)[i], ps_.moduli[i]);
+        c[i] = v;
+        c[last + i] = h_shoup(v, ps_.moduli[i]);
     }
-    const size_t w_last = (size_t)items * n, w_tmp = (size_t)items * last * n;
-    u64 *ws = workspace(w_last + w_tmp);
-    u64 *d_last = ws, *d_tmp = ws + w_last;
+    if (vec_cache_.size() > 4096) throw std::runtime_error("too many distinct rescale constants cached");
+    return limb_vector(key, c);
+}
+
+void Engine::rescale_core(const u64 *in, uint32_t in_limbs, u64 *out, uint32_t items, uint32_t nl, const u64 *d_c, u64 *d_last,
+                          u64 *d_tmp, uint32_t group, size_t out_gstride) {
+    const uint32_t n = ps_.n, last = nl - 1;
     // 1. dropped limb -> COEFFICIENT format
-    NttIo io{in, d_last, (size_t)nl * n, (size_t)n, last, 0, last, 1, nl};
+    NttIo io{in, d_last, (size_t)in_limbs * n, (size_t)n, last, 0, last, 1, nl};
     ntt_passes(io, tabs_, items, true, nullptr, nullptr, lanes());
     const int col_h = fast_log_h(tabs_.log_r1, 1u << tabs_.log_r2);
     if (col_h >= 2 && row_tail_supported(tabs_)) {
@@ -1289,7 +1284,7 @@ void Engine::rescale(const u64 *in, u64 *out, uint32_t n_ct, uint32_t nl, const 
         }
         MK_HIP(hipGetLastError());
         NttIo row{d_tmp, out, (size_t)last * n, (size_t)last * n, 0, 0, 0, last, last};
-        TailArgs tail{in, nullptr, d_c, d_c + last, 0, nl, 1, 0u};
+        TailArgs tail{in, nullptr, d_c, d_c + last, 0, in_limbs, 1, 0u, group, out_gstride};
         launch_row<false>(row, tabs_, items, tail, lanes());
         MK_HIP(hipGetLastError());
         return;
@@ -1299,8 +1294,42 @@ void Engine::rescale(const u64 *in, u64 *out, uint32_t n_ct, uint32_t nl, const 
     k_switch_modulus<<<ew_grid(n, last, items), EW_THREADS, 0, stream_>>>(d_last, d_tmp, g, d_limb_, ps_.moduli[last]);
     MK_HIP(hipGetLastError());
     ntt_launch(d_tmp, items, last, last, false, nullptr, nullptr);
-    k_sub_mul<<<ew_grid(n, last, items), EW_THREADS, 0, stream_>>>(in, d_tmp, out, g, d_limb_, d_c, d_c + last);
+    k_sub_mul<<<ew_grid(n, last, items), EW_THREADS, 0, stream_>>>(in, in_limbs, d_tmp, out, g, d_limb_, d_c, d_c + last, group,
+                                                                out_gstride);
     MK_HIP(hipGetLastError());
+}
+
+void Engine::rescale(const u64 *in, u64 *out, uint32_t n_ct, uint32_t nl, const std::vector<u64> *factors) {
+    need_device();
+    check_nl(nl);
+    if (nl < 2) throw std::invalid_argument("rescale needs at least 2 limbs");
+    if (!n_ct) return;
+    const uint32_t n = ps_.n, last = nl - 1, items = 2 * n_ct;
+    const u64 *d_c = rescale_consts(nl, factors);
+    const size_t w_last = (size_t)items * n, w_tmp = (size_t)items * last * n;
+    u64 *ws = workspace(w_last + w_tmp);
+    rescale_core(in, nl, out, items, nl, d_c, ws, ws + w_last, 0, 0);
+}
+
+static bool ranges_overlap(const void *a, size_t a_bytes, const void *b, size_t b_bytes) {
+    const uintptr_t a_lo = (uintptr_t)a, b_lo = (uintptr_t)b;
+    return a_lo < b_lo + b_bytes && b_lo < a_lo + a_bytes;
+}
+
+// Rescale(prefix(in, nl_out + 1)): the rescale launches on the first nl_out + 1 limbs of ciphertexts nl_in limbs wide,
+// read where they are (a polynomial of the prefix is a polynomial of the input at stride nl_in)
+void Engine::compress(const u64 *in, u64 *out, uint32_t n_ct, uint32_t nl_in, uint32_t nl_out) {
+    need_device();
+    check_nl(nl_in);
+    if (nl_out < 1 || nl_out >= nl_in) throw std::invalid_argument("compress needs 1 <= nl_out < nl_in");
+    if (!n_ct) return;
+    const uint32_t n = ps_.n, nl = nl_out + 1, items = 2 * n_ct;
+    if (ranges_overlap(in, (size_t)items * nl_in * n * sizeof(u64), out, (size_t)items * nl_out * n * sizeof(u64)))
+        throw std::invalid_argument("compress cannot write over its input");
+    const u64 *d_c = rescale_consts(nl, nullptr);
+    const size_t w_last = (size_t)items * n, w_tmp = (size_t)items * nl_out * n;
+    u64 *ws = workspace(w_last + w_tmp);
+    rescale_core(in, nl_in, out, items, nl, d_c, ws, ws + w_last, 0, 0);
 }
 
 // ---- hybrid key switching -----------------------------------------------------------
@@ -1896,13 +1925,34 @@ void Engine::reencrypt_fanout(const u64 *ct, const u64 *evks, u64 *out, uint32_t
     need_device();
     check_nl(nl);
     if (!n_keys || !n_ct) return;
+    const size_t ct_bytes = (size_t)n_ct * 2 * nl * ps_.n * sizeof(u64);
+    if (ranges_overlap(ct, ct_bytes, out, n_keys * ct_bytes))
+        throw std::invalid_argument("fan-out re-encryption cannot write over its input");
+    fanout_core(ct, nl, evks, out, n_keys, n_ct, nl, false);
+}
+
+// out[k][b] = Rescale(ReEncrypt(prefix(ct[b], nl_out + 1), evks[k])): the fan-out at nl = nl_out + 1 limbs on the
+// aggregate's prefix, read in place, with the closing rescale of every (key, ciphertext, component) polynomial of a
+// group as one pass into the compact layout
+void Engine::reencrypt_fanout_compact(const u64 *ct, const u64 *evks, u64 *out, uint32_t n_keys, uint32_t n_ct, uint32_t nl_in,
+                                      uint32_t nl_out) {
+    need_device();
+    check_nl(nl_in);
+    if (nl_out < 1 || nl_out >= nl_in) throw std::invalid_argument("compact fan-out needs 1 <= nl_out < nl_in");
+    if (!n_keys || !n_ct) return;
+    const size_t poly_bytes = (size_t)n_ct * 2 * ps_.n * sizeof(u64);
+    if (ranges_overlap(ct, poly_bytes * nl_in, out, n_keys * poly_bytes * nl_out))
+        throw std::invalid_argument("fan-out re-encryption cannot write over its input");
+    fanout_core(ct, nl_in, evks, out, n_keys, n_ct, nl_out + 1, true);
+}
+
+void Engine::fanout_core(const u64 *ct, uint32_t in_limbs, const u64 *evks, u64 *out, uint32_t n_keys, uint32_t n_ct, uint32_t nl,
+                         bool compact) {
     const uint32_t n = ps_.n, K = ps_.K, ext = nl + K, nparts = ps_.num_parts(nl), D = ps_.D;
-    const size_t ct_words = (size_t)2 * nl * n, evk_words = (size_t)ps_.beta * 2 * D * n;
-    {
-        const uintptr_t c_lo = (uintptr_t)ct, c_hi = c_lo + (size_t)n_ct * ct_words * sizeof(u64);
-        const uintptr_t o_lo = (uintptr_t)out, o_hi = o_lo + (size_t)n_keys * n_ct * ct_words * sizeof(u64);
-        if (o_lo < c_hi && c_lo < o_hi) throw std::invalid_argument("fan-out re-encryption cannot write over its input");
-    }
+    // input ciphertexts are in_limbs wide (the kernels take the stride and the c0 / c1 pointers apart from nl); the
+    // key-switched ciphertexts have nl limbs, the outputs of the compact form nl - 1
+    const size_t ct_words = (size_t)2 * in_limbs * n, ks_words = (size_t)2 * nl * n, evk_words = (size_t)ps_.beta * 2 * D * n;
+    const size_t out_words = compact ? (size_t)2 * (nl - 1) * n : ks_words;
     const bool fused = fanout_fused(nl);
     unsigned long long fp_mask = 0, intq_mask = 0, p_mask = 0, all_mask = ext >= 64 ? ~0ull : ((1ull << ext) - 1);
     for (uint32_t i = 0; i < nl; ++i) (tabs_.h_fp_of[i] ? fp_mask : intq_mask) |= 1ull << i;
@@ -1911,12 +1961,14 @@ void Engine::reencrypt_fanout(const u64 *ct, const u64 *evks, u64 *out, uint32_t
     const size_t w_coef = (size_t)chunk * nl * n, w_dig = (size_t)chunk * nparts * ext * n;
     const size_t w_til = (size_t)group * chunk * 2 * ext * n, w_pc = (size_t)group * chunk * 2 * K * n;
     const size_t w_conv = (size_t)group * chunk * 2 * nl * n;
-    u64 *ws = workspace(w_coef + w_dig + w_til + w_pc + w_conv);
-    u64 *coef = ws, *dig = coef + w_coef, *til = dig + w_dig, *pc = til + w_til, *conv = pc + w_pc;
+    const size_t w_ks = compact ? (size_t)group * chunk * ks_words : 0;  // key-switched group ahead of its rescale
+    const u64 *d_c = compact ? rescale_consts(nl, nullptr) : nullptr;
+    u64 *ws = workspace(w_coef + w_dig + w_til + w_pc + w_conv + w_ks);
+    u64 *coef = ws, *dig = coef + w_coef, *til = dig + w_dig, *pc = til + w_til, *conv = pc + w_pc, *ks = conv + w_conv;
     const bool wide_rows = fast_row(tabs_.log_r2, 1u << tabs_.log_r1) == 9;
     for (uint32_t b0 = 0; b0 < n_ct; b0 += chunk) {
         const uint32_t cnt = std::min(chunk, n_ct - b0);
-        const u64 *ct0 = ct + (size_t)b0 * ct_words, *c1 = ct0 + (size_t)nl * n;
+        const u64 *ct0 = ct + (size_t)b0 * ct_words, *c1 = ct0 + (size_t)in_limbs * n;
         {   // the shared half; on the fused path the row passes are left to the fan-out kernels
             struct Reset {
                 bool &flag;
@@ -1928,18 +1980,27 @@ void Engine::reencrypt_fanout(const u64 *ct, const u64 *evks, u64 *out, uint32_t
         for (uint32_t k0 = 0; k0 < n_keys; k0 += group) {
             const uint32_t gk = std::min(group, n_keys - k0);
             const u64 *evk0 = evks + (size_t)k0 * evk_words;
-            u64 *out0 = out + ((size_t)k0 * n_ct + b0) * ct_words;
+            u64 *out0 = out + ((size_t)k0 * n_ct + b0) * out_words;
+            // compact: the group's key-switched ciphertexts go to ks [key][cnt][2][nl][N]
+            u64 *sw0 = compact ? ks : out0;
+            const size_t sw_gstride = compact ? (size_t)cnt * ks_words : (size_t)n_ct * ks_words;
             if (fused) {
                 FanArgs a{dig, c1, evk0, til, pc, ct_words, evk_words, nl, ext, D, ps_.alpha, cnt, gk, K, 0, 0};
                 if (wide_rows) launch_fan3_n<3>(a, tabs_, nparts, ps_.L, fp_mask, intq_mask, p_mask, stream_);
                 else launch_fan3_n<2>(a, tabs_, nparts, ps_.L, fp_mask, intq_mask, p_mask, stream_);
                 MK_HIP(hipGetLastError());
                 // polynomial p = (key * cnt + b) * 2 + comp: c0 of ciphertext b, output of key k0 + key
-                moddown_core(til, pc, conv, out0, (size_t)nl * n, ct0, ct_words, gk * 2 * cnt, nl, false, true, 2 * cnt,
-                             (size_t)n_ct * ct_words);
+                moddown_core(til, pc, conv, sw0, (size_t)nl * n, ct0, ct_words, gk * 2 * cnt, nl, false, true, 2 * cnt, sw_gstride);
             } else {
                 inner_product_all(c1, ct_words, evk0, dig, til, cnt, nl, all_mask);
-                moddown_core(til, pc, conv, out0, (size_t)nl * n, ct0, ct_words, 2 * cnt, nl, false, false);
+                moddown_core(til, pc, conv, sw0, (size_t)nl * n, ct0, ct_words, 2 * cnt, nl, false, false);
+            }
+            if (compact) {
+                // the closing rescale of all gk * 2 * cnt polynomials at once; til is free again and holds its scratch
+                // (ext words per polynomial against the 1 + (nl - 1) needed)
+                const uint32_t polys = gk * 2 * cnt;
+                rescale_core(ks, nl, out0, polys, nl, d_c, til, til + (size_t)polys * n, fused ? 2 * cnt : 0,
+                             (size_t)n_ct * out_words);
             }
         }
     }

@@ -120,6 +120,13 @@ public:
     // out[k][b] = ReEncrypt(ct[b], evks[k]): ModUp (and, on the fused path, the digits' row transforms) once per
     // ciphertext; ct [n_ct][2][nl][N] read-only, evks [n_keys][beta][2][D][N], out [n_keys][n_ct][2][nl][N]
     void reencrypt_fanout(const u64 *ct, const u64 *evks, u64 *out, uint32_t n_keys, uint32_t n_ct, uint32_t nl);
+    // compact forms for ciphertexts that will only be decrypted; both read the first nl_out + 1 limbs of in / ct
+    // u64[n_ct][2][nl_in][N] in place (a lower level of the same ciphertext) and write nl_out limbs:
+    //   compress:                 out[b]    = Rescale(prefix(in[b]))                       out [n_ct][2][nl_out][N]
+    //   reencrypt_fanout_compact: out[k][b] = Rescale(ReEncrypt(prefix(ct[b]), evks[k]))  out [n_keys][n_ct][2][nl_out][N]
+    void compress(const u64 *in, u64 *out, uint32_t n_ct, uint32_t nl_in, uint32_t nl_out);
+    void reencrypt_fanout_compact(const u64 *ct, const u64 *evks, u64 *out, uint32_t n_keys, uint32_t n_ct, uint32_t nl_in,
+                                  uint32_t nl_out);
     void modup(const u64 *c1, u64 *digits, uint32_t n, uint32_t nl);
     void moddown(const u64 *in, u64 *out, uint32_t n, uint32_t nl);
     // accumulate: out[b] += ReEncrypt(ct[b]) (coefficient-wise, mod q) -- the fold into a running aggregate
@@ -188,6 +195,16 @@ private:
     void inner_product_all(const u64 *c1, size_t ct_stride, const u64 *evk, const u64 *dig, u64 *til, uint32_t cnt,
                            uint32_t nl, unsigned long long mask);
     bool fanout_fused(uint32_t nl) const;
+    // fan-out over ciphertexts whose limbs are in_limbs * N words apart (their first nl are used); compact: the closing
+    // rescale to nl - 1 limbs follows the key switch of every group
+    void fanout_core(const u64 *ct, uint32_t in_limbs, const u64 *evks, u64 *out, uint32_t n_keys, uint32_t n_ct, uint32_t nl,
+                     bool compact);
+    const u64 *rescale_consts(uint32_t nl, const std::vector<u64> *factors);
+    // ModReduceInternalInPlace on `polys` polynomials of nl limbs, in_limbs * N words apart; out polynomial p (nl - 1
+    // limbs) at out + (p / group) * out_gstride + (p % group) * (nl - 1) * N (group 0: p * (nl - 1) * N).
+    // d_last [polys][N] and d_tmp [polys][nl - 1][N] are scratch
+    void rescale_core(const u64 *in, uint32_t in_limbs, u64 *out, uint32_t polys, uint32_t nl, const u64 *d_c, u64 *d_last,
+                      u64 *d_tmp, uint32_t group, size_t out_gstride);
     void moddown_convert(const u64 *til, u64 *pc, u64 *conv, uint32_t cnt, uint32_t nl, bool rows_done);
     int conv_src_mode(const DevConv &cv) const;
 

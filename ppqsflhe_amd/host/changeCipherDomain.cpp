@@ -3,15 +3,32 @@
 // The reference loops cc->ReEncrypt(ct, reKey) over mean / std_dev / values[] of every layer (:61-117); here all
 // ciphertexts of the file go to HBM once and are re-encrypted by ONE mkckks_reencrypt_batch call.  Seeded ciphertexts
 // (encryptModelWeights --seeded) are accepted per blob: c1 is rebuilt on the device; the output is full ciphertexts.
+//   changeCipherDomain <cc_path> <rekey_path|-> <input_encfile> <output_encfile> --limbs <k>
+// writes the output at k limbs for a receiver that will only decrypt it (the per-key counterpart of serverRound
+// --back-limbs): the first k + 1 limbs of every input ciphertext (which must be at noiseScaleDeg 2 with more than k limbs)
+// are re-encrypted and rescaled to k by mkckks_reencrypt_fanout_compact_batch; with "-" as the key there is no key switch
+// (mkckks_compress_batch).  Headroom rule for k: include/mkckks.h.
 #include "hostlib.hpp"
 using namespace mkh;
 
 int main(int argc, char *argv[]) {
-    if (argc != 5) {
-        std::cerr << "Usage: " << argv[0] << " <cc_path> <rekey_path> <input_encfile> <output_encfile>" << std::endl;
+    const bool compact = argc == 7 && std::string(argv[5]) == "--limbs";
+    if (argc != 5 && !compact) {
+        std::cerr << "Usage: " << argv[0] << " <cc_path> <rekey_path> <input_encfile> <output_encfile>\n       " << argv[0]
+                  << " <cc_path> <rekey_path|-> <input_encfile> <output_encfile> --limbs <k>" << std::endl;
         return 1;
     }
     const std::string cc_path = argv[1], rekey_path = argv[2], input_encfile = argv[3], output_encfile = argv[4];
+    uint32_t k_limbs = 0;
+    if (compact) {
+        const std::string v = argv[6];
+        if (v.empty() || v.size() > 6 || v.find_first_not_of("0123456789") != std::string::npos || std::atoi(v.c_str()) < 1) {
+            std::cerr << "[recrypt] ERROR: --limbs needs a limb count of at least 1" << std::endl;
+            return 1;
+        }
+        k_limbs = (uint32_t)std::atoi(v.c_str());
+    }
+    const bool keyed = !(compact && rekey_path == "-");
     CcFile cc;
     try {
         cc = read_cc(cc_path);
@@ -24,11 +41,11 @@ int main(int argc, char *argv[]) {
         std::cout << "[recrypt] CryptoContext loaded\n";
         const uint32_t N = s.N();
         std::vector<uint64_t> evk;
-        if (!load_eval_key(s, rekey_path, evk)) {
+        if (keyed && !load_eval_key(s, rekey_path, evk)) {
             std::cerr << "[recrypt] ERROR: Failed to load ReKey from " << rekey_path << std::endl;
             return 1;
         }
-        std::cout << "[recrypt] ReKey loaded\n";
+        if (keyed) std::cout << "[recrypt] ReKey loaded\n";
         Json inputJson;
         bool binary = false;  // the output keeps the input's envelope form
         try {
@@ -47,6 +64,14 @@ int main(int argc, char *argv[]) {
             const uint32_t nl = cts[0].nl;
             for (const Ciphertext &c : cts)
                 if (c.nl != nl) throw std::runtime_error("ciphertexts of one file must share a level");
+            if (compact)
+                for (const Ciphertext &c : cts)
+                    if (c.noise_deg != 2 || c.nl <= k_limbs) {
+                        std::cerr << "[recrypt] ERROR: --limbs " << k_limbs << " needs input at noiseScaleDeg 2 with more than "
+                                  << k_limbs << " limbs (it has noiseScaleDeg " << c.noise_deg << ", " << c.nl << " limbs)"
+                                  << std::endl;
+                        return 1;
+                    }
             const size_t words = (size_t)2 * nl * N;
             std::vector<uint64_t> flat(cts.size() * words, 0);
             SeedList seeds;
@@ -57,12 +82,33 @@ int main(int argc, char *argv[]) {
             }
             uint64_t *d_ct = s.to_device(flat.data(), flat.size());
             seeds.expand(s, d_ct, nl, 0, cts.size());
-            uint64_t *d_evk = s.to_device(evk.data(), evk.size());
-            Session::check(mkckks_reencrypt_batch(s.ctx(), d_ct, d_evk, d_ct, (uint32_t)cts.size(), nl));
-            s.to_host(flat.data(), d_ct, flat.size());
+            size_t owords = words;
+            if (!compact) {
+                uint64_t *d_evk = s.to_device(evk.data(), evk.size());
+                Session::check(mkckks_reencrypt_batch(s.ctx(), d_ct, d_evk, d_ct, (uint32_t)cts.size(), nl));
+                s.to_host(flat.data(), d_ct, flat.size());
+            } else {
+                owords = (size_t)2 * k_limbs * N;
+                uint64_t *d_out = s.alloc<uint64_t>(cts.size() * owords);
+                if (keyed) {
+                    uint64_t *d_evk = s.to_device(evk.data(), evk.size());
+                    Session::check(mkckks_reencrypt_fanout_compact_batch(s.ctx(), d_ct, d_evk, d_out, 1, (uint32_t)cts.size(), nl,
+                                                                         k_limbs));
+                } else {
+                    Session::check(mkckks_compress_batch(s.ctx(), d_ct, d_out, (uint32_t)cts.size(), nl, k_limbs));
+                }
+                flat.resize(cts.size() * owords);
+                s.to_host(flat.data(), d_out, flat.size());
+            }
             for (size_t i = 0; i < cts.size(); ++i) {
-                cts[i].data.assign(flat.begin() + i * words, flat.begin() + (i + 1) * words);
+                cts[i].data.assign(flat.begin() + i * owords, flat.begin() + (i + 1) * owords);
                 cts[i].seeded = false;
+                if (compact) {  // header of Rescale(prefix(., k + 1))
+                    cts[i].level += nl - k_limbs;
+                    cts[i].scale = cts[i].scale / (double)s.moduli()[k_limbs];
+                    cts[i].nl = k_limbs;
+                    cts[i].noise_deg = 1;
+                }
                 Json &lay = outputJson["weights_summary"].a[refs[i].layer];
                 std::string b64 = encode_ct(cts[i], N);
                 if (refs[i].field == 0) lay["mean"] = std::move(b64);

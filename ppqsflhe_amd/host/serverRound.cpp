@@ -15,6 +15,12 @@
 // s_changeCipherDomain_c2_c1, server_fns.sh:76-80: changeCipherDomain <cc> <rekey_back_c> <aggfile> <out_c>) -- the
 // aggregate stays in HBM, ONE mkckks_reencrypt_fanout_batch over all back keys (which stay resident by file name under
 // --rounds); each file equals changeCipherDomain run on <output_aggfile>.  MKCKKS_BACK_LOOP=1: one call per key.
+// --back-limbs <k> (after the --back list): every back file is written at k limbs instead of the aggregate's -- what goes
+// back is only ever decrypted, so it needs modulus for scale * |value| + noise and no more (include/mkckks.h, headroom
+// rule; k is the deployment's choice).  One mkckks_reencrypt_fanout_compact_batch per key group: the aggregate's first
+// k + 1 limbs are key-switched and rescaled to k.  With it a back key of "-" names a client that already is in the target
+// domain: its file is mkckks_compress_batch of the aggregate.  Each file equals changeCipherDomain ... --limbs <k> run on
+// <output_aggfile>; the aggregate file itself is never compacted.
 // Binary (MKWS) envelopes take the I/O pipeline of iopipe.hpp: files are indexed, not loaded; reader threads fill pinned
 // slots, uploads run beside the reads, residues are range-checked on the device, results are written by pwrite() from
 // pinned slots.  MKCKKS_SYNC_IO=1 forces the synchronous path (every ciphertext through read_envelope / decode_ct /
@@ -35,9 +41,23 @@ using namespace mkh;
 struct RoundArgs {
     std::string output_file;
     std::vector<std::string> rekey_paths, enc_paths, back_keys, back_outs;
+    bool compact = false;     // --back-limbs given
+    uint32_t back_limbs = 0;  // its value
 };
 // tokens: <output_aggfile> <rekey_1|-> <encfile_1> ... [--back <rekey_back_1> <output_encfile_1> ...]
-static bool parse_round(const std::vector<std::string> &t, RoundArgs &a) {
+static bool parse_round(std::vector<std::string> t, RoundArgs &a) {
+    bool compact = false;
+    uint32_t back_limbs = 0;
+    for (size_t i = 1; i < t.size(); ++i)
+        if (t[i] == "--back-limbs") {  // one value; taken out before the positional lists are read
+            if (i + 1 >= t.size() || t[i + 1].empty() || t[i + 1].size() > 6 ||
+                t[i + 1].find_first_not_of("0123456789") != std::string::npos)
+                return false;
+            compact = true;
+            back_limbs = (uint32_t)std::atoi(t[i + 1].c_str());
+            t.erase(t.begin() + i, t.begin() + i + 2);
+            break;
+        }
     size_t n_args = t.size();
     for (size_t i = 1; i < t.size(); ++i)
         if (t[i] == "--back") {
@@ -46,7 +66,10 @@ static bool parse_round(const std::vector<std::string> &t, RoundArgs &a) {
         }
     const size_t n_back = t.size() - n_args - (n_args < t.size() ? 1 : 0);
     if (n_args < 3 || (n_args - 1) % 2 != 0 || n_back % 2 != 0 || (n_args < t.size() && n_back == 0)) return false;
+    if (compact && n_back == 0) return false;
     a = RoundArgs{};
+    a.compact = compact;
+    a.back_limbs = back_limbs;
     a.output_file = t[0];
     for (size_t i = 1; i + 1 < n_args; i += 2) {
         a.rekey_paths.push_back(t[i]);
@@ -141,6 +164,44 @@ static int run_round(Session &s, ServerState &st, const RoundArgs &a) {
     AggResult agg;
     const unsigned threads = io_threads();
     bool pinned_out = false;
+    // the back leg's arguments are judged before any file is written: the aggregate's shape follows from the first
+    // container's header (scale_aggregate's rules)
+    for (const std::string &k : a.back_keys)
+        if (k == "-" && !a.compact) {
+            std::cerr << "[round] ERROR: a back key of - needs --back-limbs" << std::endl;
+            return 1;
+        }
+    if (a.compact) {
+        if (a.back_limbs < 1) {
+            std::cerr << "[round] ERROR: --back-limbs must be at least 1" << std::endl;
+            return 1;
+        }
+        if (!items.empty()) {
+            BlobHeader h0{};
+            if (piped) {
+                const BlobRef &blob0 = idx[0].blobs.at(blob_index(*items[0].blobs[0]));
+                if (blob0.size < sizeof(BlobHeader)) throw std::runtime_error("ciphertext blob too short");
+                pread_all(idx[0].fd, &h0, sizeof h0, blob0.offset);
+            } else {
+                const std::string &b = *items[0].blobs[0];
+                const bool raw = b.size() >= 4 && !std::memcmp(b.data(), "MKCK", 4);
+                const std::string head = raw ? b.substr(0, sizeof h0) : Base64Decode(b.substr(0, sizeof h0 / 3 * 4));
+                if (head.size() < sizeof h0) throw std::runtime_error("ciphertext blob too short");
+                std::memcpy(&h0, head.data(), sizeof h0);
+            }
+            const bool rescale = h0.noise_deg == 2;
+            const uint32_t agg_nl = rescale ? h0.limbs - 1 : h0.limbs, agg_deg = rescale ? 2 : h0.noise_deg + 1;
+            if (agg_deg != 2) {
+                std::cerr << "[round] ERROR: --back-limbs needs the aggregate at noiseScaleDeg 2 (it is at " << agg_deg << ")" << std::endl;
+                return 1;
+            }
+            if (a.back_limbs >= agg_nl) {
+                std::cerr << "[round] ERROR: --back-limbs " << a.back_limbs << " is not below the aggregate's " << agg_nl << " limbs"
+                          << std::endl;
+                return 1;
+            }
+        }
+    }
     if (!items.empty() && piped) {
         RoundPlan plan;
         plan.n_clients = n_clients;
@@ -213,31 +274,50 @@ static int run_back_leg(Session &s, ServerState &st, const RoundArgs &a, const s
     const uint32_t N = s.N();
     const size_t evk_words = (size_t)s.beta() * 2 * s.D() * N, B = items.size();
     const bool loop = std::getenv("MKCKKS_BACK_LOOP") && std::atoi(std::getenv("MKCKKS_BACK_LOOP")) != 0;
-    // keys in order up to the first one that does not load: the files before it are written, then the error (as the loop did)
-    std::vector<const std::vector<uint64_t> *> keys;
+    // --back-limbs k: every file carries k limbs at noiseScaleDeg 1 (the header of Rescale(prefix(., k + 1)))
+    const uint32_t k_limbs = a.compact ? a.back_limbs : 0, out_nl = k_limbs ? k_limbs : agg.meta.nl;
+    Ciphertext meta = agg.meta;
+    if (k_limbs && B) {
+        if (agg.meta.noise_deg != 2 || k_limbs >= agg.meta.nl) throw std::runtime_error("--back-limbs does not fit the aggregate");
+        meta.level = agg.meta.level + (agg.meta.nl - k_limbs);
+        meta.nl = k_limbs;
+        meta.noise_deg = 1;
+        meta.scale = agg.meta.scale / (double)s.moduli()[k_limbs];
+    }
+    // entries in order up to the first key that does not load: the files before it are written, then the error (as the
+    // loop did); "-" (compact form only) is the client that needs no key switch
+    std::vector<const std::vector<uint64_t> *> keys;  // per entry; null for "-"
     for (size_t k = 0; k < a.back_keys.size(); ++k) {
+        if (a.back_keys[k] == "-") {
+            keys.push_back(nullptr);
+            continue;
+        }
         const std::vector<uint64_t> *evk = cached_key(s, st, a.back_keys[k]);
         if (!evk) break;
         keys.push_back(evk);
     }
-    const size_t n_keys = keys.size();
+    const size_t n_entries = keys.size();
+    std::vector<size_t> real, plain;  // entries with a key / without
+    for (size_t k = 0; k < n_entries; ++k) (keys[k] ? real : plain).push_back(k);
+    const size_t n_keys = real.size();
     size_t uploaded = 0;
     auto write_one = [&](size_t k, uint64_t *d_back) {
         Json backJson = outputJson;  // layer / shape carried over; blobs replaced below
         if (B) {
             if (pinned_out) {
-                write_envelope_from_device(s, *st.cache.ring, items, d_back, agg.meta, backJson, a.back_outs[k], threads);
+                write_envelope_from_device(s, *st.cache.ring, items, d_back, meta, backJson, a.back_outs[k], threads);
             } else {
-                store_agg_items(s, items, d_back, agg.meta, backJson);
+                store_agg_items(s, items, d_back, meta, backJson);
                 write_envelope(backJson, a.back_outs[k], binary);
             }
         } else {
             write_envelope(backJson, a.back_outs[k], binary);
         }
-        std::cout << "[round] aggregate re-encrypted with " << a.back_keys[k] << " -> " << a.back_outs[k] << "\n";
+        if (keys[k]) std::cout << "[round] aggregate re-encrypted with " << a.back_keys[k] << " -> " << a.back_outs[k] << "\n";
+        else std::cout << "[round] aggregate compressed for its own domain -> " << a.back_outs[k] << "\n";
     };
+    const size_t words = B * (size_t)2 * out_nl * N;  // one key's output
     if (!loop && B && n_keys) {
-        const size_t words = B * (size_t)2 * agg.meta.nl * N;
         // keys per call: the outputs of one call are bounded (MKCKKS_BACK_MAX_MIB, default 16 GiB) beside the round's buffers
         size_t max_mib = 16384;
         if (const char *e = std::getenv("MKCKKS_BACK_MAX_MIB")) max_mib = (size_t)std::max(1, std::atoi(e));
@@ -247,47 +327,64 @@ static int run_back_leg(Session &s, ServerState &st, const RoundArgs &a, const s
         uint64_t *d_back = st.cache.grow(st.cache.back, per_call * words);
         st.back_names.resize(std::max(st.back_names.size(), n_keys));
         for (size_t k = 0; k < n_keys; ++k) {
-            if (st.back_names[k] == a.back_keys[k]) continue;  // resident in its slot
+            if (st.back_names[k] == a.back_keys[real[k]]) continue;  // resident in its slot
             st.back_names[k].clear();
-            Session::check(mkckks_upload(s.ctx(), d_evks + k * evk_words, keys[k]->data(), evk_words * 8));
-            st.back_names[k] = a.back_keys[k];
+            Session::check(mkckks_upload(s.ctx(), d_evks + k * evk_words, keys[real[k]]->data(), evk_words * 8));
+            st.back_names[k] = a.back_keys[real[k]];
             ++uploaded;
         }
         for (size_t k0 = 0; k0 < n_keys; k0 += per_call) {
             const size_t gk = std::min(per_call, n_keys - k0);
-            Session::check(mkckks_reencrypt_fanout_batch(s.ctx(), agg.d_out, d_evks + k0 * evk_words, d_back, (uint32_t)gk,
-                                                         (uint32_t)B, agg.meta.nl));
-            for (size_t k = 0; k < gk; ++k) write_one(k0 + k, d_back + k * words);
+            if (k_limbs)
+                Session::check(mkckks_reencrypt_fanout_compact_batch(s.ctx(), agg.d_out, d_evks + k0 * evk_words, d_back,
+                                                                     (uint32_t)gk, (uint32_t)B, agg.meta.nl, k_limbs));
+            else
+                Session::check(mkckks_reencrypt_fanout_batch(s.ctx(), agg.d_out, d_evks + k0 * evk_words, d_back, (uint32_t)gk,
+                                                             (uint32_t)B, agg.meta.nl));
+            for (size_t k = 0; k < gk; ++k) write_one(real[k0 + k], d_back + k * words);
         }
     } else {
         for (size_t k = 0; k < n_keys; ++k) {  // one key at a time through slot 0 of the key array
             uint64_t *d_back = nullptr;
             if (B) {
-                const size_t words = B * (size_t)2 * agg.meta.nl * N;
                 st.back_names.clear();
                 d_back = st.cache.grow(st.cache.back, words);
                 uint64_t *d_back_evk = st.cache.grow(st.cache.back_evk, evk_words);
-                Session::check(mkckks_upload(s.ctx(), d_back_evk, keys[k]->data(), evk_words * 8));
+                Session::check(mkckks_upload(s.ctx(), d_back_evk, keys[real[k]]->data(), evk_words * 8));
                 ++uploaded;
-                Session::check(mkckks_reencrypt_batch(s.ctx(), agg.d_out, d_back_evk, d_back, (uint32_t)B, agg.meta.nl));
+                if (k_limbs)
+                    Session::check(mkckks_reencrypt_fanout_compact_batch(s.ctx(), agg.d_out, d_back_evk, d_back, 1, (uint32_t)B,
+                                                                         agg.meta.nl, k_limbs));
+                else
+                    Session::check(mkckks_reencrypt_batch(s.ctx(), agg.d_out, d_back_evk, d_back, (uint32_t)B, agg.meta.nl));
             }
-            write_one(k, d_back);
+            write_one(real[k], d_back);
         }
     }
-    if (n_keys < a.back_keys.size()) {
-        std::cerr << "[round] ERROR: Failed to load ReKey from " << a.back_keys[n_keys] << std::endl;
+    for (size_t k : plain) {  // the client that already is in the target domain: no key switch, the rescale alone
+        uint64_t *d_back = nullptr;
+        if (B) {
+            d_back = st.cache.grow(st.cache.back, words);
+            Session::check(mkckks_compress_batch(s.ctx(), agg.d_out, d_back, (uint32_t)B, agg.meta.nl, k_limbs));
+        }
+        write_one(k, d_back);
+    }
+    if (n_entries < a.back_keys.size()) {
+        std::cerr << "[round] ERROR: Failed to load ReKey from " << a.back_keys[n_entries] << std::endl;
         return 1;
     }
     const double ms = now_ms() - t_leg;
-    std::cout << "[round] back leg: " << n_keys << " keys x " << B << " ciphertexts in " << ms << " ms -> "
-              << (double)(n_keys * B) / ms * 1e3 << " ciphertexts/s, " << uploaded << " key(s) uploaded\n";
+    std::cout << "[round] back leg: " << n_entries << " keys x " << B << " ciphertexts in " << ms << " ms -> "
+              << (double)(n_entries * B) / ms * 1e3 << " ciphertexts/s, " << uploaded << " key(s) uploaded";
+    if (k_limbs) std::cout << ", " << k_limbs << " limbs";
+    std::cout << "\n";
     return 0;
 }
 
 int main(int argc, char *argv[]) {
     auto usage = [&] {
         std::cerr << "Usage: " << argv[0] << " <cc_path> <output_aggfile> <rekey_1|-> <encfile_1> [<rekey_2|-> <encfile_2> ...]"
-                  << " [--back <rekey_back_1> <output_encfile_1> ...]\n       " << argv[0]
+                  << " [--back <rekey_back_1|-> <output_encfile_1> ... [--back-limbs <k>]]\n       " << argv[0]
                   << " <cc_path> --rounds <file with one such argument list (after <cc_path>) per line>" << std::endl;
         return 1;
     };
