@@ -143,7 +143,8 @@ int mkckks_rescale_batch(mkckks_ctx *c, const uint64_t *d_in, uint64_t *d_out, u
 int mkckks_mult_const_batch(mkckks_ctx *c, uint64_t *d_ct, uint32_t n_ct, uint32_t nl, double operand);
 
 /* ---- cc->ReEncrypt(ct, reKey)  (changeCipherDomain.cpp:74,89,105) --------
- * INDCPA proxy re-encryption = hybrid key switch of c1 with the eval key:
+ * INDCPA proxy re-encryption (the HRA-secure form: mkckks_rerandomize_batch first) = hybrid key switch of c1 with the
+ * eval key:
  * out = (c0 + <d,b>/P, <d,a>/P).  d_evk is u64[beta][2][D][N] (full level);
  * ciphertexts have nl <= L limbs; in/out may alias. */
 int mkckks_reencrypt_batch(mkckks_ctx *c, const uint64_t *d_ct, const uint64_t *d_evk, uint64_t *d_out,
@@ -221,6 +222,14 @@ int mkckks_sample_gauss(mkckks_ctx *c, int32_t *d_out, size_t count, double sigm
                         uint32_t stream_id);
 int mkckks_sample_uniform(mkckks_ctx *c, uint64_t *d_out, uint32_t n_polys, uint32_t nl, int with_p,
                           const uint8_t *h_key32, uint32_t stream_id);
+/* wide ("flooding") Gaussian errors for mkckks_rerandomize_batch: d_out int64[count], element i =
+ * (int64_t)rint(sigma * z) with z = component i % 2 of the Box-Muller pair i / 2 of stream `stream_id` (the mapping
+ * csrc/sampler_kernels.hpp documents for decode flooding: chacha_normal_pair) -- a pure function of (key, stream_id, i),
+ * independent of launch geometry and of `count`.  2^6 <= sigma <= 2^56, else MKCKKS_E_INVALID: below 2^6 a rounded
+ * normal is no stand-in for a discrete Gaussian; |z| < 8.6, so up to 2^56 every |e| stays below the 2^62 of
+ * mkckks_rerandomize_batch.  count == 0 is a no-op. */
+int mkckks_sample_gauss_wide(mkckks_ctx *c, int64_t *d_out, size_t count, double sigma, const uint8_t *h_key32,
+                             uint32_t stream_id);
 /* known-answer hook: the 16 output words of one ChaCha20 block (RFC 8439 2.3.2) -> d_out16 (device) */
 int mkckks_chacha20_block(mkckks_ctx *c, uint32_t *d_out16, const uint8_t *h_key32, uint32_t counter,
                           const uint32_t *h_nonce3);
@@ -242,6 +251,29 @@ int mkckks_rekeygen(mkckks_ctx *c, const int8_t *d_s_old, const uint64_t *d_pk_n
  * e0,e1 int32[n_ct][N]; out u64[n_ct][2][nl][N]. */
 int mkckks_encrypt_batch(mkckks_ctx *c, const uint64_t *d_pk, const uint64_t *d_pt, const int8_t *d_v,
                          const int32_t *d_e0, const int32_t *d_e1, uint64_t *d_ct, uint32_t n_ct, uint32_t nl);
+
+/* ---- cc->ReEncrypt(ct, reKey, publicKey), first half  (changeCipherDomain.cpp:74 with the third argument) ------
+ * HRA-secure proxy re-encryption (Cohen 2019): upstream's PREBase::ReEncrypt(ct, evalKey, publicKey) re-randomises
+ * the ciphertext with an encryption of zero under the SOURCE domain's public key (EncryptZeroCore, errors from a wide
+ * "flooding" Gaussian) before the key switch.  This is that re-randomisation; for t < n_ct, i < nl:
+ *     out[t][0][i] = ct[t][0][i] + pk[0][i] * NTT_i(v_t) + NTT_i(e0_t)   mod q_i
+ *     out[t][1][i] = ct[t][1][i] + pk[1][i] * NTT_i(v_t) + NTT_i(e1_t)   mod q_i
+ * d_ct u64[n_ct][2][nl_in][N], read at its first nl limbs (a lower level is a prefix, as in mkckks_compress_batch);
+ * d_pk u64[2][D][N] addressed by limb id; d_v int8[n_ct][N] ternary; d_e0 / d_e1 int64[n_ct][N] with |e| < 2^62 (the
+ * caller's contract; mkckks_sample_gauss_wide keeps it); d_out u64[n_ct][2][nl][N].  d_out == d_ct is allowed exactly
+ * when nl_in == nl (in place); any other overlap is MKCKKS_E_INVALID.  1 <= nl <= nl_in <= L; n_ct == 0 is a no-op.
+ * The randomness is the caller's, as in mkckks_encrypt_batch: hosts draw it with mkckks_sample_ternary /
+ * mkckks_sample_gauss_wide under an OS-drawn key of their own.  Outputs are canonical residues: the result equals
+ * exact integer arithmetic word for word.
+ * Consequence: ReEncrypt(ct, evk, pk) = mkckks_rerandomize_batch followed by any of the re-encryption entry points
+ * (mkckks_reencrypt_batch, _sum_batch, _fanout_batch, _fanout_compact_batch).
+ * Noise rule: under the key of pk the mask decrypts to e0 + e1 * s (+ the key's own e * v, below 0.3 % at sigma >= 2^6):
+ * standard deviation sigma * sqrt(1 + h) per coefficient, h the number of non-zero coefficients of the ternary secret,
+ * ~ sigma * sqrt(2N/3).  Keep it well below the ciphertext's own noise at its scale (at noiseScaleDeg 2, scale ~ 2^(2p),
+ * sigma up to 2^28 costs no measurable precision at p = 40 and 50). */
+int mkckks_rerandomize_batch(mkckks_ctx *c, const uint64_t *d_ct, const uint64_t *d_pk, const int8_t *d_v,
+                             const int64_t *d_e0, const int64_t *d_e1, uint64_t *d_out, uint32_t n_ct, uint32_t nl_in,
+                             uint32_t nl);
 
 /* ---- seeded secret-key ciphertexts (new: half the bytes of a client ciphertext) ---------------------------------
  * A seeded ciphertext is (c0, seed): c1 = a is not sent but regenerated from a 32-byte ChaCha20 key K and a u32

@@ -85,6 +85,8 @@ SYMBOLS = {
     "mkckks_decrypt_batch": (_int, [_vp, _vp, _vp, _vp, _u32, _u32]),
     "mkckks_sample_ternary": (_int, [_vp, _vp, _sz, C.c_char_p, _u32]),
     "mkckks_sample_gauss": (_int, [_vp, _vp, _sz, _dbl, C.c_char_p, _u32]),
+    "mkckks_sample_gauss_wide": (_int, [_vp, _vp, _sz, _dbl, C.c_char_p, _u32]),
+    "mkckks_rerandomize_batch": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32]),
     "mkckks_sample_uniform": (_int, [_vp, _vp, _u32, _u32, _int, C.c_char_p, _u32]),
     "mkckks_chacha20_block": (_int, [_vp, _vp, C.c_char_p, _u32, C.POINTER(_u32)]),
     "mkckks_encrypt_seeded_batch": (_int, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, C.c_char_p, _u32]),
@@ -405,6 +407,12 @@ class Context:
         """out[k][b] = ReEncrypt(ct[b], evks[k]): one ciphertext batch into n_keys key domains (ModUp shared)."""
         self._check(self._L.mkckks_reencrypt_fanout_batch(self._h, _ptr(ct), _ptr(evks), _ptr(out), n_keys, n_ct, nl))
 
+    def rerandomize(self, ct, pk, v, e0, e1, out, n_ct, nl_in, nl):
+        """out[t] = first nl limbs of ct[t] + Enc_pk(0; v[t], e0[t], e1[t]): the re-randomisation of the HRA-secure
+        ReEncrypt(ct, evk, pk); follow with any reencrypt* call.  v int8, e0 / e1 int64 (sample_gauss_wide)."""
+        self._check(self._L.mkckks_rerandomize_batch(self._h, _ptr(ct), _ptr(pk), _ptr(v), _ptr(e0), _ptr(e1), _ptr(out),
+                                                     n_ct, nl_in, nl))
+
     def compress(self, inp, out, n_ct, nl_in, nl_out):
         """out[b] = Rescale(first nl_out + 1 limbs of inp[b]): a ciphertext that will only be decrypted, at nl_out limbs."""
         self._check(self._L.mkckks_compress_batch(self._h, _ptr(inp), _ptr(out), n_ct, nl_in, nl_out))
@@ -457,6 +465,10 @@ class Context:
 
     def sample_gauss(self, out, count, sigma, key, stream_id=0):
         self._check(self._L.mkckks_sample_gauss(self._h, _ptr(out), count, float(sigma), sampler_key(key), stream_id))
+
+    def sample_gauss_wide(self, out, count, sigma, key, stream_id=0):
+        """int64 rint(sigma * z), z standard normal (mkckks_sample_gauss_wide): the errors of `rerandomize`."""
+        self._check(self._L.mkckks_sample_gauss_wide(self._h, _ptr(out), count, float(sigma), sampler_key(key), stream_id))
 
     def sample_uniform(self, out, n_polys, nl, with_p, key, stream_id=0):
         self._check(self._L.mkckks_sample_uniform(self._h, _ptr(out), n_polys, nl, int(with_p), sampler_key(key), stream_id))

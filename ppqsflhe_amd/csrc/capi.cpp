@@ -370,6 +370,22 @@ int mkckks_encrypt_batch(mkckks_ctx *c, const uint64_t *pk, const uint64_t *pt, 
         c->eng->encrypt(pk, pt, v, e0, e1, ct, n_ct, nl);
     });
 }
+int mkckks_rerandomize_batch(mkckks_ctx *c, const uint64_t *ct, const uint64_t *pk, const int8_t *v, const int64_t *e0,
+                             const int64_t *e1, uint64_t *out, uint32_t n_ct, uint32_t nl_in, uint32_t nl) {
+    return guarded([&] {
+        need(c && ct && pk && v && e0 && e1 && out, "null argument");
+        const mk::ParamSet &ps = c->eng->params();
+        need(nl >= 1 && nl <= nl_in && nl_in <= ps.L, "need 1 <= nl <= nl_in <= L");
+        if (!(out == ct && nl_in == nl)) {  // in place is the one allowed overlap; addresses only
+            const size_t poly_bytes = (size_t)n_ct * 2 * ps.n * sizeof(uint64_t);
+            const uintptr_t i_lo = (uintptr_t)ct, i_hi = i_lo + poly_bytes * nl_in;
+            const uintptr_t o_lo = (uintptr_t)out, o_hi = o_lo + poly_bytes * nl;
+            need(!(o_lo < i_hi && i_lo < o_hi), "output overlaps input");
+        }
+        if (!n_ct) return;
+        c->eng->rerandomize(ct, pk, v, e0, e1, out, n_ct, nl_in, nl);
+    });
+}
 int mkckks_encrypt_seeded_batch(mkckks_ctx *c, const uint64_t *sk, const uint64_t *pt, const int32_t *e, uint64_t *c0,
                                 uint32_t n_ct, uint32_t nl, const uint8_t *h_seed32, uint32_t stream_base) {
     return guarded([&] {
@@ -401,6 +417,15 @@ int mkckks_sample_gauss(mkckks_ctx *c, int32_t *out, size_t count, double sigma,
     return guarded([&] {
         need(c && out && h_key32, "null argument");
         c->eng->sample_gauss(out, count, sigma, h_key32, stream_id);
+    });
+}
+int mkckks_sample_gauss_wide(mkckks_ctx *c, int64_t *out, size_t count, double sigma, const uint8_t *h_key32,
+                             uint32_t stream_id) {
+    return guarded([&] {
+        need(c && out && h_key32, "null argument");
+        need(sigma >= 0x1p6 && sigma <= 0x1p56, "sigma outside [2^6, 2^56]");
+        if (!count) return;
+        c->eng->sample_gauss_wide(out, count, sigma, h_key32, stream_id);
     });
 }
 int mkckks_sample_uniform(mkckks_ctx *c, uint64_t *out, uint32_t n_polys, uint32_t nl, int with_p, const uint8_t *h_key32,

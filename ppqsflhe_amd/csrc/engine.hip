@@ -342,6 +342,7 @@ __device__ __forceinline__ u64 lift_value(int32_t v, const LimbConst &lc) {
     const u64 m = reduce_word((u64)(v < 0 ? -(int64_t)v : (int64_t)v), lc);
     return (v < 0 && m != 0) ? lc.q - m : m;
 }
+__device__ __forceinline__ u64 lift_value(int64_t v, const LimbConst &lc) { return lift_signed(v, lc); }  // |v| < 2^63
 // exact residue of round(x) for a double x (|x| < 2^120): mantissa * 2^e reduced in 128 bits
 __device__ __forceinline__ u64 lift_value(double x, const LimbConst &lc) {
     const double r = round(x);
@@ -2106,6 +2107,88 @@ void Engine::decrypt(const u64 *ct, const u64 *sk, u64 *m, uint32_t n_ct, uint32
     ntt_launch(m, n_ct, nl, nl, true, nullptr, nullptr);
 }
 
+// ---- re-randomisation before a key switch (PREBase::ReEncrypt(ct, evalKey, publicKey) -> EncryptZeroCore) ----------
+
+template <int COL_H, int ROW_H>
+static void launch_rerand(LiftIo li, RerandArgs ra, const NttTables &T, uint32_t cnt, hipStream_t s) {
+    const uint32_t r1 = 1u << T.log_r1, r2 = 1u << T.log_r2;
+    NttIo sel{};
+    sel.nslots = sel.nl = ra.nl;
+    for (int fp = 0; fp < 2; ++fp) {
+        const unsigned long long mask = class_mask(sel, T.h_fp_of, T.L, fp != 0);
+        const uint32_t nsel = (uint32_t)__builtin_popcountll(mask);
+        if (!nsel) continue;
+        li.slot_mask = ra.slot_mask = mask;
+        li.nsel = ra.nsel = nsel;
+        const dim3 cgrid(r2 / (256u >> COL_H), 3 * nsel, cnt), rgrid((r1 / (256u >> ROW_H)) * nsel * cnt);
+        if (fp) {
+            k_lift_col<COL_H, AR_FP><<<cgrid, NTT_THREADS, 0, s>>>(li, T);
+            k_rerand_row<ROW_H, AR_FP><<<rgrid, NTT_THREADS, 0, s>>>(ra, T);
+        } else {
+            with_int_arith(T, [&](auto ar) {
+                k_lift_col<COL_H, decltype(ar)::value><<<cgrid, NTT_THREADS, 0, s>>>(li, T);
+                k_rerand_row<ROW_H, decltype(ar)::value><<<rgrid, NTT_THREADS, 0, s>>>(ra, T);
+            });
+        }
+    }
+}
+template <int COL_H>
+static void launch_rerand_c(const LiftIo &li, const RerandArgs &ra, const NttTables &T, uint32_t cnt, int row_h, hipStream_t s) {
+    switch (row_h) {
+        case 4: launch_rerand<COL_H, 4>(li, ra, T, cnt, s); break;
+        case 3: launch_rerand<COL_H, 3>(li, ra, T, cnt, s); break;
+        default: launch_rerand<COL_H, 2>(li, ra, T, cnt, s);
+    }
+}
+
+void Engine::rerandomize(const u64 *ct, const u64 *pk, const int8_t *v, const int64_t *e0, const int64_t *e1, u64 *out,
+                         uint32_t n_ct, uint32_t nl_in, uint32_t nl) {
+    need_device();
+    check_nl(nl);
+    check_nl(nl_in);
+    if (nl > nl_in) throw std::invalid_argument("need nl <= nl_in");
+    if (!n_ct) return;
+    const uint32_t n = ps_.n, D = ps_.D;
+    const size_t poly = (size_t)nl * n;
+    // fused: lift inside the column pass, the products and sums inside the row pass's copy-out (two-round rows only)
+    const int col_h = fast_log_h(tabs_.log_r1, 1u << tabs_.log_r2), row_h = fast_row(tabs_.log_r2, 1u << tabs_.log_r1);
+    const bool fused = col_h != 0 && row_h >= 2 && row_h <= 4;
+    const uint32_t chunk = knobs_.chunk;
+    u64 *ws = workspace(3 * poly * (n_ct < chunk ? n_ct : chunk));
+    for (uint32_t b0 = 0; b0 < n_ct; b0 += chunk) {
+        const uint32_t cnt = n_ct - b0 < chunk ? n_ct - b0 : chunk;
+        const u64 *cin = ct + (size_t)b0 * 2 * nl_in * n;
+        u64 *cout = out + (size_t)b0 * 2 * poly;
+        const int8_t *vb = v + (size_t)b0 * n;
+        const int64_t *e0b = e0 + (size_t)b0 * n, *e1b = e1 + (size_t)b0 * n;
+        if (fused) {
+            const LiftIo li{vb, e0b, e1b, ws, nl, 0, 0};
+            const RerandArgs ra{ws, cin, pk, cout, nl_in, nl, D, 0, 0};
+            switch (col_h) {
+                case 4: launch_rerand_c<4>(li, ra, tabs_, cnt, row_h, stream_); break;
+                case 3: launch_rerand_c<3>(li, ra, tabs_, cnt, row_h, stream_); break;
+                default: launch_rerand_c<2>(li, ra, tabs_, cnt, row_h, stream_);
+            }
+            MK_HIP(hipGetLastError());
+        } else {  // the composition of Engine::encrypt with the ciphertext's components in the plaintext's place
+            u64 *ve = ws, *e0e = ve + poly * cnt, *e1e = e0e + poly * cnt;
+            EwGeom g{n, nl, ps_.L};
+            k_lift<int8_t><<<ew_grid(n, nl, cnt), EW_THREADS, 0, stream_>>>(vb, ve, g, d_limb_, nl);
+            k_lift<int64_t><<<ew_grid(n, nl, cnt), EW_THREADS, 0, stream_>>>(e0b, e0e, g, d_limb_, nl);
+            k_lift<int64_t><<<ew_grid(n, nl, cnt), EW_THREADS, 0, stream_>>>(e1b, e1e, g, d_limb_, nl);
+            MK_HIP(hipGetLastError());
+            ntt_launch(ve, 3 * cnt, nl, nl, false, nullptr, nullptr);
+            const size_t cstride = (size_t)2 * nl_in * n;
+            Opnd p0{pk, 0, 1}, p1{pk + (size_t)D * n, 0, 1}, vv{ve, poly, 0}, z0{e0e, poly, 0}, z1{e1e, poly, 0};
+            Opnd c0{cin, cstride, 0}, c1{cin + (size_t)nl_in * n, cstride, 0};
+            k_fma<<<ew_grid(n, nl, cnt), EW_THREADS, 0, stream_>>>(p0, vv, z0, c0, nullptr, 0, cout, 2 * poly, 0, g, d_limb_, nl);
+            k_fma<<<ew_grid(n, nl, cnt), EW_THREADS, 0, stream_>>>(p1, vv, z1, c1, nullptr, 0, cout + poly, 2 * poly, 0, g,
+                                                                 d_limb_, nl);
+            MK_HIP(hipGetLastError());
+        }
+    }
+}
+
 // ---- randomness ------------------------------------------------------------------------------------
 
 static ChaChaKey load_key(const uint8_t *key32) {
@@ -2152,6 +2235,15 @@ void Engine::sample_gauss(int32_t *out, size_t count, double sigma, const uint8_
     }
     t.thr[t.count - 1] = ~0ull;
     k_sample_gauss<<<(unsigned)((count + 255) / 256), 256, 0, stream_>>>(out, count, key, sid, t);
+    MK_HIP(hipGetLastError());
+}
+
+void Engine::sample_gauss_wide(int64_t *out, size_t count, double sigma, const uint8_t *key32, uint32_t sid) {
+    need_device();
+    const ChaChaKey key = load_key(key32);
+    if (!count) return;
+    const size_t pairs = (count + 1) / 2;
+    k_sample_gauss_wide<<<(unsigned)((pairs + 255) / 256), 256, 0, stream_>>>(out, count, sigma, key, sid);
     MK_HIP(hipGetLastError());
 }
 

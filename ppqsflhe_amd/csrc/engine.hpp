@@ -137,12 +137,18 @@ public:
                   const int32_t *e1, u64 *evk);
     void encrypt(const u64 *pk, const u64 *pt, const int8_t *v, const int32_t *e0, const int32_t *e1,
                  u64 *ct, uint32_t n_ct, uint32_t nl);
+    // re-randomisation before a key switch: out = ct + Enc_pk(0; v, e0, e1) on the first nl limbs of ct
+    // u64[n_ct][2][nl_in][N]; v int8[n_ct][N], e0 / e1 int64[n_ct][N] (|e| < 2^62); out u64[n_ct][2][nl][N], may be ct
+    // when nl_in == nl
+    void rerandomize(const u64 *ct, const u64 *pk, const int8_t *v, const int64_t *e0, const int64_t *e1, u64 *out,
+                     uint32_t n_ct, uint32_t nl_in, uint32_t nl);
     void lift_ntt(const double *coef, u64 *out, uint32_t n, uint32_t nl);
     void decrypt(const u64 *ct, const u64 *sk, u64 *m, uint32_t n_ct, uint32_t nl);
     // counter-based samplers (ChaCha20 block function under a 256-bit key): element i of stream sid is a pure
     // function of (key, sid, i), independent of launch shape
     void sample_ternary(int8_t *out, size_t count, const uint8_t *key32, uint32_t sid);
     void sample_gauss(int32_t *out, size_t count, double sigma, const uint8_t *key32, uint32_t sid);
+    void sample_gauss_wide(int64_t *out, size_t count, double sigma, const uint8_t *key32, uint32_t sid);  // rint(sigma z)
     void sample_uniform(u64 *out, uint32_t items, uint32_t nl, bool with_p, const uint8_t *key32, uint32_t sid);
     void chacha_block(uint32_t *d_out16, const uint8_t *key32, uint32_t counter, const uint32_t nonce[3]);  // KAT hook
     // seeded ciphertexts: a = sample_uniform(1 poly, nl, Q only) of stream (key, sid).  encrypt_seeded: item t of

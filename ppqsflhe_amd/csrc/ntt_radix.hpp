@@ -2149,4 +2149,183 @@ __global__ __launch_bounds__(NTT_THREADS, INVP ? MK_INVP_WAVES : MK_INNERQ_WAVES
     }
 }
 
+// =====================================================================================
+// Re-randomisation before a key switch (mkckks_rerandomize_batch; Engine::rerandomize):
+//   out0 = ct0 + b * NTT(v) + NTT(e0),  out1 = ct1 + a * NTT(v) + NTT(e1)   per limb, (b, a) the public key.
+// Two kernels; the lifted polynomials exist in HBM only as the column pass's output, never in COEFFICIENT or in
+// EVALUATION form.
+// =====================================================================================
+
+// exact residue of a signed integer (|v| < 2^63): the signed fold of k_lift.  An fp64-class limb takes the same integer
+// reduction and converts the canonical residue (below 2^51) afterwards: a 62-bit value does not fit the 53 bits of the
+// fp path, its residue does.
+MK_D u64 lift_signed(int64_t v, const LimbConst &lc) {
+    const u64 m = reduce_word(v < 0 ? (u64)0 - (u64)v : (u64)v, lc);
+    return (v < 0 && m != 0) ? lc.q - m : m;
+}
+MK_D u64 lift_signed(int8_t v, const LimbConst &lc) { return v == 0 ? 0 : (v > 0 ? 1 : lc.q - 1); }
+
+struct LiftIo {
+    const int8_t *v;         // [items][N] ternary
+    const int64_t *e0, *e1;  // [items][N]
+    u64 *out;                // [items][3][nl][N]: V, E0, E1 after the column pass (lazy u64, doubles on an fp limb)
+    uint32_t nl;
+    unsigned long long slot_mask;  // Q limbs (slot == limb id) of this instance's arithmetic class
+    uint32_t nsel;
+};
+
+// Forward column pass with lift on load (the !INV branch of k_ntt_col_r, inputs computed as k_switch_col computes
+// them): the H inputs of a thread are small signed integers reduced into the limb.  The 17 N source bytes of a
+// ciphertext feed all of its limbs.  Grid (column tile, 3 * nsel: polynomial-major, item).
+template <int LOG_H, int AR>
+__global__ __launch_bounds__(NTT_THREADS, 4) void k_lift_col(LiftIo io, NttTables T) {
+    using TL = ColTile<LOG_H>;
+    constexpr int H = TL::H, S = TL::S;
+    __shared__ u64 lds[TL::WORDS + ColTwB<LOG_H>::WORDS];
+    const uint32_t n = 1u << T.log_n, r2 = 1u << T.log_r2;
+    const uint32_t which = blockIdx.y / io.nsel, sl = nth_set_bit(io.slot_mask, blockIdx.y % io.nsel), item = blockIdx.z;
+    const LimbConst lc = T.limb[sl];
+    if ((lc.fp != 0) != (AR == AR_FP)) return;  // never: the host selects the limbs of this instance's class
+    const int c = threadIdx.x % S, j = threadIdx.x / S;
+    const size_t s0 = (size_t)item * n + blockIdx.x * S + c;
+    u64 x[H];
+    if (which == 0) {
+#pragma unroll
+        for (int k = 0; k < H; ++k) x[k] = lift_signed(io.v[s0 + (size_t)(j + H * k) * r2], lc);
+    } else {
+        const int64_t *e = (which == 1 ? io.e0 : io.e1) + s0;
+#pragma unroll
+        for (int k = 0; k < H; ++k) x[k] = lift_signed(e[(size_t)(j + H * k) * r2], lc);
+    }
+    if (AR == AR_FP) {  // canonical residues -> doubles (exact, q < 2^51)
+#pragma unroll
+        for (int k = 0; k < H; ++k) x[k] = dbits(u52_to_double(x[k]));
+    }
+    u64 *dst = io.out + (((size_t)item * 3 + which) * io.nl + sl) * n + blockIdx.x * S + c;
+    col_forward_finish<LOG_H, AR>(x, lds, T.tw + (size_t)sl * n, T.tw_sh + (size_t)sl * n, lc, j, c, dst, r2);
+}
+
+struct RerandArgs {
+    const u64 *col;    // [items][3][nl][N] from k_lift_col
+    const u64 *ct;     // [items][2][nl_in][N], first nl limbs read
+    const u64 *pk;     // [2][D][N], addressed by limb id
+    u64 *out;          // [items][2][nl][N]; may be ct when nl_in == nl (every word is read by the thread that writes it)
+    uint32_t nl_in, nl, D;
+    unsigned long long slot_mask;
+    uint32_t nsel;
+};
+
+// the forward row pass of k_ntt_row_r on this workgroup's S rows of `src`, result canonical in the LDS tile (each wave
+// its own rows: WaveOwnership).  twa / twa_sh are staged by the caller.
+template <int LOG_H, int AR>
+MK_D void rerand_row_forward(const u64 *src, u64 *lds, const u64 *twa, const u64 *twa_sh, const u64 *twb, uint32_t row0,
+                             int g, int j, const LimbConst &lc) {
+    using TL = RowTile<LOG_H>;
+    constexpr int H = TL::H, R = TL::R;
+    u64 x[H], w[H - 1], wp[H - 1];
+#pragma unroll
+    for (int k = 0; k < H; ++k) x[k] = ld_pass(src + (size_t)g * R + j + H * k);
+    RowTwA<LOG_H>::fetch(twa, twa_sh, g, w, wp);
+    radix_forward_any<LOG_H, AR>(x, w, wp, lc);
+    load_rowb_twiddles<LOG_H>(twb, row0 + g, j, w, wp);
+    wave_lds_sync();  // the previous polynomial's copy-out has read the tile
+#pragma unroll
+    for (int k = 0; k < H; ++k) lds[TL::at(g, j + H * k)] = x[k];
+    wave_lds_sync();
+#pragma unroll
+    for (int k = 0; k < H; ++k) x[k] = lds[TL::at(g, H * j + k)];
+    radix_forward_any<LOG_H, AR>(x, w, wp, lc);
+#pragma unroll
+    for (int k = 0; k < H; ++k)
+        lds[TL::at(g, H * j + k)] = (AR == AR_FP) ? fp_to_canonical(bitsd(x[k]), lc.qd, lc.qinv) : canon8(x[k], lc.q, lc.q2);
+    wave_lds_sync();
+}
+
+// Row pass with the re-randomisation tail: one workgroup per (ciphertext, limb, row tile) finishes the forward transform
+// of V, E0 and E1 for its S rows, one after the other, and the copy-outs of E0 / E1 write out0 = ct0 + b V + E0 and
+// out1 = ct1 + a V + E1.  Products as k_fma (mul_mod: both factors vary).  V across the three transforms, two ways:
+//   VLDS = true  (the product: 4 % faster at N = 2^16): V stays in a tile of its own, E0 / E1 go through a
+//                second one and the products are formed in their copy-outs (2 x 34 KiB at 256-point rows);
+//   VLDS = false (-DMK_RERAND_VLDS=0, kept for the A/B): ONE LDS tile; b*V and a*V of the thread's own copy-out words
+//                wait in registers (2 x 2 PAIRS words) while E0 and E1 are transformed.
+// Grid order of k_ntt_row_r: the ciphertexts of one (limb, tile) are neighbours in one XCD's queue, so the twiddle tile
+// and the two public-key tiles are fetched once and then hit in L2.
+#ifndef MK_RERAND_VLDS
+#define MK_RERAND_VLDS 1
+#endif
+template <int LOG_H, int AR, bool VLDS = (MK_RERAND_VLDS != 0)>
+__global__ __launch_bounds__(NTT_THREADS) void k_rerand_row(RerandArgs a, NttTables T) {
+    using TL = RowTile<LOG_H>;
+    using TA = RowTwA<LOG_H>;
+    constexpr int H = TL::H, S = TL::S, R = TL::R, PAIRS = S * R / 2 / NTT_THREADS;
+    __shared__ u64 lds[(VLDS ? 2 : 1) * TL::WORDS + 2 * TA::WORDS];
+    u64 *lds_e = lds + (VLDS ? TL::WORDS : 0);  // tile of E0 / E1
+    u64 *twa = lds_e + TL::WORDS, *twa_sh = twa + TA::WORDS;
+    const uint32_t n = 1u << T.log_n, r1 = 1u << T.log_r1;
+    const uint32_t tiles = r1 / S, groups = tiles * a.nsel, items = gridDim.x / groups;
+    uint32_t grp, item;
+    group_member(blockIdx.x, groups, items, T.cu_affine, grp, item);
+    const uint32_t sl = nth_set_bit(a.slot_mask, grp / tiles);  // Q limb: slot == limb id
+    const LimbConst lc = T.limb[sl];
+    if ((lc.fp != 0) != (AR == AR_FP)) return;  // block-uniform
+    const uint32_t row0 = (grp % tiles) * S;
+    const int g = threadIdx.x / H, j = threadIdx.x % H;
+    const size_t poly = (size_t)a.nl * n, tile = (size_t)sl * n + (size_t)row0 * R;
+    const u64 *col = a.col + (size_t)item * 3 * poly + tile;
+    const u64 *twb = T.twb + (size_t)sl * 2 * n;
+    stage_twiddles_wave<LOG_H>(twa, twa_sh, T.tw + (size_t)sl * n, T.tw_sh + (size_t)sl * n, r1 + row0);
+    wave_lds_sync();
+
+    rerand_row_forward<LOG_H, AR>(col, lds, twa, twa_sh, twb, row0, g, j, lc);
+    const ulong2 *pk0 = reinterpret_cast<const ulong2 *>(a.pk + tile), *pk1 = reinterpret_cast<const ulong2 *>(a.pk + (size_t)a.D * n + tile);
+    ulong2 bv[PAIRS], av[PAIRS];
+    if (!VLDS) {
+#pragma unroll
+        for (int i = 0; i < PAIRS; ++i) {
+            const int e = wave_pair<LOG_H>(i);
+            const int gg = (2 * e) / R, xx = (2 * e) % R;
+            const u64 vx = lds[TL::at(gg, xx)], vy = lds[TL::at(gg, xx + 1)];
+            const ulong2 b = pk0[e], aa = pk1[e];
+            bv[i] = ulong2{mul_mod(b.x, vx, lc), mul_mod(b.y, vy, lc)};
+            av[i] = ulong2{mul_mod(aa.x, vx, lc), mul_mod(aa.y, vy, lc)};
+        }
+    }
+
+    const u64 *c0 = a.ct + (size_t)item * 2 * a.nl_in * n + tile;
+    u64 *o0 = a.out + (size_t)item * 2 * poly + tile;
+    rerand_row_forward<LOG_H, AR>(col + poly, lds_e, twa, twa_sh, twb, row0, g, j, lc);
+#pragma unroll
+    for (int i = 0; i < PAIRS; ++i) {
+        const int e = wave_pair<LOG_H>(i);
+        const int gg = (2 * e) / R, xx = (2 * e) % R;
+        const ulong2 c = ld_pass2(reinterpret_cast<const ulong2 *>(c0) + e);
+        if (VLDS) {
+            const ulong2 k = pk0[e];
+            bv[i] = ulong2{mul_mod(k.x, lds[TL::at(gg, xx)], lc), mul_mod(k.y, lds[TL::at(gg, xx + 1)], lc)};
+        }
+        ulong2 r;
+        r.x = add_mod(add_mod(c.x, bv[i].x, lc.q), lds_e[TL::at(gg, xx)], lc.q);
+        r.y = add_mod(add_mod(c.y, bv[i].y, lc.q), lds_e[TL::at(gg, xx + 1)], lc.q);
+        st_pass2(reinterpret_cast<ulong2 *>(o0) + e, r);
+    }
+
+    rerand_row_forward<LOG_H, AR>(col + 2 * poly, lds_e, twa, twa_sh, twb, row0, g, j, lc);
+    const u64 *c1 = c0 + (size_t)a.nl_in * n;
+    u64 *o1 = o0 + poly;
+#pragma unroll
+    for (int i = 0; i < PAIRS; ++i) {
+        const int e = wave_pair<LOG_H>(i);
+        const int gg = (2 * e) / R, xx = (2 * e) % R;
+        const ulong2 c = ld_pass2(reinterpret_cast<const ulong2 *>(c1) + e);
+        if (VLDS) {
+            const ulong2 k = pk1[e];
+            av[i] = ulong2{mul_mod(k.x, lds[TL::at(gg, xx)], lc), mul_mod(k.y, lds[TL::at(gg, xx + 1)], lc)};
+        }
+        ulong2 r;
+        r.x = add_mod(add_mod(c.x, av[i].x, lc.q), lds_e[TL::at(gg, xx)], lc.q);
+        r.y = add_mod(add_mod(c.y, av[i].y, lc.q), lds_e[TL::at(gg, xx + 1)], lc.q);
+        st_pass2(reinterpret_cast<ulong2 *>(o1) + e, r);
+    }
+}
+
 }  // namespace mk

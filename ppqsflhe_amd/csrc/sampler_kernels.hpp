@@ -120,6 +120,18 @@ __global__ void k_sample_gauss(int32_t *out, size_t n, ChaChaKey key, uint32_t s
     out[i] = sign ? -k : k;
 }
 
+// wide ("flooding") Gaussian for the re-randomisation before a key switch (mkckks_sample_gauss_wide): element i is
+// rint(sigma * z), z = component i % 2 of chacha_normal_pair(key, sid, i / 2) -- a rounded continuous normal, which is a
+// stand-in for D_{Z,sigma} only for sigma >= 2^6 (the host checks the range).  |z| <= sqrt(2 * 53 ln 2) < 8.6 (u1 >= 2^-53),
+// so |e| < 2^60 at sigma = 2^56.  One lane = one pair, two stores.
+__global__ void k_sample_gauss_wide(int64_t *out, size_t n, double sigma, ChaChaKey key, uint32_t sid) {
+    const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (2 * p >= n) return;
+    const double2 z = chacha_normal_pair(key, sid, p);
+    out[2 * p] = (int64_t)rint(sigma * z.x);
+    if (2 * p + 1 < n) out[2 * p + 1] = (int64_t)rint(sigma * z.y);
+}
+
 // uniform residues in [0, q) per limb by rejection (accept r < 2^64 - (2^64 mod q)); out [items][slots][N]
 __global__ void k_sample_uniform(u64 *out, uint32_t n, uint32_t nl, uint32_t L, const LimbConst *limb, ChaChaKey key,
                                  uint32_t sid) {

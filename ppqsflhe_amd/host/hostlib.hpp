@@ -448,6 +448,35 @@ inline bool load_secret_key(Session &s, const std::string &path, std::vector<uin
 }
 
 // ------------------------------------------------------------------------------------------------
+// HRA-secure re-encryption (changeCipherDomain --hra, serverRound --hra-back): cc->ReEncrypt(ct, reKey, publicKey)
+// re-randomises every ciphertext with an encryption of zero under the public key of the domain it is in, errors from a
+// wide Gaussian of sigma = 2^bits, before the key switch (mkckks_rerandomize_batch; include/mkckks.h has the noise rule).
+// Randomness of ciphertext t: streams 3t (v), 3t + 1 (e0), 3t + 2 (e1) of `key`, a fresh OS-drawn key per use.
+// ------------------------------------------------------------------------------------------------
+constexpr uint32_t HRA_SIGMA_BITS_DEFAULT = 20, HRA_SIGMA_BITS_MIN = 6, HRA_SIGMA_BITS_MAX = 56;
+inline bool parse_hra_sigma_bits(const std::string &v, uint32_t &bits) {
+    if (v.empty() || v.size() > 2 || v.find_first_not_of("0123456789") != std::string::npos) return false;
+    bits = (uint32_t)std::atoi(v.c_str());
+    return bits >= HRA_SIGMA_BITS_MIN && bits <= HRA_SIGMA_BITS_MAX;
+}
+// device scratch of hra_rerandomize for n_ct ciphertexts, in 64-bit words: e0, e1 (int64 each), then v (int8)
+inline size_t hra_scratch_words(size_t n_ct, uint32_t N) { return 2 * n_ct * N + (n_ct * N + 7) / 8; }
+// d_out[t] = first nl limbs of d_ct[t] (nl_in limbs each) + Enc_pk(0); d_out may be d_ct when nl_in == nl
+inline void hra_rerandomize(Session &s, const uint64_t *d_ct, const uint64_t *d_pk, uint64_t *d_scratch, uint64_t *d_out,
+                            uint32_t n_ct, uint32_t nl_in, uint32_t nl, uint32_t sigma_bits, const SamplerKey &key) {
+    const size_t N = s.N();
+    int64_t *d_e0 = reinterpret_cast<int64_t *>(d_scratch), *d_e1 = d_e0 + n_ct * N;
+    int8_t *d_v = reinterpret_cast<int8_t *>(d_e1 + n_ct * N);
+    const double sigma = std::ldexp(1.0, (int)sigma_bits);
+    for (uint32_t t = 0; t < n_ct; ++t) {
+        Session::check(mkckks_sample_ternary(s.ctx(), d_v + t * N, N, key.bytes, 3 * t));
+        Session::check(mkckks_sample_gauss_wide(s.ctx(), d_e0 + t * N, N, sigma, key.bytes, 3 * t + 1));
+        Session::check(mkckks_sample_gauss_wide(s.ctx(), d_e1 + t * N, N, sigma, key.bytes, 3 * t + 2));
+    }
+    Session::check(mkckks_rerandomize_batch(s.ctx(), d_ct, d_pk, d_v, d_e0, d_e1, d_out, n_ct, nl_in, nl));
+}
+
+// ------------------------------------------------------------------------------------------------
 // weights_summary envelope helpers: the ciphertext fields of one file in a fixed order
 // ------------------------------------------------------------------------------------------------
 struct CtRef {

@@ -317,7 +317,7 @@ class RoundCache {
 public:
     explicit RoundCache(Session &s) : s_(s) {}
     ~RoundCache() {
-        for (Slot *b : {&all, &sum, &out, &evk, &back, &back_evk})
+        for (Slot *b : {&all, &sum, &out, &evk, &back, &back_evk, &hra, &hra_rand, &hra_pk})
             if (b->p) mkckks_dev_free(s_.ctx(), b->p);
     }
     RoundCache(const RoundCache &) = delete;
@@ -347,6 +347,8 @@ public:
         return *r;
     }
     Slot all, sum, out, evk, back, back_evk;
+    Slot hra, hra_rand, hra_pk;          // --hra-back: the re-randomised aggregate (prefix), its randomness, the public key
+    std::string hra_pk_name;             // public key resident in hra_pk.p (by file name, like the back keys)
     std::vector<std::string> evk_names;  // keys resident in evk.p, in order
     std::unique_ptr<PinnedRing> ring, out_pin;
     std::string warm_shape;              // "<nl>/<chunk>/<n_pre>/<n_plain>/<rescale>" the kernels were launched with

@@ -21,6 +21,12 @@
 // k + 1 limbs are key-switched and rescaled to k.  With it a back key of "-" names a client that already is in the target
 // domain: its file is mkckks_compress_batch of the aggregate.  Each file equals changeCipherDomain ... --limbs <k> run on
 // <output_aggfile>; the aggregate file itself is never compacted.
+// --hra-back <target_domain_pubkey> [--hra-sigma-bits <s>] (after the --back list): HRA-secure distribution leg,
+// cc->ReEncrypt(ct, reKey, publicKey).  The aggregate is re-randomised ONCE per round under the public key of the domain
+// it is in (mkckks_rerandomize_batch, errors of sigma = 2^s, s in [6, 56], default 20; fresh OS-drawn key per round) into
+// a buffer of its own -- with --back-limbs only its k + 1-limb prefix -- and every keyed back entry is re-encrypted from
+// that buffer; all back keys of a round share the one mask, the key-switch noise is per key anyway.  The aggregate file
+// and "-" entries are untouched; the public key stays resident by file name.  Back files differ from run to run.
 // Binary (MKWS) envelopes take the I/O pipeline of iopipe.hpp: files are indexed, not loaded; reader threads fill pinned
 // slots, uploads run beside the reads, residues are range-checked on the device, results are written by pwrite() from
 // pinned slots.  MKCKKS_SYNC_IO=1 forces the synchronous path (every ciphertext through read_envelope / decode_ct /
@@ -43,6 +49,9 @@ struct RoundArgs {
     std::vector<std::string> rekey_paths, enc_paths, back_keys, back_outs;
     bool compact = false;     // --back-limbs given
     uint32_t back_limbs = 0;  // its value
+    std::string hra_pk;       // --hra-back: public key file of the aggregate's domain (empty: no re-randomisation)
+    uint32_t hra_bits = HRA_SIGMA_BITS_DEFAULT;
+    bool hra_bits_ok = true;  // false: --hra-sigma-bits was no integer in [6, 56] (reported by run_round)
 };
 // tokens: <output_aggfile> <rekey_1|-> <encfile_1> ... [--back <rekey_back_1> <output_encfile_1> ...]
 static bool parse_round(std::vector<std::string> t, RoundArgs &a) {
@@ -58,6 +67,25 @@ static bool parse_round(std::vector<std::string> t, RoundArgs &a) {
             t.erase(t.begin() + i, t.begin() + i + 2);
             break;
         }
+    std::string hra_pk;
+    uint32_t hra_bits = HRA_SIGMA_BITS_DEFAULT;
+    bool hra_bits_ok = true, have_bits = false;
+    for (size_t i = 1; i < t.size(); ++i)
+        if (t[i] == "--hra-back") {  // one value, taken out the same way
+            if (i + 1 >= t.size() || t[i + 1].empty()) return false;
+            hra_pk = t[i + 1];
+            t.erase(t.begin() + i, t.begin() + i + 2);
+            break;
+        }
+    for (size_t i = 1; i < t.size(); ++i)
+        if (t[i] == "--hra-sigma-bits") {
+            if (i + 1 >= t.size()) return false;
+            have_bits = true;
+            hra_bits_ok = parse_hra_sigma_bits(t[i + 1], hra_bits);
+            t.erase(t.begin() + i, t.begin() + i + 2);
+            break;
+        }
+    if (have_bits && hra_pk.empty()) return false;
     size_t n_args = t.size();
     for (size_t i = 1; i < t.size(); ++i)
         if (t[i] == "--back") {
@@ -67,7 +95,11 @@ static bool parse_round(std::vector<std::string> t, RoundArgs &a) {
     const size_t n_back = t.size() - n_args - (n_args < t.size() ? 1 : 0);
     if (n_args < 3 || (n_args - 1) % 2 != 0 || n_back % 2 != 0 || (n_args < t.size() && n_back == 0)) return false;
     if (compact && n_back == 0) return false;
+    if (!hra_pk.empty() && n_back == 0) return false;
     a = RoundArgs{};
+    a.hra_pk = hra_pk;
+    a.hra_bits = hra_bits;
+    a.hra_bits_ok = hra_bits_ok;
     a.compact = compact;
     a.back_limbs = back_limbs;
     a.output_file = t[0];
@@ -85,6 +117,7 @@ static bool parse_round(std::vector<std::string> t, RoundArgs &a) {
 struct ServerState {
     explicit ServerState(Session &s) : cache(s) {}
     std::map<std::string, std::vector<uint64_t>> keys;  // re-encryption keys by file name, loaded once per process
+    std::map<std::string, std::vector<uint64_t>> pks;   // --hra-back public keys, the same way
     RoundCache cache;
     std::vector<std::string> back_names;  // back keys resident in cache.back_evk, slot by slot (by file name)
     double t_ctx = 0;      // ms: context creation
@@ -171,6 +204,21 @@ static int run_round(Session &s, ServerState &st, const RoundArgs &a) {
             std::cerr << "[round] ERROR: a back key of - needs --back-limbs" << std::endl;
             return 1;
         }
+    if (!a.hra_pk.empty()) {
+        if (!a.hra_bits_ok) {
+            std::cerr << "[round] ERROR: --hra-sigma-bits needs an integer in [" << HRA_SIGMA_BITS_MIN << ", " << HRA_SIGMA_BITS_MAX
+                      << "]" << std::endl;
+            return 1;
+        }
+        if (!st.pks.count(a.hra_pk)) {
+            std::vector<uint64_t> pk;
+            if (!load_public_key(s, a.hra_pk, pk)) {
+                std::cerr << "[round] ERROR: Failed to load public key from " << a.hra_pk << std::endl;
+                return 1;
+            }
+            st.pks[a.hra_pk] = std::move(pk);
+        }
+    }
     if (a.compact) {
         if (a.back_limbs < 1) {
             std::cerr << "[round] ERROR: --back-limbs must be at least 1" << std::endl;
@@ -317,6 +365,26 @@ static int run_back_leg(Session &s, ServerState &st, const RoundArgs &a, const s
         else std::cout << "[round] aggregate compressed for its own domain -> " << a.back_outs[k] << "\n";
     };
     const size_t words = B * (size_t)2 * out_nl * N;  // one key's output
+    // --hra-back: what the keyed entries read is the re-randomised aggregate (its k + 1-limb prefix with --back-limbs),
+    // one re-randomisation per round; agg.d_out itself stays as it is
+    const uint64_t *d_src = agg.d_out;
+    uint32_t src_nl = agg.meta.nl;
+    const bool hra = !a.hra_pk.empty();
+    if (hra && B && n_keys) {
+        const std::vector<uint64_t> &pk = st.pks.at(a.hra_pk);
+        if (pk.size() > st.cache.hra_pk.words) st.cache.hra_pk_name.clear();
+        uint64_t *d_pk = st.cache.grow(st.cache.hra_pk, pk.size());
+        if (st.cache.hra_pk_name != a.hra_pk) {
+            st.cache.hra_pk_name.clear();
+            Session::check(mkckks_upload(s.ctx(), d_pk, pk.data(), pk.size() * 8));
+            st.cache.hra_pk_name = a.hra_pk;
+        }
+        src_nl = k_limbs ? k_limbs + 1 : agg.meta.nl;
+        uint64_t *d_rr = st.cache.grow(st.cache.hra, B * (size_t)2 * src_nl * N);
+        hra_rerandomize(s, agg.d_out, d_pk, st.cache.grow(st.cache.hra_rand, hra_scratch_words(B, N)), d_rr, (uint32_t)B,
+                        agg.meta.nl, src_nl, a.hra_bits, fresh_key());
+        d_src = d_rr;
+    }
     if (!loop && B && n_keys) {
         // keys per call: the outputs of one call are bounded (MKCKKS_BACK_MAX_MIB, default 16 GiB) beside the round's buffers
         size_t max_mib = 16384;
@@ -336,11 +404,11 @@ static int run_back_leg(Session &s, ServerState &st, const RoundArgs &a, const s
         for (size_t k0 = 0; k0 < n_keys; k0 += per_call) {
             const size_t gk = std::min(per_call, n_keys - k0);
             if (k_limbs)
-                Session::check(mkckks_reencrypt_fanout_compact_batch(s.ctx(), agg.d_out, d_evks + k0 * evk_words, d_back,
-                                                                     (uint32_t)gk, (uint32_t)B, agg.meta.nl, k_limbs));
+                Session::check(mkckks_reencrypt_fanout_compact_batch(s.ctx(), d_src, d_evks + k0 * evk_words, d_back,
+                                                                     (uint32_t)gk, (uint32_t)B, src_nl, k_limbs));
             else
-                Session::check(mkckks_reencrypt_fanout_batch(s.ctx(), agg.d_out, d_evks + k0 * evk_words, d_back, (uint32_t)gk,
-                                                             (uint32_t)B, agg.meta.nl));
+                Session::check(mkckks_reencrypt_fanout_batch(s.ctx(), d_src, d_evks + k0 * evk_words, d_back, (uint32_t)gk,
+                                                             (uint32_t)B, src_nl));
             for (size_t k = 0; k < gk; ++k) write_one(real[k0 + k], d_back + k * words);
         }
     } else {
@@ -353,10 +421,10 @@ static int run_back_leg(Session &s, ServerState &st, const RoundArgs &a, const s
                 Session::check(mkckks_upload(s.ctx(), d_back_evk, keys[real[k]]->data(), evk_words * 8));
                 ++uploaded;
                 if (k_limbs)
-                    Session::check(mkckks_reencrypt_fanout_compact_batch(s.ctx(), agg.d_out, d_back_evk, d_back, 1, (uint32_t)B,
-                                                                         agg.meta.nl, k_limbs));
+                    Session::check(mkckks_reencrypt_fanout_compact_batch(s.ctx(), d_src, d_back_evk, d_back, 1, (uint32_t)B,
+                                                                         src_nl, k_limbs));
                 else
-                    Session::check(mkckks_reencrypt_batch(s.ctx(), agg.d_out, d_back_evk, d_back, (uint32_t)B, agg.meta.nl));
+                    Session::check(mkckks_reencrypt_batch(s.ctx(), d_src, d_back_evk, d_back, (uint32_t)B, src_nl));
             }
             write_one(real[k], d_back);
         }
@@ -377,6 +445,7 @@ static int run_back_leg(Session &s, ServerState &st, const RoundArgs &a, const s
     std::cout << "[round] back leg: " << n_entries << " keys x " << B << " ciphertexts in " << ms << " ms -> "
               << (double)(n_entries * B) / ms * 1e3 << " ciphertexts/s, " << uploaded << " key(s) uploaded";
     if (k_limbs) std::cout << ", " << k_limbs << " limbs";
+    if (hra) std::cout << ", re-randomised at sigma 2^" << a.hra_bits;
     std::cout << "\n";
     return 0;
 }
@@ -384,7 +453,7 @@ static int run_back_leg(Session &s, ServerState &st, const RoundArgs &a, const s
 int main(int argc, char *argv[]) {
     auto usage = [&] {
         std::cerr << "Usage: " << argv[0] << " <cc_path> <output_aggfile> <rekey_1|-> <encfile_1> [<rekey_2|-> <encfile_2> ...]"
-                  << " [--back <rekey_back_1|-> <output_encfile_1> ... [--back-limbs <k>]]\n       " << argv[0]
+                  << " [--back <rekey_back_1|-> <output_encfile_1> ... [--back-limbs <k>] [--hra-back <target_domain_pubkey> [--hra-sigma-bits <s>]]]\n       " << argv[0]
                   << " <cc_path> --rounds <file with one such argument list (after <cc_path>) per line>" << std::endl;
         return 1;
     };
