@@ -344,6 +344,51 @@ int mkckks_decode_flood_batch(mkckks_ctx *c, const uint64_t *d_m, double *d_vals
 int mkckks_decrypt_batch(mkckks_ctx *c, const uint64_t *d_ct, const uint64_t *d_sk, uint64_t *d_m,
                          uint32_t n_ct, uint32_t nl);
 
+/* ==== threshold decryption: a joint public key whose secret nobody holds ======================================
+ * The reference enables the capability (server/src/genCC.cpp:73, Enable(MULTIPARTY)) and never calls it; its clients'
+ * uploads are re-encrypted into ONE client's domain, whose key then opens every individual upload.  With a joint key
+ * pk = (sum b_i, a), secret sum s_i, the aggregate is opened by n partial decryptions that are summed.
+ *
+ * ---- cc->MultipartyKeyGen(prevPublicKey) -------------------------------------------------------------------------
+ * The joining key generation: for all D limbs
+ *     pk[0] = pk_prev[0] + NTT(e) - pk_prev[1] * NTT(s),   pk[1] = pk_prev[1];   sk = NTT(s) as in mkckks_keygen.
+ * d_pk_prev u64[2][D][N] (EVALUATION); s ternary int8[N], e int32[N] (COEFFICIENT), the caller's randomness as in
+ * mkckks_keygen; d_pk out u64[2][D][N], d_sk out u64[D][N].  d_pk may be d_pk_prev (in place); no other overlap.  The
+ * first party calls mkckks_keygen, every further party this with its predecessor's public key; the last party's
+ * public key is the joint key.  mkckks_rekeygen takes it like any public key (own domain -> joint domain), and so does
+ * mkckks_encrypt_batch. */
+int mkckks_keygen_join(mkckks_ctx *c, const uint64_t *d_pk_prev, const int8_t *d_s, const int32_t *d_e, uint64_t *d_pk,
+                       uint64_t *d_sk);
+/* ---- cc->MultipartyDecryptMain (lead = 0) / cc->MultipartyDecryptLead (lead != 0) --------------------------------
+ * One party's share of a decryption under the joint key; for t < n_ct, i < nl:
+ *     share[t][i] = INTT_i( ct[t][1][i] * sk[i] + (lead ? ct[t][0][i] : 0) ) + (e[t] mod q_i)     mod q_i
+ * in COEFFICIENT format, canonical residues (the result equals exact integer arithmetic word for word).
+ * d_ct u64[n_ct][2][nl_in][N] read at its first nl limbs (a lower level is a prefix, as in mkckks_rerandomize_batch);
+ * d_sk u64[D][N] addressed by limb id (the party's own sk of mkckks_keygen / mkckks_keygen_join); d_e int64[n_ct][N]
+ * smudging errors with |e| < 2^62 (the caller's contract; mkckks_sample_gauss_wide keeps it); d_share out
+ * u64[n_ct][nl][N].  Every pointer is required, d_e included: a share without smudging gives c1 * s_i away, so there
+ * is no noiseless mode (tests pass zeros).  1 <= nl <= nl_in <= L; d_share must not overlap d_ct (MKCKKS_E_INVALID);
+ * n_ct == 0 is a no-op.  Upstream adds the noise in EVALUATION and transforms after the fusion; by linearity mod q_i
+ * the two orders give the same bits.  Bit-identical to mkckks_rerandomize_batch(v = 0, e0 = e, e1 = 0) followed by
+ * mkckks_decrypt_batch (lead), or the same on a copy whose component 0 is zero (lead = 0).
+ * Noise rule: n shares add sum_i e_i to the plaintext polynomial; the real part of slot k receives
+ * sum_j e_j cos(j theta_k), so the decoded values carry a Gaussian error of standard deviation
+ * sigma * sqrt(n * N / 2) / scale.  At noise degree 2 (scale ~ 2^(2p)) that is nothing for any sigma of the sampler; at
+ * scale 2^p it is the price of the statistical security sigma buys.
+ * Security rules: n-of-n -- the server plus any n - 1 parties learn the aggregate only, and a party that does not
+ * answer blocks the round (t-of-n is out of scope).  ONE share per ciphertext per party, with fresh errors each time:
+ * two shares of one ciphertext average the smudging away.  The key the smudging errors are drawn under keys nothing
+ * else. */
+int mkckks_partial_decrypt_batch(mkckks_ctx *c, const uint64_t *d_ct, const uint64_t *d_sk, const int64_t *d_e,
+                                 uint64_t *d_share, uint32_t n_ct, uint32_t nl_in, uint32_t nl, int lead);
+/* ---- cc->MultipartyDecryptFusion ---------------------------------------------------------------------------------
+ * m = sum_p shares[p] mod q_i: d_shares u64[n_parties][n_ct][nl][N] -> d_m u64[n_ct][nl][N], the layout
+ * mkckks_decrypt_batch writes, so mkckks_decode_batch / mkckks_decode_flood_batch follow unchanged.  n_parties >= 1;
+ * d_m may alias shares[0] (d_m == d_shares), any other overlap is MKCKKS_E_INVALID; n_ct == 0 is a no-op.  The
+ * caller guarantees that exactly ONE share was made with lead != 0 (the hosts check it from the share headers). */
+int mkckks_fuse_shares_batch(mkckks_ctx *c, const uint64_t *d_shares, uint64_t *d_m, uint32_t n_parties, uint32_t n_ct,
+                             uint32_t nl);
+
 /* ---- multi-GPU aggregation step (new) -----------------------
  * after an RCCL ncclSum over uint64 of `n_terms` canonical residues per word,
  * reduce every word mod its limb modulus: d_ct u64[n_ct][2][nl][N] in place. */

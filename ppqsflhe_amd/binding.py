@@ -80,6 +80,9 @@ SYMBOLS = {
     "mkckks_moddown_batch": (_int, [_vp, _vp, _vp, _u32, _u32]),
     "mkckks_keygen": (_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "mkckks_rekeygen": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mkckks_keygen_join": (_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "mkckks_partial_decrypt_batch": (_int, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _int]),
+    "mkckks_fuse_shares_batch": (_int, [_vp, _vp, _vp, _u32, _u32, _u32]),
     "mkckks_encrypt_batch": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32]),
     "mkckks_lift_ntt_batch": (_int, [_vp, _vp, _vp, _u32, _u32]),
     "mkckks_decrypt_batch": (_int, [_vp, _vp, _vp, _vp, _u32, _u32]),
@@ -432,6 +435,11 @@ class Context:
     def keygen(self, s, a, e, pk, sk):
         self._check(self._L.mkckks_keygen(self._h, _ptr(s), _ptr(a), _ptr(e), _ptr(pk), _ptr(sk)))
 
+    def keygen_join(self, pk_prev, s, e, pk, sk):
+        """MultipartyKeyGen(prevPublicKey): pk = (pk_prev[0] + e - pk_prev[1] * s, pk_prev[1]); the last party's pk is the
+        joint key, whose secret is the sum of the parties' sk."""
+        self._check(self._L.mkckks_keygen_join(self._h, _ptr(pk_prev), _ptr(s), _ptr(e), _ptr(pk), _ptr(sk)))
+
     def rekeygen(self, s_old, pk_new, u, e0, e1, evk):
         self._check(self._L.mkckks_rekeygen(self._h, _ptr(s_old), _ptr(pk_new), _ptr(u), _ptr(e0), _ptr(e1), _ptr(evk)))
 
@@ -501,3 +509,13 @@ class Context:
 
     def decrypt(self, ct, sk, m, n_ct, nl):
         self._check(self._L.mkckks_decrypt_batch(self._h, _ptr(ct), _ptr(sk), _ptr(m), n_ct, nl))
+
+    def partial_decrypt(self, ct, sk, e, share, n_ct, nl_in, nl, lead):
+        """share[t] = INTT(c1 * sk (+ c0 when lead)) + e[t] on the first nl limbs of ct[t]: one party's share of a threshold
+        decryption.  e int64 smudging errors (sample_gauss_wide), fresh for every call; exactly one party passes lead."""
+        self._check(self._L.mkckks_partial_decrypt_batch(self._h, _ptr(ct), _ptr(sk), _ptr(e), _ptr(share), n_ct, nl_in, nl,
+                                                         int(bool(lead))))
+
+    def fuse_shares(self, shares, m, n_parties, n_ct, nl):
+        """m = sum of shares[p] (MultipartyDecryptFusion), in the layout of `decrypt`; m may be shares[0]."""
+        self._check(self._L.mkckks_fuse_shares_batch(self._h, _ptr(shares), _ptr(m), n_parties, n_ct, nl))

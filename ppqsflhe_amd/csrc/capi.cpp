@@ -471,6 +471,44 @@ int mkckks_decrypt_batch(mkckks_ctx *c, const uint64_t *ct, const uint64_t *sk, 
         c->eng->decrypt(ct, sk, m, n_ct, nl);
     });
 }
+int mkckks_keygen_join(mkckks_ctx *c, const uint64_t *pk_prev, const int8_t *s, const int32_t *e, uint64_t *pk,
+                       uint64_t *sk) {
+    return guarded([&] {
+        need(c && pk_prev && s && e && pk && sk, "null argument");
+        c->eng->keygen_join(pk_prev, s, e, pk, sk);
+    });
+}
+int mkckks_partial_decrypt_batch(mkckks_ctx *c, const uint64_t *ct, const uint64_t *sk, const int64_t *e, uint64_t *share,
+                                 uint32_t n_ct, uint32_t nl_in, uint32_t nl, int lead) {
+    return guarded([&] {
+        need(c && ct && sk && e && share, "null argument");
+        const mk::ParamSet &ps = c->eng->params();
+        need(nl >= 1 && nl <= nl_in && nl_in <= ps.L, "need 1 <= nl <= nl_in <= L");
+        const size_t item_bytes = (size_t)n_ct * ps.n * sizeof(uint64_t);  // addresses only
+        const uintptr_t i_lo = (uintptr_t)ct, i_hi = i_lo + item_bytes * 2 * nl_in;
+        const uintptr_t o_lo = (uintptr_t)share, o_hi = o_lo + item_bytes * nl;
+        need(!(o_lo < i_hi && i_lo < o_hi), "share overlaps the ciphertexts");
+        if (!n_ct) return;
+        c->eng->partial_decrypt(ct, sk, e, share, n_ct, nl_in, nl, lead != 0);
+    });
+}
+int mkckks_fuse_shares_batch(mkckks_ctx *c, const uint64_t *shares, uint64_t *m, uint32_t n_parties, uint32_t n_ct,
+                             uint32_t nl) {
+    return guarded([&] {
+        need(c && shares && m, "null argument");
+        const mk::ParamSet &ps = c->eng->params();
+        need(n_parties >= 1, "need n_parties >= 1");
+        need(nl >= 1 && nl <= ps.L, "nl out of range");
+        if (m != shares) {  // shares[0] is the one allowed alias; addresses only
+            const size_t share_bytes = (size_t)n_ct * nl * ps.n * sizeof(uint64_t);
+            const uintptr_t i_lo = (uintptr_t)shares, i_hi = i_lo + share_bytes * n_parties;
+            const uintptr_t o_lo = (uintptr_t)m, o_hi = o_lo + share_bytes;
+            need(!(o_lo < i_hi && i_lo < o_hi), "output overlaps the shares");
+        }
+        if (!n_ct) return;
+        c->eng->fuse_shares(shares, m, n_parties, n_ct, nl);
+    });
+}
 int mkckks_reduce_mod_batch(mkckks_ctx *c, uint64_t *ct, uint32_t n_ct, uint32_t nl, uint32_t n_terms) {
     return guarded([&] {
         need(c && ct, "null argument");

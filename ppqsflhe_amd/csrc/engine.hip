@@ -2189,6 +2189,114 @@ void Engine::rerandomize(const u64 *ct, const u64 *pk, const int8_t *v, const in
     }
 }
 
+// ---- threshold decryption (MultipartyKeyGen / MultipartyDecryptLead, Main / MultipartyDecryptFusion) ---------------
+
+void Engine::keygen_join(const u64 *pk_prev, const int8_t *s, const int32_t *e, u64 *pk, u64 *sk) {
+    need_device();
+    const uint32_t n = ps_.n, D = ps_.D, L = ps_.L;
+    u64 *ee = workspace((size_t)D * n);
+    EwGeom g{n, L, L};
+    k_lift<int8_t><<<ew_grid(n, D, 1), EW_THREADS, 0, stream_>>>(s, sk, g, d_limb_, D);
+    k_lift<int32_t><<<ew_grid(n, D, 1), EW_THREADS, 0, stream_>>>(e, ee, g, d_limb_, D);
+    MK_HIP(hipGetLastError());
+    ntt_launch(sk, 1, L, D, false, nullptr, nullptr);
+    ntt_launch(ee, 1, L, D, false, nullptr, nullptr);
+    // b = b_prev + e - a*s ; a copied
+    Opnd x{pk_prev + (size_t)D * n, 0, 0}, y{sk, 0, 0}, z{ee, 0, 0}, w{pk_prev, 0, 0};
+    k_fma<<<ew_grid(n, D, 1), EW_THREADS, 0, stream_>>>(x, y, z, w, nullptr, 1, pk, 0, 0, g, d_limb_, D);
+    MK_HIP(hipGetLastError());
+    if (pk != pk_prev)
+        MK_HIP(hipMemcpyAsync(pk + (size_t)D * n, pk_prev + (size_t)D * n, (size_t)D * n * sizeof(u64), hipMemcpyDeviceToDevice,
+                              stream_));
+}
+
+template <int COL_H, int ROW_H>
+static void launch_pdec(PdecArgs pa, const NttTables &T, uint32_t cnt, hipStream_t s) {
+    const uint32_t r1 = 1u << T.log_r1, r2 = 1u << T.log_r2;
+    NttIo sel{};
+    sel.nslots = sel.nl = pa.nl;
+    for (int fp = 0; fp < 2; ++fp) {
+        const unsigned long long mask = class_mask(sel, T.h_fp_of, T.L, fp != 0);
+        const uint32_t nsel = (uint32_t)__builtin_popcountll(mask);
+        if (!nsel) continue;
+        pa.slot_mask = mask;
+        pa.nsel = nsel;
+        const dim3 rgrid((r1 / (256u >> ROW_H)) * nsel * cnt), cgrid(r2 / (256u >> COL_H), nsel, cnt);
+        if (fp) {
+            k_pdec_row<ROW_H, AR_FP><<<rgrid, NTT_THREADS, 0, s>>>(pa, T);
+            k_pdec_col<COL_H, AR_FP><<<cgrid, NTT_THREADS, 0, s>>>(pa, T);
+        } else {
+            with_int_arith(T, [&](auto ar) {
+                k_pdec_row<ROW_H, decltype(ar)::value><<<rgrid, NTT_THREADS, 0, s>>>(pa, T);
+                k_pdec_col<COL_H, decltype(ar)::value><<<cgrid, NTT_THREADS, 0, s>>>(pa, T);
+            });
+        }
+    }
+}
+template <int COL_H>
+static void launch_pdec_c(const PdecArgs &pa, const NttTables &T, uint32_t cnt, int row_h, hipStream_t s) {
+    switch (row_h) {
+        case 4: launch_pdec<COL_H, 4>(pa, T, cnt, s); break;
+        case 3: launch_pdec<COL_H, 3>(pa, T, cnt, s); break;
+        default: launch_pdec<COL_H, 2>(pa, T, cnt, s);
+    }
+}
+
+void Engine::partial_decrypt(const u64 *ct, const u64 *sk, const int64_t *e, u64 *share, uint32_t n_ct, uint32_t nl_in,
+                             uint32_t nl, bool lead) {
+    need_device();
+    check_nl(nl);
+    check_nl(nl_in);
+    if (nl > nl_in) throw std::invalid_argument("need nl <= nl_in");
+    if (!n_ct) return;
+    const uint32_t n = ps_.n;
+    const size_t poly = (size_t)nl * n;
+    // fused: the product inside the inverse row pass's copy-in, the error inside the inverse column pass's stores (two-round
+    // rows only); the library switches take the composition
+    const int col_h = fast_log_h(tabs_.log_r1, 1u << tabs_.log_r2), row_h = fast_row(tabs_.log_r2, 1u << tabs_.log_r1);
+    const bool fused = col_h != 0 && row_h >= 2 && row_h <= 4 && !knobs_.generic_ntt && !knobs_.no_fp64 && !knobs_.no_pm;
+    // the fused pair needs no workspace: its chunk is MKCKKS_CHUNK full-level ciphertexts' worth of limbs, so that a batch
+    // of compact (1-limb) ciphertexts is not cut into launches of 16 limb polynomials (measured launch-bound: DESIGN.md)
+    const uint32_t chunk = fused ? knobs_.chunk * (ps_.L / nl) : knobs_.chunk;
+    u64 *ws = fused ? nullptr : workspace(poly * (n_ct < chunk ? n_ct : chunk));
+    for (uint32_t b0 = 0; b0 < n_ct; b0 += chunk) {
+        const uint32_t cnt = n_ct - b0 < chunk ? n_ct - b0 : chunk;
+        const u64 *cin = ct + (size_t)b0 * 2 * nl_in * n;
+        const int64_t *eb = e + (size_t)b0 * n;
+        u64 *out = share + (size_t)b0 * poly;
+        if (fused) {
+            const PdecArgs pa{cin, sk, eb, out, nl_in, nl, lead ? 1u : 0u, 0, 0};
+            switch (col_h) {
+                case 4: launch_pdec_c<4>(pa, tabs_, cnt, row_h, stream_); break;
+                case 3: launch_pdec_c<3>(pa, tabs_, cnt, row_h, stream_); break;
+                default: launch_pdec_c<2>(pa, tabs_, cnt, row_h, stream_);
+            }
+            MK_HIP(hipGetLastError());
+        } else {  // Engine::decrypt on the prefix, then the lifted error added
+            EwGeom g{n, nl, ps_.L};
+            const size_t cstride = (size_t)2 * nl_in * n;
+            Opnd c1{cin + (size_t)nl_in * n, cstride, 0}, s{sk, 0, 1}, c0{lead ? cin : nullptr, cstride, 0}, none{nullptr, 0, 0};
+            k_fma<<<ew_grid(n, nl, cnt), EW_THREADS, 0, stream_>>>(c1, s, c0, none, nullptr, 0, out, poly, 0, g, d_limb_, nl);
+            MK_HIP(hipGetLastError());
+            ntt_launch(out, cnt, nl, nl, true, nullptr, nullptr);
+            k_lift<int64_t><<<ew_grid(n, nl, cnt), EW_THREADS, 0, stream_>>>(eb, ws, g, d_limb_, nl);
+            k_add<<<ew_grid(n, nl, cnt), EW_THREADS, 0, stream_>>>(out, ws, out, g, d_limb_, nl);
+            MK_HIP(hipGetLastError());
+        }
+    }
+}
+
+void Engine::fuse_shares(const u64 *shares, u64 *m, uint32_t n_parties, uint32_t n_ct, uint32_t nl) {
+    need_device();
+    check_nl(nl);
+    if (!n_parties) throw std::invalid_argument("need n_parties >= 1");
+    if (!n_ct) return;
+    EwGeom g{ps_.n, nl, ps_.L};
+    // every thread reads its words of all shares before it writes them: m may be shares[0]
+    k_sum<<<ew_grid(ps_.n, nl, n_ct), EW_THREADS, 0, stream_>>>(shares, m, g, d_limb_, nl, n_parties, (size_t)n_ct * nl * ps_.n);
+    MK_HIP(hipGetLastError());
+}
+
 // ---- randomness ------------------------------------------------------------------------------------
 
 static ChaChaKey load_key(const uint8_t *key32) {

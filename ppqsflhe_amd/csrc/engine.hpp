@@ -142,6 +142,14 @@ public:
     // when nl_in == nl
     void rerandomize(const u64 *ct, const u64 *pk, const int8_t *v, const int64_t *e0, const int64_t *e1, u64 *out,
                      uint32_t n_ct, uint32_t nl_in, uint32_t nl);
+    // threshold decryption.  keygen_join: pk = (pk_prev[0] + e - pk_prev[1] * s, pk_prev[1]), sk as keygen.
+    // partial_decrypt: share[t] = INTT(c1 * sk (+ c0 when lead)) + e[t] on the first nl limbs of ct u64[n_ct][2][nl_in][N];
+    // e int64[n_ct][N] (|e| < 2^62); share u64[n_ct][nl][N], COEFFICIENT, canonical.  fuse_shares: m = sum over
+    // shares u64[n_parties][n_ct][nl][N]; m may be shares[0]
+    void keygen_join(const u64 *pk_prev, const int8_t *s, const int32_t *e, u64 *pk, u64 *sk);
+    void partial_decrypt(const u64 *ct, const u64 *sk, const int64_t *e, u64 *share, uint32_t n_ct, uint32_t nl_in,
+                         uint32_t nl, bool lead);
+    void fuse_shares(const u64 *shares, u64 *m, uint32_t n_parties, uint32_t n_ct, uint32_t nl);
     void lift_ntt(const double *coef, u64 *out, uint32_t n, uint32_t nl);
     void decrypt(const u64 *ct, const u64 *sk, u64 *m, uint32_t n_ct, uint32_t nl);
     // counter-based samplers (ChaCha20 block function under a 256-bit key): element i of stream sid is a pure

@@ -2328,4 +2328,119 @@ __global__ __launch_bounds__(NTT_THREADS) void k_rerand_row(RerandArgs a, NttTab
     }
 }
 
+// =====================================================================================
+// Partial (threshold) decryption (mkckks_partial_decrypt_batch; Engine::partial_decrypt):
+//   share = INTT(c1 * s (+ c0 on the lead share)) + (e mod q)   per limb, COEFFICIENT format, canonical.
+// The mirror image of k_lift_col / k_rerand_row: the product is formed in the loads of the first inverse pass and the
+// smudging error is reduced and added in the stores of the last one; c1 * s exists in HBM only as the row pass's output.
+// =====================================================================================
+
+struct PdecArgs {
+    const u64 *ct;     // [items][2][nl_in][N], first nl limbs read
+    const u64 *sk;     // [D][N], addressed by limb id
+    const int64_t *e;  // [items][N], |e| < 2^62
+    u64 *out;          // [items][nl][N]: written by the row pass (lazy, doubles on an fp limb), finished in place by the column pass
+    uint32_t nl_in, nl, lead;
+    unsigned long long slot_mask;  // Q limbs (slot == limb id) of this instance's arithmetic class
+    uint32_t nsel;
+};
+
+// Inverse row pass (the INV branch of k_ntt_row_r) whose copy-in computes c1 * s (+ c0): products as k_fma (mul_mod on
+// canonical words, every arithmetic class).  Grid order of k_ntt_row_r: the ciphertexts of one (limb, tile) are
+// neighbours in one XCD's queue, so the secret-key tile and the twiddle tile are fetched once and then hit in L2.
+template <int LOG_H, int AR>
+__global__ __launch_bounds__(NTT_THREADS) void k_pdec_row(PdecArgs a, NttTables T) {
+    using TL = RowTile<LOG_H>;
+    using TA = RowTwA<LOG_H>;
+    constexpr int H = TL::H, S = TL::S, R = TL::R, PAIRS = S * R / 2 / NTT_THREADS;
+    __shared__ u64 lds[TL::WORDS + 2 * TA::WORDS];
+    u64 *twa = lds + TL::WORDS, *twa_sh = twa + TA::WORDS;
+    const uint32_t n = 1u << T.log_n, r1 = 1u << T.log_r1;
+    const uint32_t tiles = r1 / S, groups = tiles * a.nsel, items = gridDim.x / groups;
+    uint32_t grp, item;
+    group_member(blockIdx.x, groups, items, T.cu_affine, grp, item);
+    const uint32_t sl = nth_set_bit(a.slot_mask, grp / tiles);  // Q limb: slot == limb id
+    const LimbConst lc = T.limb[sl];
+    if ((lc.fp != 0) != (AR == AR_FP)) return;  // block-uniform
+    const uint32_t row0 = (grp % tiles) * S;
+    const int g = threadIdx.x / H, j = threadIdx.x % H;
+    const size_t tile = (size_t)sl * n + (size_t)row0 * R;
+    const ulong2 *c0 = reinterpret_cast<const ulong2 *>(a.ct + (size_t)item * 2 * a.nl_in * n + tile);
+    const ulong2 *c1 = reinterpret_cast<const ulong2 *>(a.ct + ((size_t)item * 2 + 1) * a.nl_in * n + tile);
+    const ulong2 *sk = reinterpret_cast<const ulong2 *>(a.sk + tile);
+    u64 *dst = a.out + (size_t)item * a.nl * n + tile;
+    u64 x[H], w[H - 1], wp[H - 1];
+    load_rowb_twiddles<LOG_H>(T.itwb + (size_t)sl * 2 * n, row0 + g, j, w, wp);  // first: in flight while the tile is staged
+    for (int i = 0; i < PAIRS; ++i) {
+        const int e = wave_pair<LOG_H>(i);
+        const int gg = (2 * e) / R, xx = (2 * e) % R;
+        const ulong2 c = ld_pass2(c1 + e), s = sk[e];
+        ulong2 v{mul_mod(c.x, s.x, lc), mul_mod(c.y, s.y, lc)};
+        if (a.lead) {
+            const ulong2 b = ld_pass2(c0 + e);
+            v.x = add_mod(v.x, b.x, lc.q);
+            v.y = add_mod(v.y, b.y, lc.q);
+        }
+        lds[TL::at(gg, xx)] = v.x;
+        lds[TL::at(gg, xx + 1)] = v.y;
+    }
+    stage_twiddles_wave<LOG_H>(twa, twa_sh, T.itw + (size_t)sl * n, T.itw_sh + (size_t)sl * n, r1 + row0);
+    wave_lds_sync();
+#pragma unroll
+    for (int k = 0; k < H; ++k) x[k] = lds[TL::at(g, H * j + k)];
+    if (AR == AR_FP) {  // canonical input -> doubles
+#pragma unroll
+        for (int k = 0; k < H; ++k) x[k] = dbits((double)x[k]);
+    }
+    radix_inverse_any<LOG_H, AR>(x, w, wp, lc);
+#pragma unroll
+    for (int k = 0; k < H; ++k) lds[TL::at(g, H * j + k)] = x[k];
+    wave_lds_sync();
+#pragma unroll
+    for (int k = 0; k < H; ++k) x[k] = lds[TL::at(g, j + H * k)];
+    TA::fetch(twa, twa_sh, g, w, wp);
+    radix_inverse_any<LOG_H, AR>(x, w, wp, lc);
+#pragma unroll
+    for (int k = 0; k < H; ++k) st_pass(dst + (size_t)g * R + j + H * k, x[k]);  // lazy (doubles on an fp limb): the column pass scales
+}
+
+// Inverse column pass (the INV branch of k_ntt_col_r, N^-1 scaling, canonical output), in place on PdecArgs::out, whose
+// stores add the smudging error: e is reduced by the limb's modulus in exact integer arithmetic (lift_signed, also on an
+// fp64-class limb: 62 bits do not fit 53) and added to the canonical coefficient.  The 8 N error bytes of a ciphertext
+// feed all of its limbs.  Grid (column tile, nsel, item).
+template <int LOG_H, int AR>
+__global__ __launch_bounds__(NTT_THREADS, 4) void k_pdec_col(PdecArgs a, NttTables T) {
+    using TL = ColTile<LOG_H>;
+    constexpr int H = TL::H, S = TL::S;
+    __shared__ u64 lds[TL::WORDS + ColTwB<LOG_H>::WORDS];
+    const uint32_t n = 1u << T.log_n, r2 = 1u << T.log_r2;
+    const uint32_t sl = nth_set_bit(a.slot_mask, blockIdx.y), item = blockIdx.z;
+    const LimbConst lc = T.limb[sl];
+    if ((lc.fp != 0) != (AR == AR_FP)) return;  // never: the host selects the limbs of this instance's class
+    const int c = threadIdx.x % S, j = threadIdx.x / S;
+    u64 *p = a.out + ((size_t)item * a.nl + sl) * n + blockIdx.x * S + c;
+    const int64_t *err = a.e + (size_t)item * n + blockIdx.x * S + c;
+    u64 x[H];
+    ColTwB<LOG_H>::stage(lds + TL::WORDS, T.itw + (size_t)sl * n, T.itw_sh + (size_t)sl * n);
+#pragma unroll
+    for (int k = 0; k < H; ++k) x[k] = ld_pass(p + (size_t)(H * j + k) * r2);  // from the row pass: doubles on an fp limb
+    wave_lds_sync();  // the strip is this wave's own
+    const u64 *strip = lds + TL::WORDS;
+    radix_inverse_staged<LOG_H, AR>(x, [&](int i) { return ColTwB<LOG_H>::pair_b(strip, j, i); }, lc);
+#pragma unroll
+    for (int k = 0; k < H; ++k) lds[TL::at(j, k, c)] = x[k];
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < H; ++k) x[k] = lds[TL::at(k, j, c)];
+    radix_inverse_staged<LOG_H, AR>(x, [&](int i) { return ColTwB<LOG_H>::pair_a(strip, i); }, lc);
+    const u64 sc = (AR == AR_FP) ? dbits(lc.ninv_d) : lc.ninv, sc_sh = (AR == AR_FP) ? dbits(lc.ninv_qd) : lc.ninv_sh;
+#pragma unroll
+    for (int k = 0; k < H; ++k) {
+        const u64 v = (AR == AR_FP) ? fp_to_canonical(fp_mulmod(bitsd(x[k]), bitsd(sc), bitsd(sc_sh), lc.qd), lc.qd, lc.qinv)
+                                    : shoup_mul(x[k], sc, sc_sh, lc.q);
+        const u64 ev = lift_signed(err[(size_t)(j + H * k) * r2], lc);
+        st_pass(p + (size_t)(j + H * k) * r2, add_mod(v, ev, lc.q));
+    }
+}
+
 }  // namespace mk
