@@ -70,7 +70,15 @@ const char *mkckks_version(void);
  * replaces GenCryptoContext(params)+Enable(...) (server/src/genCC.cpp:68-76)
  * and Serial::DeserializeFromFile(cc) (server/src/changeCipherDomain.cpp:33,
  * aggregateEncryptedWeights.cpp:47 and the client mains): builds Q, P, roots,
- * twiddles and all CRT tables and keeps them resident in HBM. */
+ * twiddles and all CRT tables and keeps them resident in HBM.
+ * Accepted: log_n 8..17, mult_depth 1..30, 20 <= scaling_bits < first_bits <= 60,
+ * aux_bits 30..60, extra_bits 18..30, digit size alpha and #special primes K <= 8.
+ * Refused (-1) inside that range: parameters whose moduli are not pairwise
+ * distinct -- the extra limb (first prime = 1 mod 2N above 2^(extra_bits-1)) is
+ * placed without regard to the scaling limbs and coincides with one whenever
+ * extra_bits = scaling_bits + 1, and where such primes are sparse (seen at log_n >= 15
+ * with scaling_bits 20..22 and extra_bits <= 20, e.g. log_n 16, 20, 20); such
+ * a basis has no CRT and cannot be rescaled. */
 int mkckks_ctx_create(const mkckks_params *p, mkckks_ctx **out);
 int mkckks_ctx_destroy(mkckks_ctx *c);
 int mkckks_ctx_info(const mkckks_ctx *c, mkckks_info *out);

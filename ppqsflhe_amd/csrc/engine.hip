@@ -1625,7 +1625,13 @@ bool Engine::keyswitch_digits(const u64 *c1, size_t ct_stride, const u64 *evk, u
     unsigned long long fp_mask = 0, all_mask = ext >= 64 ? ~0ull : ((1ull << ext) - 1);
     for (uint32_t i = 0; i < nl; ++i)
         if (tabs_.h_fp_of[i]) fp_mask |= 1ull << i;
-    const bool fuse = fp_mask != 0 && (row_h == 3 || row_h == 4 || row_h == 9) &&
+    // fp64-class P limbs (aux_bits <= 50) are in neither fused kernel: k_row_inner_fp covers the Q slots of fp_mask only
+    // and the integer kernels cannot read their tables, so such a context takes the full row pass + k_inner_product_b
+    // (the condition of qsum_ok and fanout_fused)
+    bool p_fp = false;
+    for (uint32_t k = 0; k < ps_.K; ++k)
+        if (tabs_.h_fp_of[ps_.L + k]) p_fp = true;
+    const bool fuse = fp_mask != 0 && !p_fp && (row_h == 3 || row_h == 4 || row_h == 9) &&
                       fast_log_h(tabs_.log_r1, 1u << tabs_.log_r2) != 0;
     const bool fuse_int = fuse && (row_h == 4 || row_h == 9);  // +1.3 % at C3
     {

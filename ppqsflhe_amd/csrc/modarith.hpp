@@ -277,7 +277,9 @@ MK_HD void mac_cols(Cols &c, uint32_t a0, uint32_t a1, uint32_t b0, uint32_t b1)
 // the three columns (under-estimate by <= 2), so qhat in {Q-3..Q} and the remainder is below 4q.
 MK_HD u64 reduce_cols_lazy(const Cols &c, const LimbConst &L) {  // result in [0, 4q)
     const u64 lo = c.c0 + (c.c1 << 30) + (c.c2 << 60);
-    const int e1 = 30 - (int)L.sh;  // sh in [18,58]
+    // sh in [16,58] (q of 18..60 bits).  For sh <= 30 only c0 is floored; a q below 2^30 has b1 = 0, so c2 = 0 and
+    // c1 < 4 * 2^30 * 2^k = 2^(sh+34), which the left shift by 30 - sh keeps below 2^64.
+    const int e1 = 30 - (int)L.sh;
     const u64 y = (c.c0 >> L.sh) + (e1 >= 0 ? (c.c1 << e1) : (c.c1 >> (-e1))) + (c.c2 << (60 - L.sh));
     const u64 qh = mulhi64(y, L.mu);
     return lo - qh * L.q;

@@ -193,6 +193,13 @@ void ParamSet::generate(uint32_t log_n_, uint32_t depth, uint32_t sbits, uint32_
         moduli.push_back(cursor);
     }
     if (alpha > 8 || K > 8) throw std::invalid_argument("digit size / #special primes above 8 unsupported");
+    // The chain avoids repeats within itself and P avoids Q, but the extra limb (first prime above 2^(ebits-1)) and q_0
+    // are placed on their own: with ebits = sbits + 1, or where primes = 1 mod 2N are sparse (N = 2^16, 20-bit scaling),
+    // the extra limb lands on a scaling limb.  Such a basis has no CRT (q_l^-1 mod q_i does not exist: no rescale), so it is refused here.
+    for (uint32_t i = 0; i < D; ++i)
+        if (contains(moduli, 0, i, moduli[i]))
+            throw std::invalid_argument("moduli are not pairwise distinct: too few primes = 1 mod 2N of these widths (raise "
+                                        "scaling_bits or extra_bits, or lower log_n)");
 
     roots.resize(D);
     limb.resize(D);

@@ -4,11 +4,12 @@
 #include <cstdio>
 #include <cstdlib>
 #include <stdexcept>
+#include <string>
 
 #include "params.hpp"
 
 int main() {
-    struct Cfg { uint32_t log_n, depth, sbits, first, dnum; };
+    struct Cfg { uint32_t log_n, depth, sbits, first, dnum, aux = 60, extra = 20; };
     const Cfg cfgs[] = {{10, 3, 40, 60, 2}, {12, 1, 40, 60, 2}, {14, 2, 40, 60, 2}, {12, 18, 50, 60, 3}, {16, 10, 50, 60, 3}};
     try {
         for (const Cfg &c : cfgs) {
@@ -35,22 +36,29 @@ int main() {
             std::printf("ok log_n=%u L=%u K=%u alpha=%u beta=%u checksum=%llu\n", ps.log_n, ps.L, ps.K, ps.alpha, ps.beta, sum);
         }
         // pseudo-Mersenne arithmetic of modarith.hpp (host mirror of the device code): congruence and the stated output
-        // bounds on boundary and random operands, for every eligible prime the configurations above produce plus 55-
-        // and 58-bit first moduli
+        // bounds on boundary and random operands, for every eligible prime the configurations above produce plus first
+        // moduli of every width from 51 to 59 bits and special primes of 55 bits (the shifts of pm_fold, pm_lazy and
+        // pm_reduce128 depend on the width k).  Every width a configuration asks for must turn up among the primes checked.
         {
             using mk::u64;
             typedef unsigned __int128 u128;
             unsigned long long checked = 0;
             u64 rng = 0x9E3779B97F4A7C15ull;
             auto next = [&]() { rng ^= rng << 13; rng ^= rng >> 7; rng ^= rng << 17; return rng; };
+            u64 widths_wanted = 0, widths_seen = 0;  // bit k: an integer limb of k bits was asked for / was checked
             for (const Cfg &c : {Cfg{14, 2, 40, 60, 2}, Cfg{16, 10, 50, 60, 3}, Cfg{14, 2, 40, 55, 2}, Cfg{14, 2, 40, 58, 2},
-                                 Cfg{17, 19, 50, 60, 3}}) {
+                                 Cfg{17, 19, 50, 60, 3}, Cfg{12, 2, 40, 52, 2}, Cfg{12, 2, 40, 60, 2, 55}, Cfg{12, 2, 40, 51, 2},
+                                 Cfg{12, 2, 40, 53, 2}, Cfg{12, 2, 40, 54, 2}, Cfg{12, 2, 40, 56, 2}, Cfg{12, 2, 40, 57, 2},
+                                 Cfg{12, 2, 40, 59, 2}}) {
                 mk::ParamSet ps;
-                ps.generate(c.log_n, c.depth, c.sbits, c.first, c.dnum, 60, 20);
+                ps.generate(c.log_n, c.depth, c.sbits, c.first, c.dnum, c.aux, c.extra);
+                for (uint32_t bits : {c.first, c.aux})
+                    if (bits >= 51) widths_wanted |= (u64)1 << bits;
                 for (uint32_t i = 0; i < ps.D; ++i) {
                     const u64 q = ps.moduli[i];
                     if (q < (5ull << 48) || !mk::pm_eligible(q)) continue;
                     mk::LimbConst lc = ps.limb[i];
+                    widths_seen |= (u64)1 << lc.k;
                     lc.pm = 1;
                     lc.pm_c = (uint32_t)(((u64)1 << lc.k) - q);
                     const mk::PmK P = mk::pm_consts(lc);
@@ -108,7 +116,107 @@ int main() {
                 }
             }
             if (!checked) throw std::runtime_error("no pseudo-Mersenne prime was exercised");
+            for (uint32_t k = 51; k <= 60; ++k)
+                if ((widths_wanted >> k & 1) && !(widths_seen >> k & 1))
+                    throw std::runtime_error("no eligible pseudo-Mersenne prime of " + std::to_string(k) + " bits");
             std::printf("ok pseudo-Mersenne arithmetic (%llu products)\n", checked);
+        }
+        // Barrett / Shoup arithmetic of modarith.hpp (what every limb outside the fp64 and pseudo-Mersenne classes runs, and
+        // every base conversion): exact against unsigned __int128 at the ends of the stated operand ranges, for every
+        // modulus of the contexts of tests/test_parameter_lattice.py -- 18 to 60 bits wide
+        {
+            using mk::u64;
+            typedef unsigned __int128 u128;
+            unsigned long long checked = 0, moduli = 0;
+            u64 rng = 0xD1B54A32D192ED03ull;
+            auto next = [&]() { rng ^= rng << 13; rng ^= rng >> 7; rng ^= rng << 17; return rng; };
+            auto fail = [](const char *what, u64 q) {
+                throw std::runtime_error(std::string(what) + " at q = " + std::to_string(q));
+            };
+            u64 widths = 0;
+            for (const Cfg &c : {Cfg{12, 2, 51, 60, 2}, Cfg{12, 2, 54, 60, 2}, Cfg{12, 2, 59, 60, 2}, Cfg{14, 3, 55, 60, 2},
+                                 Cfg{16, 2, 56, 60, 3}, Cfg{12, 3, 30, 60, 2}, Cfg{16, 2, 21, 60, 2}, Cfg{17, 2, 24, 60, 2},
+                                 Cfg{12, 2, 24, 40, 2}, Cfg{12, 2, 40, 45, 2}, Cfg{12, 2, 40, 52, 2}, Cfg{12, 2, 40, 60, 2, 45},
+                                 Cfg{12, 2, 40, 60, 2, 55}, Cfg{12, 2, 40, 60, 2, 30, 18}, Cfg{12, 2, 40, 60, 2, 60, 30},
+                                 Cfg{12, 6, 40, 60, 1}, Cfg{12, 4, 40, 60, 6}, Cfg{12, 8, 40, 60, 2}, Cfg{12, 14, 40, 60, 2},
+                                 Cfg{12, 14, 40, 60, 2, 48}, Cfg{8, 3, 50, 60, 2}, Cfg{13, 2, 50, 60, 2}, Cfg{15, 2, 50, 60, 3}}) {
+                mk::ParamSet ps;
+                ps.generate(c.log_n, c.depth, c.sbits, c.first, c.dnum, c.aux, c.extra);
+                for (uint32_t i = 0; i < ps.D; ++i) {
+                    const mk::LimbConst &lc = ps.limb[i];
+                    const u64 q = lc.q;
+                    widths |= (u64)1 << lc.k;
+                    ++moduli;
+                    // mul_mod: a, b < q
+                    const u64 ends[] = {0, 1, q - 1};
+                    for (u64 a : ends)
+                        for (u64 b : ends)
+                            if (mk::mul_mod(a, b, lc) != (u64)((u128)a * b % q)) fail("mul_mod", q);
+                    for (int it = 0; it < 2000; ++it) {
+                        const u64 a = next() % q, b = next() % q;
+                        if (mk::mul_mod(a, b, lc) != (u64)((u128)a * b % q)) fail("mul_mod", q);
+                    }
+                    // barrett_reduce128: x < 2^(k + 62), at the largest such x and below it
+                    const u128 top = ((u128)1 << (lc.k + 62)) - 1;
+                    for (int it = 0; it < 2000; ++it) {
+                        const u128 x = it == 0 ? top : it == 1 ? top - q : (((u128)next() << 64) | next()) & top;
+                        if (mk::barrett_reduce128((u64)(x >> 64), (u64)x, lc) != (u64)(x % q)) fail("barrett_reduce128", q);
+                    }
+                    // reduce_word: any 64-bit word
+                    for (u64 x : {(u64)0, q, q - 1, 2 * q, ~(u64)0, ~(u64)0 - q})
+                        if (mk::reduce_word(x, lc) != x % q) fail("reduce_word", q);
+                    for (int it = 0; it < 2000; ++it) {
+                        const u64 x = next();
+                        if (mk::reduce_word(x, lc) != x % q) fail("reduce_word", q);
+                    }
+                    // reduce_wide: accumulators below 2^124
+                    const u128 wide = ((u128)1 << 124) - 1;
+                    for (int it = 0; it < 2000; ++it) {
+                        const u128 x = it == 0 ? wide : it == 1 ? wide - q : it == 2 ? (wide >> 64) << 64
+                                                                          : (((u128)next() << 64) | next()) & wide;
+                        if (mk::reduce_wide((u64)(x >> 64), (u64)x, lc) != (u64)(x % q)) fail("reduce_wide", q);
+                    }
+                    // reduce_cols / reduce_cols_lazy: 1..4 products a b, a < 2^60, b < q; reduce_cols4: 5..8 of them.
+                    // Round 0 of every term count: every product (2^60 - 1) (q - 1)
+                    for (int it = 0; it < 4000; ++it) {
+                        const int terms = 1 + it % 8;
+                        mk::Cols cs{0, 0, 0};
+                        mk::Cols4 c4{0, 0, 0, 0};
+                        u128 X = 0;
+                        for (int t = 0; t < terms; ++t) {
+                            const u64 a = (it < 8 || it % 5 == 0) ? (1ull << 60) - 1 : next() >> 4;
+                            const u64 b = (it < 8 || it % 3 == 0) ? q - 1 : next() % q;
+                            uint32_t a0, a1, b0, b1;
+                            mk::split30(a, a0, a1);
+                            mk::split30(b, b0, b1);
+                            if (terms <= 4) mk::mac_cols(cs, a0, a1, b0, b1);
+                            else mk::mac_cols4(c4, a0, a1, b0, b1);
+                            X += (u128)a * b;
+                        }
+                        if (terms <= 4) {
+                            const u64 lazy = mk::reduce_cols_lazy(cs, lc);
+                            if (lazy >= 4 * q || lazy % q != (u64)(X % q)) fail("reduce_cols_lazy", q);
+                            if (mk::reduce_cols(cs, lc) != (u64)(X % q)) fail("reduce_cols", q);
+                        } else if (mk::reduce_cols4(c4, lc) != (u64)(X % q)) fail("reduce_cols4", q);
+                    }
+                    // shoup_lazy: any 64-bit a, result below 2q
+                    const u64 as[] = {0, q - 1, 2 * q - 1, 4 * q - 1, ~(u64)0};
+                    for (int it = 0; it < 2000; ++it) {
+                        const u64 w = it == 0 ? 0 : it == 1 ? 1 : it == 2 ? q - 1 : next() % q, wp = mk::h_shoup(w, q);
+                        for (u64 a : as) {
+                            const u64 r = mk::shoup_lazy(a, w, wp, q);
+                            if (r >= 2 * q || r % q != (u64)((u128)a * w % q)) fail("shoup_lazy", q);
+                        }
+                        const u64 a = next(), r = mk::shoup_lazy(a, w, wp, q);
+                        if (r >= 2 * q || r % q != (u64)((u128)a * w % q)) fail("shoup_lazy", q);
+                        if (mk::shoup_mul(a, w, wp, q) != (u64)((u128)a * w % q)) fail("shoup_mul", q);
+                    }
+                    checked += 2009 + 2000 + 2006 + 2000 + 4000 + 2000 * 7;
+                }
+            }
+            for (uint32_t k : {18u, 20u, 30u, 45u, 52u, 55u, 60u})
+                if (!(widths >> k & 1)) throw std::runtime_error("no modulus of " + std::to_string(k) + " bits");
+            std::printf("ok Barrett arithmetic (%llu moduli, %llu checks)\n", moduli, checked);
         }
         mk::ParamSet bad;
         try {

@@ -44,7 +44,10 @@ def test_params_under_asan_ubsan():
     assert r.returncode == 0, r.stdout + r.stderr
     assert r.stdout.count("ok log_n=") == 5 and "invalid parameters are refused" in r.stdout
     # the butterflies' pseudo-Mersenne products and folds (modarith.hpp is host + device code): residues and range bounds
+    # (first moduli of 51..59 bits and 55-bit special primes included: a width without an eligible prime is an error)
     assert "ok pseudo-Mersenne arithmetic" in r.stdout
+    # the Barrett / Shoup family against unsigned __int128, for every modulus of tests/test_parameter_lattice.py's contexts
+    assert "ok Barrett arithmetic" in r.stdout
 
 
 def test_host_parsers_on_wellformed_inputs(selftest, tmp_path, golden_dir):
