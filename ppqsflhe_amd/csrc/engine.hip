@@ -309,10 +309,10 @@ __global__ void k_inner_product_b(const u64 *digits, const u64 *c1, size_t c1_st
         for (int j = 0; j < NPARTS; ++j) {
             const ulong2 d = (j == own) ? ld2(c1 + (size_t)item * c1_stride + (size_t)slot * g.n + idx)
                                         : ld2(digits + (((size_t)item * NPARTS + j) * ext + slot) * g.n + idx);
-            mac128(h0x, l0x, d.x, b[j].x);
-            mac128(h0y, l0y, d.y, b[j].y);
-            mac128(h1x, l1x, d.x, a[j].x);
-            mac128(h1y, l1y, d.y, a[j].y);
+            mac128_split(h0x, l0x, d.x, b[j].x);
+            mac128_split(h0y, l0y, d.y, b[j].y);
+            mac128_split(h1x, l1x, d.x, a[j].x);
+            mac128_split(h1y, l1y, d.y, a[j].y);
         }
         ulong2 r0, r1;
         if (NPARTS <= 4) {

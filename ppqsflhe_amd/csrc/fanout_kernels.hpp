@@ -253,10 +253,10 @@ __global__ __launch_bounds__(NTT_THREADS, fan_waves<LOGC>(NPARTS + (INVP ? 1 : 0
             for (int i = 0; i < PAIRS; ++i) {
                 const int xx = (2 * row3_pair<LOGC>(c.g, c.t, i)) % R;
                 const u64 yx = tile[TL::at(c.g, xx)], yz = tile[TL::at(c.g, xx + 1)];
-                mac128(h0[2 * i], l0[2 * i], yx, eb[i].x);
-                mac128(h0[2 * i + 1], l0[2 * i + 1], yz, eb[i].y);
-                mac128(h1[2 * i], l1[2 * i], yx, ec[i].x);
-                mac128(h1[2 * i + 1], l1[2 * i + 1], yz, ec[i].y);
+                mac128_split(h0[2 * i], l0[2 * i], yx, eb[i].x);
+                mac128_split(h0[2 * i + 1], l0[2 * i + 1], yz, eb[i].y);
+                mac128_split(h1[2 * i], l1[2 * i], yx, ec[i].x);
+                mac128_split(h1[2 * i + 1], l1[2 * i + 1], yz, ec[i].y);
             }
             if (more) {
 #pragma unroll

@@ -136,6 +136,14 @@ MK_HD PmK pm_consts(const LimbConst &L) {
 // table entries of a pseudo-Mersenne limb for the twiddle w (host side)
 MK_HD u64 pm_tw(u64 w, const LimbConst &L) { return w << (63 - L.k); }
 inline u64 pm_tw_companion(u64 w, const LimbConst &L) { return (u64)(((u128)w << 32) % L.q) << (63 - L.k); }
+// the value as it is, but opaque to the device optimiser: a sum written as "multiply-add onto this addend" stays one
+// v_mad_u64_u32 (left alone, the compiler re-associates a*b + c + d and a*b + (hi:lo) into extra moves and 64-bit adds)
+MK_HD u64 pinned(u64 x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm("" : "+v"(x));
+#endif
+    return x;
+}
 // x (any 64-bit word) -> x mod q in [0, U + 2^30):  (x mod 2^k) + (x >> k) c, and (x >> k) c < 2^(64-k) 2^(k-34).
 MK_HD u64 pm_fold(u64 x, const PmK &P) {
     const uint32_t xh = (uint32_t)(x >> 32);
@@ -158,28 +166,101 @@ MK_HD u64 hi32_pair(u64 y) {
 //   lo = S mod 2^(k+1) = (S' mod 2^64) >> t,  and 2^(k+1) = 2c (mod q)  ->  lo + hi 2c < 2U + 0.375U.
 // Result in [0, 2.375U).  No partial sum wraps: a_lo wt_lo < 2^64; a_lo wt_hi + 2^32 < 2^64 (wt < 2^63); a_hi < 2^31 keeps
 // a_hi wxt_lo + 2^32 below 2^64; z ends as floor(S' / 2^32) < 1.5 * 2^63.
+// The two low partial products are summed whole, L = a_lo wt_lo + a_hi wxt_lo < 1.5 * 2^64, and the bit that falls off
+// the 64-bit sum is the multiplier's own carry-out: H = a_lo wt_hi + a_hi wxt_hi + (L mod 2^64 >> 32) stays below 2^64
+// and the carry belongs to bit 32 of H, i.e. it is added to H's high word (hi < 1.5 * 2^31 keeps that in 32 bits).
+// Splitting L into words first (the earlier form) took two more pair constructions and a 64-bit add per product.
+#if defined(__HIP_DEVICE_COMPILE__)
+// The device forms below keep each run of dependent instructions in ONE asm statement: the compiler pads every asm
+// statement with a wait state before the first use of its outputs (it cannot see what is inside), so a statement per
+// instruction costs an s_nop per instruction.  Carries travel as lane masks in scalar pairs (v_mad_u64_u32's sdst, which
+// the compiler itself never uses); multiplies and adds whose carry-out is of no use write it to vcc (clobbered).
+// gfx950 wants two wait states between a vector instruction that WRITES a scalar register and a vector instruction that
+// READS it, and nothing pads the inside of a string: every carry below is consumed at least two instructions after it is
+// produced (pair, multiply, ... in between), except mac128's last add, which carries its own s_nop.
+// tools/sgpr_hazard_scan.py checks an assembly listing (make asm) for this rule.
+//
+// l = a1 * bx + l (carry-out cy: bit 64 of the sum),  h = a0 * bt + (l >> 32)
+MK_D void mad_cy_then_high(u64 &l, u64 &h, u64 &cy, uint32_t a1, uint32_t bx, uint32_t a0, uint32_t bt) {
+    asm("v_mad_u64_u32 %0, %2, %3, %4, %0\n\t"
+        "v_lshrrev_b64 %1, 32, %0\n\t"
+        "v_mad_u64_u32 %1, vcc, %5, %6, %1"
+        : "+&v"(l), "=&v"(h), "=&s"(cy)
+        : "v"(a1), "v"(bx), "v"(a0), "v"(bt)
+        : "vcc");
+}
+// the same with one wave-uniform multiplier u for both products (a constant of PmK, taken from a scalar register)
+MK_D void mad_cy_then_high_u(u64 &l, u64 &h, u64 &cy, uint32_t a1, uint32_t a0, uint32_t u) {
+    asm("v_mad_u64_u32 %0, %2, %3, %5, %0\n\t"
+        "v_lshrrev_b64 %1, 32, %0\n\t"
+        "v_mad_u64_u32 %1, vcc, %4, %5, %1"
+        : "+&v"(l), "=&v"(h), "=&s"(cy)
+        : "v"(a1), "v"(a0), "s"(u)
+        : "vcc");
+}
+// (x + (cy ? 1 : 0)) * u + addend, x + 1 < 2^32, u wave-uniform
+MK_D u64 addc_then_mad(uint32_t x, u64 cy, uint32_t u, u64 addend) {
+    u64 r;
+    uint32_t t;
+    asm("v_addc_co_u32 %1, vcc, 0, %2, %3\n\t"
+        "v_mad_u64_u32 %0, vcc, %1, %4, %5"
+        : "=v"(r), "=&v"(t)
+        : "v"(x), "s"(cy), "s"(u), "v"(addend)
+        : "vcc");
+    return r;
+}
+#endif
 MK_HD u64 pm_lazy(u64 a, u64 wt, u64 wxt, const PmK &P) {
     const uint32_t a0 = (uint32_t)a, a1 = (uint32_t)(a >> 32);
     const u64 y0 = (u64)a0 * (uint32_t)wt;
-    u64 z = (u64)a0 * (uint32_t)(wt >> 32) + hi32_pair(y0);
-    const u64 y1 = (u64)a1 * (uint32_t)wxt + (u64)(uint32_t)y0;
-    z = (u64)a1 * (uint32_t)(wxt >> 32) + z;
-    z += hi32_pair(y1);
-    const u64 lo = (((u64)(uint32_t)z << 32) | (uint32_t)y1) >> P.t;
-    return (u64)(uint32_t)(z >> 32) * P.c2 + lo;
+#if defined(__HIP_DEVICE_COMPILE__)
+    u64 l = y0, h, cy;
+    mad_cy_then_high(l, h, cy, a1, (uint32_t)wxt, a0, (uint32_t)(wt >> 32));
+    h = (u64)a1 * (uint32_t)(wxt >> 32) + h;
+    // ((low word of h) : (low word of l)) >> t, written as its two words (t < 32) straight into the last addend's pair
+    const uint32_t lo0 = __builtin_amdgcn_alignbit((uint32_t)h, (uint32_t)l, P.t);
+    const uint32_t lo1 = (uint32_t)h >> P.t;
+    return addc_then_mad((uint32_t)(h >> 32), cy, P.c2, ((u64)lo1 << 32) | lo0);
+#else
+    const u64 l = (u64)a1 * (uint32_t)wxt + y0;  // mod 2^64
+    const uint32_t cy = l < y0 ? 1u : 0u;
+    u64 h = (u64)a0 * (uint32_t)(wt >> 32) + (l >> 32);
+    h = (u64)a1 * (uint32_t)(wxt >> 32) + h;
+    const uint32_t hh = (uint32_t)(h >> 32) + cy;
+    const u64 lo = (((u64)(uint32_t)h << 32) | (uint32_t)l) >> P.t;
+    return (u64)hh * P.c2 + lo;
+#endif
 }
 
 // X = hi:lo -> X mod q in [0, q), for X < 2^(2k+6) (a sum of up to 6 products of a lazy word < 8U and a residue): the high
 // word is folded with 2^64 = c64 (mod q) into Y = m1 2^32 + (low word of m0) < 2^(2k-28) + 2^64, Y is folded at bit k
 // (Y >> k < 2^32) into r < U + 2^32 c <= 1.25U, one conditional subtraction finishes.  11 instructions where Barrett's
 // quotient estimate (high product, low product, two corrections) takes about 25.
+// Device: the low word takes all of lo as its addend, M = hi_lo c64 + lo < 2^62 + 2^64 with the multiplier's carry-out,
+// so Y = (hi_hi c64 + (M >> 32)) 2^32 + (low word of M) -- the same Y, without splitting lo into two pairs first.
 MK_HD u64 pm_reduce128(u64 hi, u64 lo, const PmK &P, u64 q) {
-    const u64 m0 = (u64)(uint32_t)hi * P.c64 + (u64)(uint32_t)lo;
-    u64 m1 = (u64)(uint32_t)(hi >> 32) * P.c64 + hi32_pair(lo);
-    m1 += hi32_pair(m0);
-    const uint32_t yh = (uint32_t)(m1 >> P.s_f);
-    const u64 ylo = ((u64)((uint32_t)m1 & P.m_f) << 32) | (uint32_t)m0;
+#if defined(__HIP_DEVICE_COMPILE__)
+    u64 m = lo, n, cy;
+    mad_cy_then_high_u(m, n, cy, (uint32_t)hi, (uint32_t)(hi >> 32), P.c64);
+    const u64 ylo1 = ((u64)((uint32_t)n & P.m_f) << 32) | (uint32_t)m;
+    // nh = (Y >> 64) = high word of n + carry < 2^(2k-92) + 1,  yh = (nh : low word of n) >> (k - 32) = Y >> k < 2^32
+    u64 r;
+    uint32_t nh, yh1;
+    asm("v_addc_co_u32 %1, vcc, 0, %3, %5\n\t"
+        "v_alignbit_b32 %2, %1, %4, %6\n\t"
+        "v_mad_u64_u32 %0, vcc, %2, %7, %8"
+        : "=v"(r), "=&v"(nh), "=&v"(yh1)
+        : "v"((uint32_t)(n >> 32)), "v"((uint32_t)n), "s"(cy), "s"(P.s_f), "s"(P.c), "v"(ylo1)
+        : "vcc");
+    return csub(r, q);
+#else
+    const u64 m = (u64)(uint32_t)hi * P.c64 + lo;  // mod 2^64
+    const u64 cy = m < lo ? 1u : 0u;
+    const u64 n = (u64)(uint32_t)(hi >> 32) * P.c64 + (m >> 32) + (cy << 32);
+    const uint32_t yh = (uint32_t)(n >> P.s_f);
+    const u64 ylo = ((u64)((uint32_t)n & P.m_f) << 32) | (uint32_t)m;
     return csub((u64)yh * P.c + ylo, q);
+#endif
 }
 
 // Barrett reduction of a 128-bit x = hi:lo with x < 2^(k+62) (k = bitlen q) to [0,q).
@@ -297,7 +378,9 @@ MK_HD u64 pm_reduce_cols(const Cols &c, const PmK &P) {
     const u64 ylo = ((u64)((uint32_t)m1 & P.m_f) << 32) | (uint32_t)m0;
     const u64 a = c.c0 + ((c.c1 & 0x3FFFFFFFull) << 30);
     // (a wave-uniform "skip the fold when k = 60" costs 36 more registers in k_conv_col than the three instructions save)
-    return (u64)yh * P.c + ylo + pm_fold(a, P);
+    // The two folds are kept as two chained multiply-adds: written as one sum, the compiler merges them into
+    // (yh + ah) c with a 64-bit factor, i.e. two multiplies plus the word shuffling of a 64 x 32 product.
+    return (u64)yh * P.c + pinned(pm_fold(a, P)) + pinned(ylo);
 }
 MK_HD u64 reduce_cols(const Cols &c, const LimbConst &L) {
     return csub(csub(reduce_cols_lazy(c, L), L.q2), L.q);
@@ -329,12 +412,48 @@ MK_HD u64 reduce_cols4(const Cols4 &c, const LimbConst &L) {  // canonical
 MK_HD u64 pack30(u64 v) { return (v & 0x3FFFFFFFull) | ((v >> 30) << 32); }
 MK_HD u64 unpack30(u64 p) { return (p & 0xFFFFFFFFull) | ((p >> 32) << 30); }
 
-// 128-bit accumulate acc += a*b
-MK_HD void mac128(u64 &hi, u64 &lo, u64 a, u64 b) {
+// 128-bit accumulate acc += a*b, any a and b: the product as the compiler lowers it (a*b and __umul64hi apart).  More
+// instructions than mac128 below but fewer live registers; kept for the kernels that sit at a register or occupancy limit
+// (the fan-out inner product, k_inner_product_b), where mac128 costs scratch or a wave.
+MK_HD void mac128_split(u64 &hi, u64 &lo, u64 a, u64 b) {
     u64 ph, pl;
     mul128(a, b, ph, pl);
     lo += pl;
     hi += ph + (lo < pl ? 1 : 0);
+}
+// 128-bit accumulate acc += a*b for a < 2^63 (a lazy word), b < 2^60 (a residue) and a sum that stays below 2^128.
+// Device: the four-multiply schoolbook with the carries chained into the accumulator,
+//   r0 = a_lo b_lo + lo (carry c0 = bit 64 of the sum),  r2 = a_hi b_lo + (a_lo b_hi + (r0 >> 32)) < 2^64 (a_hi < 2^31),
+//   lo' = (low word of r2) : (low word of r0),  hi' = a_hi b_hi + hi + (r2 >> 32) + c0,
+// instead of a*b and __umul64hi(a, b), which the compiler lowers apart (2 v_mul_lo_u32 + 5 v_mad_u64_u32 + 64-bit adds).
+MK_HD void mac128(u64 &hi, u64 &lo, u64 a, u64 b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const uint32_t a0 = (uint32_t)a, a1 = (uint32_t)(a >> 32), b0 = (uint32_t)b, b1 = (uint32_t)(b >> 32);
+    u64 r0 = lo, r2, c0;
+    asm("v_mad_u64_u32 %0, %2, %3, %4, %0\n\t"
+        "v_lshrrev_b64 %1, 32, %0\n\t"
+        "v_mad_u64_u32 %1, vcc, %3, %5, %1\n\t"
+        "v_mad_u64_u32 %1, vcc, %6, %4, %1"
+        : "+&v"(r0), "=&v"(r2), "=&s"(c0)
+        : "v"(a0), "v"(b0), "v"(b1), "v"(a1)
+        : "vcc");
+    const u64 r3 = (u64)a1 * b1 + hi;
+    // hi' = r3 + (r2 >> 32) + c0: the low words take c0 as their carry-in, the high word their carry-out, which the
+    // first add has only just written: the two wait states are in the string
+    uint32_t h0, h1;
+    asm("v_addc_co_u32 %0, vcc, %2, %3, %4\n\t"
+        "s_nop 1\n\t"
+        "v_addc_co_u32 %1, vcc, 0, %5, vcc"
+        : "=&v"(h0), "=v"(h1)
+        : "v"((uint32_t)r3), "v"((uint32_t)(r2 >> 32)), "s"(c0), "v"((uint32_t)(r3 >> 32))
+        : "vcc");
+    lo = ((u64)(uint32_t)r2 << 32) | (uint32_t)r0;
+    hi = ((u64)h1 << 32) | h0;
+#else
+    const u128 s = (((u128)hi << 64) | lo) + (u128)a * b;
+    lo = (u64)s;
+    hi = (u64)(s >> 64);
+#endif
 }
 
 }  // namespace mk

@@ -124,22 +124,29 @@ MK_D void gs_butterfly(u64 &x, u64 &y, u64 w, u64 wp, u64 q, u64 q2) {
 // forward, "n": x < 4.001U as is: x' < 6.376U, y' < 7.001U < 8U = the multiplier's input bound.
 // A round alternates f, n, f, n: its outputs stay below 7.001U < 8q, which is what the integer consumers (canon8, the
 // next round's first stage) are written for.
+// u - v + 3q.  3q is taken as an opaque wave-uniform pair (PmK is per limb, and a limb is fixed per workgroup): written
+// as 3 * q the compiler rebuilds it per butterfly with a multiply-add by 3 and a 32-bit add for the high word.
+MK_D u64 pm_diff(u64 u, u64 v, const PmK &P) {
+    u64 q3 = P.q3;
+    asm("" : "+s"(q3));
+    return (u + q3) - v;
+}
 MK_D void ct_butterfly_pm_f(u64 &x, u64 &y, u64 w, u64 wx, const PmK &P) {
     const u64 u = pm_fold(x, P);
     const u64 v = pm_lazy(y, w, wx, P);
     x = u + v;
-    y = u - v + P.q3;
+    y = pm_diff(u, v, P);
 }
 MK_D void ct_butterfly_pm_n(u64 &x, u64 &y, u64 w, u64 wx, const PmK &P) {
     const u64 v = pm_lazy(y, w, wx, P);
     const u64 u = x;
     x = u + v;
-    y = u - v + P.q3;
+    y = pm_diff(u, v, P);
 }
 // inverse: x, y < 2.375U -> x' = fold(x + y) < 1.001U, d = x - y + 3q < 5.375U, y' = d w < 2.375U
 MK_D void gs_butterfly_pm(u64 &x, u64 &y, u64 w, u64 wx, const PmK &P) {
     const u64 s = x + y;
-    const u64 d = x - y + P.q3;
+    const u64 d = pm_diff(x, y, P);
     x = pm_fold(s, P);
     y = pm_lazy(d, w, wx, P);
 }

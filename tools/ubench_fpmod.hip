@@ -3,9 +3,88 @@
 #include <cstdio>
 #include <cstdint>
 #include <cmath>
-#include "../ppqsflhe_amd/csrc/modarith.hpp"  // pm_lazy / pm_fold: the library's own pseudo-Mersenne arithmetic
+#include "../ppqsflhe_amd/csrc/ntt_kernels.hpp"  // pm_lazy / pm_fold and the butterflies: the library's own pseudo-Mersenne arithmetic
 typedef uint64_t u64;
 typedef unsigned __int128 u128;
+
+// the word-splitting form of pm_lazy and the butterfly tail written as u - v + 3q, which the library used before the
+// carry-out form: kept here to time the two side by side and to compare their words on the device
+namespace split {
+__device__ __forceinline__ u64 pm_lazy(u64 a, u64 wt, u64 wxt, const mk::PmK &P) {
+    const uint32_t a0 = (uint32_t)a, a1 = (uint32_t)(a >> 32);
+    const u64 y0 = (u64)a0 * (uint32_t)wt;
+    u64 z = (u64)a0 * (uint32_t)(wt >> 32) + mk::hi32_pair(y0);
+    const u64 y1 = (u64)a1 * (uint32_t)wxt + (u64)(uint32_t)y0;
+    z = (u64)a1 * (uint32_t)(wxt >> 32) + z;
+    z += mk::hi32_pair(y1);
+    const u64 lo = (((u64)(uint32_t)z << 32) | (uint32_t)y1) >> P.t;
+    return (u64)(uint32_t)(z >> 32) * P.c2 + lo;
+}
+__device__ __forceinline__ void ct_f(u64 &x, u64 &y, u64 w, u64 wx, const mk::PmK &P) {
+    const u64 u = mk::pm_fold(x, P), v = pm_lazy(y, w, wx, P);
+    x = u + v;
+    y = u - v + P.q3;
+}
+__device__ __forceinline__ void ct_n(u64 &x, u64 &y, u64 w, u64 wx, const mk::PmK &P) {
+    const u64 v = pm_lazy(y, w, wx, P), u = x;
+    x = u + v;
+    y = u - v + P.q3;
+}
+__device__ __forceinline__ void gs(u64 &x, u64 &y, u64 w, u64 wx, const mk::PmK &P) {
+    const u64 s = x + y, d = x - y + P.q3;
+    x = mk::pm_fold(s, P);
+    y = pm_lazy(d, w, wx, P);
+}
+}  // namespace split
+
+// exactness of the pseudo-Mersenne product and butterflies on the device: the library's forms against the splitting forms
+// (word for word) and against 128-bit integer arithmetic (residues), random operands with every 3rd / 5th one forced to
+// the ends of the ranges (full low word with the largest high word; w = q - 1), and a count of the products whose low sum
+// a_lo wt_lo + a_hi wxt_lo carries out of 64 bits -- the case the carry-out form exists for
+__global__ void k_check_pm(const u64 *seeds, u64 q, uint32_t k, unsigned long long *bad, unsigned long long *carries, int iters) {
+    u64 s = seeds[blockIdx.x * blockDim.x + threadIdx.x];
+    mk::LimbConst lc{};
+    lc.q = q; lc.k = k; lc.pm_c = (uint32_t)(((u64)1 << k) - q);
+    const mk::PmK P = mk::pm_consts(lc);
+    const u64 amax = ((u64)8 << k) - 1;
+    unsigned long long nbad = 0, ncarry = 0;
+    for (int i = 0; i < iters; ++i) {
+        s = s * 6364136223846793005ull + 1442695040888963407ull;
+        u64 a = (s >> 1) & amax; s = s * 6364136223846793005ull + 1442695040888963407ull;
+        u64 w = (u64)(((u128)(s >> 1) * q) >> 63);  // < q
+        s = s * 6364136223846793005ull + 1442695040888963407ull;
+        u64 x = (s >> 2) & (amax >> 1);  // < 4U: the "n" butterfly's x
+        if (i % 3 == 0) a |= 0xffffffffull;
+        if (i % 5 == 0) a = amax - (i % 4);
+        if (i % 7 == 0) w = q - 1 - (i % 3);
+        const u64 wt = w << (63 - k), wxt = (u64)(((u128)w << 32) % q) << (63 - k);
+        const u64 r = mk::pm_lazy(a, wt, wxt, P);
+        const u64 prod = (u64)((u128)a * w % q);
+        if (r != split::pm_lazy(a, wt, wxt, P) || r % q != prod) ++nbad;
+        const u128 low = (u128)(uint32_t)a * (uint32_t)wt + (u128)(uint32_t)(a >> 32) * (uint32_t)wxt;
+        ncarry += (unsigned)(low >> 64);
+        const u64 xm = x % q, sum = (xm + prod) % q, dif = (xm + q - prod) % q;
+        u64 x1 = x, y1 = a, x2 = x, y2 = a;
+        mk::ct_butterfly_pm_n(x1, y1, wt, wxt, P);
+        split::ct_n(x2, y2, wt, wxt, P);
+        if (x1 != x2 || y1 != y2 || x1 % q != sum || y1 % q != dif) ++nbad;
+        x1 = x2 = s;  // "f" folds any 64-bit x first
+        y1 = y2 = a;
+        mk::ct_butterfly_pm_f(x1, y1, wt, wxt, P);
+        split::ct_f(x2, y2, wt, wxt, P);
+        if (x1 != x2 || y1 != y2 || x1 % q != (s % q + prod) % q || y1 % q != (s % q + q - prod) % q) ++nbad;
+        // inverse: x, y < 2.375U
+        const u64 gx = x >> 1, gy = a >> 2;
+        x1 = x2 = gx;
+        y1 = y2 = gy;
+        mk::gs_butterfly_pm(x1, y1, wt, wxt, P);
+        split::gs(x2, y2, wt, wxt, P);
+        const u64 gd = (gx % q + q - gy % q) % q;
+        if (x1 != x2 || y1 != y2 || x1 % q != (gx % q + gy % q) % q || y1 % q != (u64)((u128)gd * w % q)) ++nbad;
+    }
+    atomicAdd(bad, nbad);
+    atomicAdd(carries, ncarry);
+}
 
 // v = y*w - b*q exactly, |v| <= 1.5 q for |y| <= 2^52  (y, w integers held in doubles; wq = w/q rounded)
 __device__ __forceinline__ double fp_mulmod(double y, double w, double wq, double q) {
@@ -71,8 +150,15 @@ __global__ void k_rate(double *out, double seed) {
             lc.q = 1152921504606584833ull; lc.k = 60; lc.pm_c = (uint32_t)((1ull << 60) - lc.q);
             const mk::PmK P = mk::pm_consts(lc);
             const u64 wt = wi << 3, wxt = (u64)(((u128)wi << 32) % lc.q) << 3;
-#define PMB(x, y) { u64 u = (i & 1) ? x : mk::pm_fold(x, P); u64 v = mk::pm_lazy(y, wt, wxt, P); x = u + v; y = u - v + P.q3; }
+#define PMB(x, y) { if (i & 1) mk::ct_butterfly_pm_n(x, y, wt, wxt, P); else mk::ct_butterfly_pm_f(x, y, wt, wxt, P); }
             PMB(a0, b0) PMB(a1, b1) PMB(a2, b2) PMB(a3, b3)
+        } else if (OP == 4) {  // the same with the word-splitting product and the u - v + 3q tail
+            mk::LimbConst lc{};
+            lc.q = 1152921504606584833ull; lc.k = 60; lc.pm_c = (uint32_t)((1ull << 60) - lc.q);
+            const mk::PmK P = mk::pm_consts(lc);
+            const u64 wt = wi << 3, wxt = (u64)(((u128)wi << 32) % lc.q) << 3;
+#define PMS(x, y) { u64 u = (i & 1) ? x : mk::pm_fold(x, P); u64 v = split::pm_lazy(y, wt, wxt, P); x = u + v; y = u - v + P.q3; }
+            PMS(a0, b0) PMS(a1, b1) PMS(a2, b2) PMS(a3, b3)
         } else if (OP == 2) {  // rint rate
             x0 = rint(x0 * 1.0000001) + 0.25; x1 = rint(x1 * 1.0000001) + 0.25; x2 = rint(x2 * 1.0000001) + 0.25; x3 = rint(x3 * 1.0000001) + 0.25;
         }
@@ -113,9 +199,31 @@ int main() {
                64 - __builtin_clzll(q), nb, (double)blocks * threads * iters, m / (double)q);
         delete[] h;
     }
+    {   // pseudo-Mersenne product and butterflies: the reference context's 60-bit primes, a 55- and a 58-bit prime
+        const struct { u64 q; uint32_t k; } pms[] = {{1152921504606748673ull, 60}, {1152921504606683137ull, 60},
+                                                     {1152921504606584833ull, 60}, {36028797017456641ull, 55},
+                                                     {288230376150630401ull, 58}};
+        for (const auto &pm : pms) {
+            const int blocks = 256, threads = 256, iters = 2000;
+            u64 *seeds; unsigned long long *cnt;
+            (void)hipMalloc(&seeds, blocks * threads * 8); (void)hipMalloc(&cnt, 16);
+            u64 *h = new u64[blocks * threads];
+            for (int i = 0; i < blocks * threads; ++i) h[i] = 0x9E3779B97F4A7C15ull * (i + 1) + pm.q;
+            (void)hipMemcpy(seeds, h, blocks * threads * 8, hipMemcpyHostToDevice);
+            (void)hipMemset(cnt, 0, 16);
+            k_check_pm<<<blocks, threads>>>(seeds, pm.q, pm.k, cnt, cnt + 1, iters);
+            unsigned long long c[2] = {~0ull, 0};
+            (void)hipMemcpy(c, cnt, 16, hipMemcpyDeviceToHost);
+            printf("pm q=%llu (%u bits): %llu mismatches in %.1e products and 3 butterflies each (carry 1 in %llu)\n",
+                   (unsigned long long)pm.q, pm.k, c[0], (double)blocks * threads * iters, c[1]);
+            delete[] h;
+            (void)hipFree(seeds); (void)hipFree(cnt);
+        }
+    }
     rate<0>("fp64 butterfly (+reduce/2)", 4);
     rate<1>("int Shoup butterfly", 4);
     rate<2>("rint+mul+add", 4);
     rate<3>("int pseudo-Mersenne butterfly", 4);
+    rate<4>("  the same, word-splitting form", 4);
     return 0;
 }

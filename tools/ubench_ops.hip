@@ -22,13 +22,14 @@ constexpr int REP = 256;
 enum Op {
     MAD_U64_U32, LSHL_ADD_U64, LSHRREV_B64, LSHLREV_B64, MOV_B32, AND_B32, ADD_U32, ADD_CO_PAIR, ALIGNBIT, BITOP3,
     FMA_F64, MUL_F64, ADD_F64, RNDNE_F64, CVT_F64_U32, CNDMASK, MUL_LO_U32, MUL_HI_U32, ADD3_U32, LSHRREV_B32, XOR_B32,
-    FMA_F32, CVT_U32_F64, MAD_DEP, FMA_F64_DEP, N_OPS
+    FMA_F32, CVT_U32_F64, MAD_DEP, FMA_F64_DEP, CMP_CNDMASK, CSUB_SELECT, CSUB_MASK, N_OPS
 };
 static const char *NAMES[N_OPS] = {
     "v_mad_u64_u32", "v_lshl_add_u64", "v_lshrrev_b64", "v_lshlrev_b64", "v_mov_b32", "v_and_b32", "v_add_u32",
     "v_add_co_u32 + v_addc_co_u32 (pair)", "v_alignbit_b32", "v_bitop3_b32 (v_xor3 class)", "v_fma_f64", "v_mul_f64",
     "v_add_f64", "v_rndne_f64", "v_cvt_f64_u32", "v_cndmask_b32", "v_mul_lo_u32", "v_mul_hi_u32", "v_add3_u32",
-    "v_lshrrev_b32", "v_xor_b32", "v_fma_f32", "v_cvt_u32_f64", "v_mad_u64_u32 DEPENDENT chain", "v_fma_f64 DEPENDENT chain"};
+    "v_lshrrev_b32", "v_xor_b32", "v_fma_f32", "v_cvt_u32_f64", "v_mad_u64_u32 DEPENDENT chain", "v_fma_f64 DEPENDENT chain",
+    "v_cmp_gt_i32 + v_cndmask_b32 (pair)", "csub: x - m, sign selects", "csub: t + (m & t >> 63)"};
 
 template <int OP, int LDS_BYTES>
 __global__ __launch_bounds__(256) void k_op(u64 *out, unsigned *cycles, u64 seed) {
@@ -147,6 +148,18 @@ __global__ __launch_bounds__(256) void k_op(u64 *out, unsigned *cycles, u64 seed
 #define S(i) asm volatile("v_mad_u64_u32 %0, vcc, %1, %2, %0" : "+v"(a[0]) : "v"((uint32_t)a[0]), "v"(m32) : "vcc");
             OP8(S)
 #undef S
+        } else if (OP == CMP_CNDMASK) {  // the select with the compare that feeds it (the plain v_cndmask_b32 row reads a stale vcc)
+#define S(i) asm volatile("v_cmp_gt_i32 vcc, 0, %0\n\tv_cndmask_b32 %0, %0, %1, vcc" : "+v"(x[i]) : "v"(m32) : "vcc");
+            OP8(S)
+#undef S
+        } else if (OP == CSUB_SELECT) {  // modarith.hpp's csub as the compiler emits it (64-bit subtract, v_cmp_gt_i64, two selects)
+#define S(i) { const u64 t = a[i] + (0 - seed); a[i] = (long long)t < 0 ? a[i] : t; asm volatile("" : "+v"(a[i])); }
+            OP8(S)
+#undef S
+        } else if (OP == CSUB_MASK) {  // the branch-free way of writing it (hipcc lowers it to the same subtract, compare and two selects)
+#define S(i) { const u64 t = a[i] - seed; a[i] = t + (seed & (u64)((long long)t >> 63)); asm volatile("" : "+v"(a[i])); }
+            OP8(S)
+#undef S
         } else if (OP == FMA_F64_DEP) {
 #define S(i) asm volatile("v_fma_f64 %0, %0, %1, %0" : "+v"(d[0]) : "v"(dc));
             OP8(S)
@@ -217,5 +230,9 @@ int main() {
     bench<CVT_U32_F64>(d_out, d_cyc);
     bench<MAD_DEP>(d_out, d_cyc);
     bench<FMA_F64_DEP>(d_out, d_cyc);
+    // the conditional subtraction of modarith.hpp, whole (rows count one csub)
+    bench<CMP_CNDMASK>(d_out, d_cyc);
+    bench<CSUB_SELECT>(d_out, d_cyc);
+    bench<CSUB_MASK>(d_out, d_cyc);
     return 0;
 }
