@@ -1565,8 +1565,9 @@ static void launch_row3_inner_fp_n(const InnerArgs &a, const NttTables &T, uint3
 template <int LOGC, bool INVP>
 static void launch_row3_inner_int_k(const InnerArgs &a, const NttTables &T, uint32_t nparts, uint32_t L, u64 *pc,
                                     uint32_t K, hipStream_t s) {
-    if (!a.nsel) return;
-    const dim3 grid(((1u << T.log_r1) / RowT<LOGC>::ROWS) * a.nsel * a.items);
+    if (!a.nsel || !a.items) return;
+    // a workgroup walks up to inner_walk_len(nparts) ciphertext indices of one client
+    const dim3 grid(((1u << T.log_r1) / RowT<LOGC>::ROWS) * a.nsel * inner_walks(a, nparts));
     switch (nparts) {
         case 1: with_int_arith(T, [&](auto ar) {
             k_row3_inner_int<1, LOGC, INVP, decltype(ar)::value>

@@ -85,7 +85,7 @@ MK_D void st_stream2(ulong2 *p, ulong2 v) {
 #ifndef MK_STAMP
 #define MK_STAMP 0
 #endif
-constexpr unsigned STAMP_REGION = 1u << 20, STAMP_REGIONS = 4;
+constexpr unsigned STAMP_REGION = 1u << 20, STAMP_REGIONS = 5;
 struct Stamper {
     unsigned long long t[8];
     MK_D Stamper() {
@@ -120,6 +120,10 @@ struct Stamper {
             return v;
         }
         return 0;
+    }
+    // wait for the vector-memory loads in flight, so that their round trip is charged to the phase that issued them
+    MK_D void drain_vm() {
+        if (MK_STAMP) __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
     }
     template <int REGION>
     MK_D void flush(unsigned long long *buf, bool differences) {
@@ -1993,18 +1997,64 @@ MK_D void row3_inverse_int(u64 (&x)[8], const Row3Ctx &c, const u64 (&wc)[7], co
 // inner product with 128-bit accumulators (one Barrett at the end), three-round geometry (8 words per thread keep the
 // 16 accumulator words + data + twiddles within 3 waves per SIMD).  a.slot_mask selects SLOTS (q0 = slot 0, P limbs =
 // slots nl..ext-1); P limbs have no owning digit.
+//
+// A workgroup owns (client, limb slot, row tile) and WALKS up to MK_INNER_WALK consecutive ciphertext indices of that
+// client: every twiddle depends on (limb, tile) only, so the round-A/B twiddles of both directions are staged once per
+// workgroup (the inverse tables in a region of their own: no restaging and no workgroup barrier inside the walk), the
+// forward round-C twiddles stay in registers and the inverse ones are parked in LDS (row3_park_c_twiddles).  The first
+// digit of item i + 1 is loaded where the last digit of item i leaves the data registers, under item i's reductions and
+// inverse passes.  A walk never crosses a client (the eval key is per client); the last walk of a client is shorter
+// when the index count is no multiple of the walk length.  Per item the operations and their order are those of a
+// one-item workgroup, so the stored words do not depend on the walk length.
 #ifndef MK_INVP_WAVES
 #define MK_INVP_WAVES 2  // 168 VGPRs would spill 19 registers in the P instance; 2 waves measured +0.7 %
 #endif
 #ifndef MK_INNERQ_WAVES
 #define MK_INNERQ_WAVES 2  // the q_0 instance too: no scratch (9 registers at 3 waves), 4 096 workgroups = 8 rounds of 512 slots, +0.36 %
 #endif
+#ifndef MK_INNER_WALK
+#define MK_INNER_WALK 4  // flagship shape, P instance: 4 096 workgroups = 8 exact rounds of the 512 resident slots
+#endif
+// items per client as the walk sees them, and the walks of a launch (host and device agree on the grid through these)
+// (the single-digit instances keep one item per workgroup: their q_0 form runs 3 waves per SIMD with 158-164 registers,
+// which the walk's loop-carried state would cost it)
+MK_HD constexpr uint32_t inner_walk_len(uint32_t nparts) { return nparts == 1 ? 1 : MK_INNER_WALK; }
+MK_HD uint32_t inner_walk_ipc(const InnerArgs &a) { return a.ipc < a.items ? a.ipc : a.items; }
+MK_HD uint32_t inner_walks(const InnerArgs &a, uint32_t nparts) {
+    const uint32_t ipc = inner_walk_ipc(a), w = inner_walk_len(nparts);
+    return ipc ? (a.items / ipc) * ((ipc + w - 1) / w) : 0;
+}
+// group_member for the walk grid.  With fewer members per group, a grid whose groups are too few for group_member's
+// CU-affine form (groups % 256 != 0; the flagship's 128 P groups) would put two different (limb, tile) groups on every
+// CU.  Here the 32 CU positions of an XCD's queue are shared by c groups (c = the largest power of two <= 32 that
+// divides the groups of an XCD), 32 / c members of each side by side, and the following members of a group come 32
+// positions later: the workgroups resident on one CU share (limb, tile), and neighbouring members -- the walks of one
+// client, which share its eval-key tiles -- meet there.  A bijection like group_member: placement is a speed matter only.
+MK_D void walk_member(uint32_t b, uint32_t groups, uint32_t members, uint32_t cu_affine, uint32_t &grp, uint32_t &mem) {
+    if (cu_affine && groups % 8 == 0 && groups % 256 != 0) {
+        const uint32_t gx = groups / 8, low = gx & (0u - gx), cc = low < 32 ? low : 32, lanes = 32 / cc;
+        if (members % lanes == 0) {
+            const uint32_t xcd = b % 8, qidx = b / 8, per = cc * members;
+            const uint32_t blk = qidx / per, r = qidx % per, col = r % 32;
+            grp = (blk * cc + col % cc) * 8 + xcd;
+            mem = (r / 32) * lanes + col / cc;
+            return;
+        }
+    }
+    group_member(b, groups, members, cu_affine, grp, mem);
+}
 template <int NPARTS, int LOGC, bool INVP, int AR>
 __global__ __launch_bounds__(NTT_THREADS, INVP ? MK_INVP_WAVES : MK_INNERQ_WAVES) void k_row3_inner_int(InnerArgs a, NttTables T, uint32_t L, u64 *pc,
                                                                    uint32_t K) {
     using TL = RowT<LOGC>;
-    constexpr int R = TL::R, S = TL::ROWS, TPR = TL::TPR, PAIRS = 4;
-    __shared__ u64 lds[TL::WORDS + 2 * (TL::TWA + TL::TWB)];
+    constexpr int R = TL::R, S = TL::ROWS, TPR = TL::TPR, PAIRS = 4, W = inner_walk_len(NPARTS);
+    constexpr int TWW = 2 * (TL::TWA + TL::TWB);  // the round-A/B twiddles of one direction
+    constexpr int NC = INVP ? (LOGC == 3 ? 7 : 6) : 0;
+    // The Shoup instances (AR_INT) sit at the register limit of 2 waves per SIMD already: they reload the forward round-C
+    // twiddles and the first digit at the head of every item instead of holding them across the inverse passes
+    constexpr bool LEAN = AR != AR_PM;
+    __shared__ u64 lds[TL::WORDS + (INVP ? 2 : 1) * TWW];
+    __shared__ ulong2 ldsc[NC ? NC * NTT_THREADS : 1];  // the inverse round-C twiddles (P instance)
     Row3Ctx c;
     c.lds = lds;
     c.twa = lds + TL::WORDS;
@@ -2013,8 +2063,10 @@ __global__ __launch_bounds__(NTT_THREADS, INVP ? MK_INVP_WAVES : MK_INNERQ_WAVES
     c.twb_sh = c.twb + TL::TWB;
     const uint32_t n = 1u << T.log_n, r1 = 1u << T.log_r1;
     const uint32_t tiles = r1 / S, groups = tiles * a.nsel;
-    uint32_t grp, item;
-    group_member(blockIdx.x, groups, a.items, T.cu_affine, grp, item);
+    const uint32_t ipc = inner_walk_ipc(a), wper = (ipc + W - 1) / W;  // walks per client
+    uint32_t grp, wk;
+    walk_member(blockIdx.x, groups, inner_walks(a, NPARTS), T.cu_affine, grp, wk);
+    const uint32_t i0 = (wk % wper) * W, item0 = (wk / wper) * ipc + i0, wn = ipc - i0 < (uint32_t)W ? ipc - i0 : (uint32_t)W;
     const uint32_t sl = nth_set_bit(a.slot_mask, grp / tiles);
     const uint32_t id = limb_id_of(sl, a.nl, L);
     const LimbConst lc = T.limb[id];
@@ -2022,131 +2074,177 @@ __global__ __launch_bounds__(NTT_THREADS, INVP ? MK_INVP_WAVES : MK_INNERQ_WAVES
     const uint32_t row0 = (grp % tiles) * S;
     c.g = threadIdx.x / TPR;
     c.t = threadIdx.x % TPR;
+    Row3Ctx ci = c;  // the inverse row pass: its own round-A/B region, round C parked
+    ci.twa = c.twa + TWW;
+    ci.twa_sh = c.twa_sh + TWW;
+    ci.twb = c.twb + TWW;
+    ci.twb_sh = c.twb_sh + TWW;
+    ci.twc = ldsc;
     const u64 *tw = T.tw + (size_t)id * n, *tw_sh = T.tw_sh + (size_t)id * n;
+    Stamper stm;  // diagnostic build, sums per wave: [0] prologue, [1] transforms, [2] products, [3] restaging (none in the walk),
+                  // [4] reductions, [5] LDS hand-off + round-C fetch, [6] inverse transforms, [7] stores
+    unsigned long long t_mark = stm.now();
     row3_stage_twiddles<LOGC>(c, tw, tw_sh, r1 + row0);
     u64 wc[7], wpc[7];
-    row3_load_c_twiddles<LOGC>(tw, tw_sh, r1 + row0 + c.g, c.t, wc, wpc);
-    const size_t tile_off = (size_t)row0 * R;
-    const u64 *evk = inner_evk(a, item);
-    int jn = own == 0 ? 1 : 0;
-    const u64 *dig0 = a.dig + ((size_t)item * NPARTS * a.ext + sl) * n + tile_off + (size_t)c.g * R + c.t;
-    u64 x[8];
-    if (jn < NPARTS) {
-        const u64 *src = dig0 + (size_t)jn * a.ext * n;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) x[k] = ld_stream(src + TPR * k);
+    if (INVP) {
+        const u64 *itw = T.itw + (size_t)id * n, *itw_sh = T.itw_sh + (size_t)id * n;
+        row3_stage_twiddles<LOGC>(ci, itw, itw_sh, r1 + row0);
+        row3_load_c_twiddles<LOGC>(itw, itw_sh, r1 + row0 + c.g, c.t, wc, wpc);
+        row3_park_c_twiddles<LOGC>(ci, wc, wpc);
     }
-    u64 h0[2 * PAIRS], l0[2 * PAIRS], h1[2 * PAIRS], l1[2 * PAIRS];
+    if (!LEAN) row3_load_c_twiddles<LOGC>(tw, tw_sh, r1 + row0 + c.g, c.t, wc, wpc);
+    const size_t tile_off = (size_t)row0 * R;
+    const u64 *evk0 = inner_evk(a, item0);  // one client per walk
+    const int j0 = own == 0 ? 1 : 0;
+    const size_t dig_limb = (size_t)a.ext * n, dig_item = NPARTS * dig_limb;
+    // wave-uniform bases + one thread offset: the walk carries no per-thread 64-bit address from item to item
+    const u64 *dig0 = a.dig + (size_t)item0 * dig_item + (size_t)sl * n + tile_off;
+    const uint32_t th = (uint32_t)c.g * R + c.t;
+    u64 x[8];
+    if (!LEAN && j0 < NPARTS) {
+        const u64 *src = dig0 + j0 * dig_limb;
 #pragma unroll
-    for (int i = 0; i < 2 * PAIRS; ++i) h0[i] = l0[i] = h1[i] = l1[i] = 0;
-    if (own >= 0) {  // the digit that owns this limb: c1 itself
-        const u64 *y0 = inner_c1(a, item) + (size_t)sl * n + tile_off;
-        const u64 *e0 = evk + (((size_t)own * 2 + 0) * a.D + id) * n + tile_off;
-        const u64 *e1 = evk + (((size_t)own * 2 + 1) * a.D + id) * n + tile_off;
-#pragma unroll
-        for (int i = 0; i < PAIRS; ++i) {
-            const int e = row3_pair<LOGC>(c.g, c.t, i);
-            const ulong2 yy = ld_stream2(reinterpret_cast<const ulong2 *>(y0) + e);
-            const ulong2 b = reinterpret_cast<const ulong2 *>(e0)[e];
-            const ulong2 cc = reinterpret_cast<const ulong2 *>(e1)[e];
-            mac128(h0[2 * i], l0[2 * i], yy.x, b.x);
-            mac128(h0[2 * i + 1], l0[2 * i + 1], yy.y, b.y);
-            mac128(h1[2 * i], l1[2 * i], yy.x, cc.x);
-            mac128(h1[2 * i + 1], l1[2 * i + 1], yy.y, cc.y);
-        }
+        for (int k = 0; k < 8; ++k) x[k] = ld_stream(src + th + TPR * k);
     }
     __syncthreads();  // twiddles staged
+    stm.drain_vm();
+    t_mark = stm.add<0>(t_mark);
 #pragma unroll 1
-    for (int dj = jn; dj < NPARTS; dj = jn) {
-        jn = dj + 1 == own ? dj + 2 : dj + 1;
-        wave_lds_sync();
-        row3_forward<AR, LOGC>(x, c, wc, wpc, lc);
+    for (uint32_t it = 0; it < wn; ++it, dig0 += dig_item) {
+        const uint32_t item = item0 + it;
+        const u64 *evk = evk0;
+        if (LEAN) {
+            // per-thread addresses are formed here, not hoisted out of the walk and held in registers: the bases move by
+            // an opaque zero, the thread's coordinates are taken afresh
+            uint32_t z = 0, thl = th;
+            asm volatile("" : "+s"(z), "+v"(thl));
+            const int tl = thl % TPR, gl = thl / R;
+            evk += z;
+            row3_load_c_twiddles<LOGC>(tw + z, tw_sh + z, r1 + row0 + gl, tl, wc, wpc);
+            if (j0 < NPARTS) {
+                const u64 *src = dig0 + j0 * dig_limb;
 #pragma unroll
-        // AR_PM: the lazy words (< 7.001U) go into the products as they are -- pm_reduce128 takes 6 x 2^63 x q
-        for (int k = 0; k < 8; ++k) lds[TL::at(c.g, 8 * c.t + k)] = AR == AR_PM ? x[k] : canon8(x[k], lc.q, lc.q2);
-        if (jn < NPARTS) {
-            const u64 *src = dig0 + (size_t)jn * a.ext * n;
-#pragma unroll
-            for (int k = 0; k < 8; ++k) x[k] = ld_stream(src + TPR * k);
+                for (int k = 0; k < 8; ++k) x[k] = ld_stream(src + th + TPR * k);
+            }
         }
-        wave_lds_sync();
-        const u64 *e0 = evk + (((size_t)dj * 2 + 0) * a.D + id) * n + tile_off;
-        const u64 *e1 = evk + (((size_t)dj * 2 + 1) * a.D + id) * n + tile_off;
-        ulong2 eb[PAIRS], ec[PAIRS];
-        // the digit's eval-key tiles in one burst (see k_qsum3_fp; +0.2 % on the step) in the 2-wave instances, which have the
-        // registers; a 3-wave instance would park 14 more in scratch
-        constexpr bool BURST = INVP ? MK_INVP_WAVES == 2 : MK_INNERQ_WAVES == 2;
-        if (BURST) {
+        u64 h0[2 * PAIRS], l0[2 * PAIRS], h1[2 * PAIRS], l1[2 * PAIRS];
+#pragma unroll
+        for (int i = 0; i < 2 * PAIRS; ++i) h0[i] = l0[i] = h1[i] = l1[i] = 0;
+        if (own >= 0) {  // the digit that owns this limb: c1 itself
+            const u64 *y0 = inner_c1(a, item) + (size_t)sl * n + tile_off;
+            const u64 *e0 = evk + (((size_t)own * 2 + 0) * a.D + id) * n + tile_off;
+            const u64 *e1 = evk + (((size_t)own * 2 + 1) * a.D + id) * n + tile_off;
 #pragma unroll
             for (int i = 0; i < PAIRS; ++i) {
                 const int e = row3_pair<LOGC>(c.g, c.t, i);
-                eb[i] = reinterpret_cast<const ulong2 *>(e0)[e];
-                ec[i] = reinterpret_cast<const ulong2 *>(e1)[e];
+                const ulong2 yy = ld_stream2(reinterpret_cast<const ulong2 *>(y0) + e);
+                const ulong2 b = reinterpret_cast<const ulong2 *>(e0)[e];
+                const ulong2 cc = reinterpret_cast<const ulong2 *>(e1)[e];
+                mac128(h0[2 * i], l0[2 * i], yy.x, b.x);
+                mac128(h0[2 * i + 1], l0[2 * i + 1], yy.y, b.y);
+                mac128(h1[2 * i], l1[2 * i], yy.x, cc.x);
+                mac128(h1[2 * i + 1], l1[2 * i + 1], yy.y, cc.y);
             }
-            __builtin_amdgcn_sched_barrier(0);
+            t_mark = stm.add<2>(t_mark);
         }
-#pragma unroll
-        for (int i = 0; i < PAIRS; ++i) {
-            const int e = row3_pair<LOGC>(c.g, c.t, i);
-            const int xx = (2 * e) % R;
-            const ulong2 b = BURST ? eb[i] : reinterpret_cast<const ulong2 *>(e0)[e];
-            const ulong2 cc = BURST ? ec[i] : reinterpret_cast<const ulong2 *>(e1)[e];
-            const u64 yx = lds[TL::at(c.g, xx)], yz = lds[TL::at(c.g, xx + 1)];
-            mac128(h0[2 * i], l0[2 * i], yx, b.x);
-            mac128(h0[2 * i + 1], l0[2 * i + 1], yz, b.y);
-            mac128(h1[2 * i], l1[2 * i], yx, cc.x);
-            mac128(h1[2 * i + 1], l1[2 * i + 1], yz, cc.y);
-        }
-    }
-    // P limbs with `pc` given: the results go straight through the INVERSE row pass (first pass of ApproxModDown's
-    // SetFormat(COEFFICIENT)) and land in pc[2 item + comp][K][N]; the accumulators over P never reach HBM
-    constexpr bool inv = INVP;  // this instance is launched over P slots only, with pc given
-    const u64 *itw = T.itw + (size_t)id * n, *itw_sh = T.itw_sh + (size_t)id * n;
-    if (inv) {
-        __syncthreads();  // every wave is done with the forward round-A/B twiddles
-        row3_stage_twiddles<LOGC>(c, itw, itw_sh, r1 + row0);
-        __syncthreads();
-    }
+        int jn = j0;
 #pragma unroll 1
-    for (int comp = 0; comp < 2; ++comp) {
-        ulong2 res[PAIRS];
+        for (int dj = jn; dj < NPARTS; dj = jn) {
+            jn = dj + 1 == own ? dj + 2 : dj + 1;
+            wave_lds_sync();
+            row3_forward<AR, LOGC>(x, c, wc, wpc, lc);
 #pragma unroll
-        for (int i = 0; i < PAIRS; ++i) {
-            const u64 hx = comp ? h1[2 * i] : h0[2 * i], lx = comp ? l1[2 * i] : l0[2 * i];
-            const u64 hy = comp ? h1[2 * i + 1] : h0[2 * i + 1], ly = comp ? l1[2 * i + 1] : l0[2 * i + 1];
-            if (AR == AR_PM) {
-                const PmK P = pm_consts(lc);
-                res[i].x = pm_reduce128(hx, lx, P, lc.q);
-                res[i].y = pm_reduce128(hy, ly, P, lc.q);
-            } else {
-                res[i].x = NPARTS <= 4 ? reduce_sum4(hx, lx, lc) : reduce_wide(hx, lx, lc);
-                res[i].y = NPARTS <= 4 ? reduce_sum4(hy, ly, lc) : reduce_wide(hy, ly, lc);
-            }
-        }
-        if (!inv) {
-            u64 *td = a.til + (a.til_compact ? ((size_t)item * 2 + comp) * a.nsel + grp / tiles
-                                             : ((size_t)item * 2 + comp) * a.ext + sl) * n + tile_off;
+            // AR_PM: the lazy words (< 7.001U) go into the products as they are -- pm_reduce128 takes 6 x 2^63 x q
+            for (int k = 0; k < 8; ++k) lds[TL::at(c.g, 8 * c.t + k)] = AR == AR_PM ? x[k] : canon8(x[k], lc.q, lc.q2);
+            // the next digit, or the first digit of the walk's next item
+            const u64 *src = jn < NPARTS ? dig0 + jn * dig_limb : (!LEAN && it + 1 < wn ? dig0 + dig_item + j0 * dig_limb : nullptr);
+            if (src) {
 #pragma unroll
-            for (int i = 0; i < PAIRS; ++i) st_stream2(reinterpret_cast<ulong2 *>(td) + row3_pair<LOGC>(c.g, c.t, i), res[i]);
-        } else {
-            wave_lds_sync();  // the previous use of this wave's row (last digit's products / component 0) is over
-#pragma unroll
-            for (int i = 0; i < PAIRS; ++i) {
-                const int xx = (2 * row3_pair<LOGC>(c.g, c.t, i)) % R;
-                lds[TL::at(c.g, xx)] = res[i].x;
-                lds[TL::at(c.g, xx + 1)] = res[i].y;
+                for (int k = 0; k < 8; ++k) x[k] = ld_stream(src + th + TPR * k);
             }
             wave_lds_sync();
+            t_mark = stm.add<1>(t_mark);
+            const u64 *e0 = evk + (((size_t)dj * 2 + 0) * a.D + id) * n + tile_off;
+            const u64 *e1 = evk + (((size_t)dj * 2 + 1) * a.D + id) * n + tile_off;
+            ulong2 eb[PAIRS], ec[PAIRS];
+            // the digit's eval-key tiles in one burst (see k_qsum3_fp; +0.2 % on the step) in the 2-wave instances, which have the
+            // registers; a 3-wave instance would park 14 more in scratch
+            constexpr bool BURST = INVP ? MK_INVP_WAVES == 2 : MK_INNERQ_WAVES == 2;
+            if (BURST) {
 #pragma unroll
-            for (int k = 0; k < 8; ++k) x[k] = lds[TL::at(c.g, 8 * c.t + k)];
-            u64 iwc[7], iwpc[7];  // (re)loaded per component: keeps them out of the accumulators' live range
-            row3_load_c_twiddles<LOGC>(itw, itw_sh, r1 + row0 + c.g, c.t, iwc, iwpc);
-            row3_inverse_int<LOGC, AR>(x, c, iwc, iwpc, lc);
-            u64 *pd = pc + (((size_t)item * 2 + comp) * K + (sl - a.nl)) * n + tile_off + (size_t)c.g * R + c.t;
+                for (int i = 0; i < PAIRS; ++i) {
+                    const int e = row3_pair<LOGC>(c.g, c.t, i);
+                    eb[i] = reinterpret_cast<const ulong2 *>(e0)[e];
+                    ec[i] = reinterpret_cast<const ulong2 *>(e1)[e];
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
 #pragma unroll
-            for (int k = 0; k < 8; ++k) st_pass(pd + TPR * k, x[k]);  // lazy [0,2q): the inverse column pass scales
+            for (int i = 0; i < PAIRS; ++i) {
+                const int e = row3_pair<LOGC>(c.g, c.t, i);
+                const int xx = (2 * e) % R;
+                const ulong2 b = BURST ? eb[i] : reinterpret_cast<const ulong2 *>(e0)[e];
+                const ulong2 cc = BURST ? ec[i] : reinterpret_cast<const ulong2 *>(e1)[e];
+                const u64 yx = lds[TL::at(c.g, xx)], yz = lds[TL::at(c.g, xx + 1)];
+                mac128(h0[2 * i], l0[2 * i], yx, b.x);
+                mac128(h0[2 * i + 1], l0[2 * i + 1], yz, b.y);
+                mac128(h1[2 * i], l1[2 * i], yx, cc.x);
+                mac128(h1[2 * i + 1], l1[2 * i + 1], yz, cc.y);
+            }
+            t_mark = stm.add<2>(t_mark);
+        }
+        // P limbs with `pc` given: the results go straight through the INVERSE row pass (first pass of ApproxModDown's
+        // SetFormat(COEFFICIENT)) and land in pc[2 item + comp][K][N]; the accumulators over P never reach HBM
+        constexpr bool inv = INVP;  // this instance is launched over P slots only, with pc given
+#pragma unroll 1
+        for (int comp = 0; comp < 2; ++comp) {
+            ulong2 res[PAIRS];
+#pragma unroll
+            for (int i = 0; i < PAIRS; ++i) {
+                const u64 hx = comp ? h1[2 * i] : h0[2 * i], lx = comp ? l1[2 * i] : l0[2 * i];
+                const u64 hy = comp ? h1[2 * i + 1] : h0[2 * i + 1], ly = comp ? l1[2 * i + 1] : l0[2 * i + 1];
+                if (AR == AR_PM) {
+                    const PmK P = pm_consts(lc);
+                    res[i].x = pm_reduce128(hx, lx, P, lc.q);
+                    res[i].y = pm_reduce128(hy, ly, P, lc.q);
+                } else {
+                    res[i].x = NPARTS <= 4 ? reduce_sum4(hx, lx, lc) : reduce_wide(hx, lx, lc);
+                    res[i].y = NPARTS <= 4 ? reduce_sum4(hy, ly, lc) : reduce_wide(hy, ly, lc);
+                }
+            }
+            t_mark = stm.add<4>(t_mark);
+            if (!inv) {
+                u64 *td = a.til + (a.til_compact ? ((size_t)item * 2 + comp) * a.nsel + grp / tiles
+                                                 : ((size_t)item * 2 + comp) * a.ext + sl) * n + tile_off;
+#pragma unroll
+                for (int i = 0; i < PAIRS; ++i) st_stream2(reinterpret_cast<ulong2 *>(td) + row3_pair<LOGC>(c.g, c.t, i), res[i]);
+                t_mark = stm.add<7>(t_mark);
+            } else {
+                wave_lds_sync();  // the previous use of this wave's row (last digit's products / component 0) is over
+#pragma unroll
+                for (int i = 0; i < PAIRS; ++i) {
+                    const int xx = (2 * row3_pair<LOGC>(c.g, c.t, i)) % R;
+                    lds[TL::at(c.g, xx)] = res[i].x;
+                    lds[TL::at(c.g, xx + 1)] = res[i].y;
+                }
+                wave_lds_sync();
+                u64 y[8];  // x holds the next item's first digit
+#pragma unroll
+                for (int k = 0; k < 8; ++k) y[k] = lds[TL::at(c.g, 8 * c.t + k)];
+                u64 iwc[7], iwpc[7];  // fetched per component: keeps them out of the accumulators' live range
+                row3_fetch_c_twiddles<LOGC>(ci, iwc, iwpc);
+                t_mark = stm.add<5>(t_mark);
+                row3_inverse_int<LOGC, AR>(y, ci, iwc, iwpc, lc);
+                t_mark = stm.add<6>(t_mark);
+                u64 *pd = pc + (((size_t)item * 2 + comp) * K + (sl - a.nl)) * n + tile_off;
+#pragma unroll
+                for (int k = 0; k < 8; ++k) st_pass(pd + th + TPR * k, y[k]);  // lazy [0,2q): the inverse column pass scales
+                t_mark = stm.add<7>(t_mark);
+            }
         }
     }
+    if (INVP) stm.flush<3>(T.stamps, false);
+    else stm.flush<4>(T.stamps, false);
 }
 
 // =====================================================================================

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """In-kernel phase timing of the hot kernels (diagnostic build).  Build: make -C ppqsflhe_amd/csrc OUT=../libmkckks_stamp.so
 CXXFLAGS="... -DMK_STAMP=1"; run on the GPU box:  MKCKKS_LIB=$PWD/ppqsflhe_amd/libmkckks_stamp.so MKCKKS_STAMPS=1 python tools/stamps.py
-Every wave of k_conv_col (fp64-class / integer-class targets) and k_qsum3_fp stamps the shader clock at its phase
-boundaries; this prints the median, 10th and 90th percentile of every phase in shader cycles, and the wave lifetime.
+Every wave of k_conv_col (fp64-class / integer-class targets), k_qsum3_fp and k_row3_inner_int (P limbs / q_0) stamps
+the shader clock at its phase boundaries; this prints the median, 10th and 90th percentile of every phase in shader cycles, and the wave lifetime.
 The stamps serialise the schedule at each mark (sched_barrier + s_waitcnt lgkmcnt(0)), so the instrumented kernels run
 a few percent longer than the product ones."""
 import ctypes
@@ -40,12 +40,18 @@ def main():
         g.reencrypt_sum(cts, evks, out, C, B, L)
     torch.cuda.synchronize()
     buf = np.zeros(1 << 20, dtype=np.uint64)
+    # every vector-memory load is drained at the end of the phase that issued it (Stamper::drain_vm) where the next phase
+    # would wait for it at once: the prologue and the round-C (re)load carry their own L2 round trips
+    INNER_INT = ["prologue (to the barrier)", "forward transforms", "eval-key products", "restaging (2 barriers)",
+                 "reductions", "LDS hand-off + round C", "inverse transforms", "stores issued"]
     names = {0: ("k_conv_col, fp64-class targets (last launch of the step)", ["conversion (loads + MACs)", "round A", "exchange + barrier",
                                                                               "round B", "stores issued"], True),
              1: ("k_conv_col, integer-class targets (last launch of the step)", ["conversion (loads + MACs)", "round A",
                                                                                  "exchange + barrier", "round B", "stores issued"], True),
              2: ("k_qsum3_fp (sums over the client loop)", ["own-digit products", "transforms", "digit products",
-                                                            "conversions + store", "whole loop"], False)}
+                                                            "conversions + store", "whole loop"], False),
+             3: ("k_row3_inner_int, P limbs (sums over the items of a workgroup)", INNER_INT, True),
+             4: ("k_row3_inner_int, q_0 (sums over the items of a workgroup)", INNER_INT, True)}
     for region, (title, phases, diffs) in names.items():
         n = ctypes.c_size_t(0)
         rc = lib.mkckks_debug_stamps(g._h, buf.ctypes.data, region, ctypes.byref(n))
@@ -55,6 +61,8 @@ def main():
         a = buf.reshape(-1, 8).astype(np.int64)
         a = a[(a != 0).any(axis=1)]
         print(f"== {title}: {len(a)} waves")
+        if not len(a):  # the kernel did not run in this step (k_conv_col where the two-target k_conv_col2 is launched)
+            continue
         for i, ph in enumerate(phases):
             col = a[:, i]
             col = col[col > 0]
