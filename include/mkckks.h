@@ -383,8 +383,11 @@ int mkckks_keygen_join(mkckks_ctx *c, const uint64_t *d_pk_prev, const int8_t *d
  * sum_j e_j cos(j theta_k), so the decoded values carry a Gaussian error of standard deviation
  * sigma * sqrt(n * N / 2) / scale.  At noise degree 2 (scale ~ 2^(2p)) that is nothing for any sigma of the sampler; at
  * scale 2^p it is the price of the statistical security sigma buys.
+ * d_sk may also be a key share u64[L][N] (lambda * sigma_j of the t-of-n section below): both paths, the fused kernels and
+ * the composition under the library switches, read limbs 0 .. nl - 1 of d_sk only.
  * Security rules: n-of-n -- the server plus any n - 1 parties learn the aggregate only, and a party that does not
- * answer blocks the round (t-of-n is out of scope).  ONE share per ciphertext per party, with fresh errors each time:
+ * answer blocks the round unless the key was shared t-of-n ("t-of-n threshold decryption" below: any t parties
+ * decrypt).  ONE share per ciphertext per party, with fresh errors each time:
  * two shares of one ciphertext average the smudging away.  The key the smudging errors are drawn under keys nothing
  * else. */
 int mkckks_partial_decrypt_batch(mkckks_ctx *c, const uint64_t *d_ct, const uint64_t *d_sk, const int64_t *d_e,
@@ -396,6 +399,48 @@ int mkckks_partial_decrypt_batch(mkckks_ctx *c, const uint64_t *d_ct, const uint
  * caller guarantees that exactly ONE share was made with lead != 0 (the hosts check it from the share headers). */
 int mkckks_fuse_shares_batch(mkckks_ctx *c, const uint64_t *d_shares, uint64_t *d_m, uint32_t n_parties, uint32_t n_ct,
                              uint32_t nl);
+
+/* ==== t-of-n threshold decryption: Shamir shares of the joint secret ============================================
+ * (Mouchet et al., "An efficient threshold access-structure for RLWE-based multiparty homomorphic encryption".)
+ * Once per key epoch party i shares its own sk_i among the n parties with threshold t, limb by limb and coefficient
+ * by coefficient over Z_{q_l}, in EVALUATION form; party j sums what it received: sigma_j = sum_i f_i(j) = F(j), where
+ * F = sum_i f_i has degree t - 1 and F(0) = sum_i sk_i, the joint secret.  In a round any set T of at least t parties
+ * decrypts: party j in T passes lambda_j^T * sigma_j to mkckks_partial_decrypt_batch in the place of its secret key,
+ * lambda_j^T = prod_{m in T, m != j} m (m - j)^-1 mod q_l the Lagrange coefficient at 0, so that
+ * sum_{j in T} lambda_j sigma_j = sum_i sk_i (mod q_l); smudging and mkckks_fuse_shares_batch are unchanged.  The
+ * Lagrange factor multiplies the key share, not the error: the noise rule above holds with n replaced by |T|.
+ * Rules: key shares are SECRETS and travel over private, authenticated channels, which this library does not provide;
+ * dealers are honest-but-curious (no verifiable sharing, no proactive refresh, no resharing to a new party); any t
+ * parties together hold the joint secret; ONE decryption share per ciphertext per party still holds; all shares that
+ * are fused must have been made with the SAME set T, or they fuse to noise -- the fusion cannot tell.
+ *
+ * ---- the dealer's step ---------------------------------------------------------------------------------------------
+ * For p < n_parties, i < nl, every coefficient c:
+ *     shares[p][i][c] = sk[i][c] + sum_{k=1}^{threshold-1} r_k[i][c] * (p + 1)^k     mod q_i
+ * Party indices are 1-based evaluation points: shares[p] goes to party p + 1.  r_k is BY DEFINITION the polynomial
+ *     mkckks_sample_uniform(d, n_polys = 1, nl, with_p = 0, h_key32, stream_id + k - 1)
+ * (limb i, coefficient c = word i*N + c of the stream, rejection as there: the definition seeded ciphertexts use), but it
+ * is never written to memory: r_k together with one share gives sk away.  Key rule: h_key32 keys nothing else -- one
+ * fresh OS-drawn key per call.  d_sk u64[D][N], limbs 0 .. nl - 1 read; d_shares out u64[n_parties][nl][N], canonical
+ * residues equal to exact integer arithmetic word for word.  1 <= threshold <= n_parties <= MKCKKS_MAX_PARTIES and
+ * 1 <= nl <= L; threshold = 1 is the degenerate sharing (every share is sk).  MKCKKS_E_INVALID if
+ * stream_id + threshold - 1 does not fit in 32 bits, or if d_shares overlaps the limbs of d_sk that are read. */
+#define MKCKKS_MAX_PARTIES 64
+int mkckks_share_key(mkckks_ctx *c, const uint64_t *d_sk, uint64_t *d_shares, uint32_t nl, uint32_t n_parties,
+                     uint32_t threshold, const uint8_t *h_key32, uint32_t stream_id);
+/* ---- weighted sum of key shares ------------------------------------------------------------------------------------
+ *     out[i][c] = sum_{j<m} h_w[j][i] * in[j][i][c]     mod q_i,   canonical
+ * d_in u64[m][nl][N]; h_w HOST u64[m][nl], read before return, every weight below its modulus (else MKCKKS_E_INVALID);
+ * d_out u64[nl][N].  m >= 1, 1 <= nl <= L.  d_out may be d_in (in[0]); any other overlap is MKCKKS_E_INVALID.  Three
+ * uses: party j's sum sigma_j of the shares it received (all weights 1), the per-round lambda * sigma_j (m = 1, weights
+ * from mkckks_lagrange_at_zero), and the recovery of F at any point. */
+int mkckks_combine_key_shares(mkckks_ctx *c, const uint64_t *d_in, const uint64_t *h_w, uint64_t *d_out, uint32_t m,
+                              uint32_t nl);
+/* ---- Lagrange coefficients at 0 (host only: works on a device = -1 context) ----------------------------------------
+ * h_out[a][l] = lambda of h_parties[a] within the set h_parties[0 .. n_active), mod q_l, for the L limbs of Q.
+ * h_parties are 1-based party indices.  An index of 0 or above MKCKKS_MAX_PARTIES, a duplicate and n_active == 0 are
+ * each MKCKKS_E_INVALID. */
+int mkckks_lagrange_at_zero(const mkckks_ctx *c, const uint32_t *h_parties, uint32_t n_active, uint64_t *h_out);
 
 /* ---- multi-GPU aggregation step (new) -----------------------
  * after an RCCL ncclSum over uint64 of `n_terms` canonical residues per word,

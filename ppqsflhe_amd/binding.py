@@ -83,6 +83,9 @@ SYMBOLS = {
     "mkckks_keygen_join": (_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "mkckks_partial_decrypt_batch": (_int, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _int]),
     "mkckks_fuse_shares_batch": (_int, [_vp, _vp, _vp, _u32, _u32, _u32]),
+    "mkckks_share_key": (_int, [_vp, _vp, _vp, _u32, _u32, _u32, C.c_char_p, _u32]),
+    "mkckks_combine_key_shares": (_int, [_vp, _vp, _vp, _vp, _u32, _u32]),
+    "mkckks_lagrange_at_zero": (_int, [_vp, _vp, _u32, _vp]),
     "mkckks_encrypt_batch": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32]),
     "mkckks_lift_ntt_batch": (_int, [_vp, _vp, _vp, _u32, _u32]),
     "mkckks_decrypt_batch": (_int, [_vp, _vp, _vp, _vp, _u32, _u32]),
@@ -519,3 +522,25 @@ class Context:
     def fuse_shares(self, shares, m, n_parties, n_ct, nl):
         """m = sum of shares[p] (MultipartyDecryptFusion), in the layout of `decrypt`; m may be shares[0]."""
         self._check(self._L.mkckks_fuse_shares_batch(self._h, _ptr(shares), _ptr(m), n_parties, n_ct, nl))
+
+    # ---- t-of-n threshold decryption (include/mkckks.h: "t-of-n threshold decryption")
+    def share_key(self, sk, shares, nl, n_parties, threshold, key, stream_id=0):
+        """shares[p] = sk + sum_{k=1}^{t-1} r_k (p + 1)^k mod q_i on the first nl limbs: the dealer's Shamir sharing of its
+        key; r_k = sample_uniform(1, nl, 0, key, stream_id + k - 1), never written.  `key`: a fresh 32-byte key per call."""
+        self._check(self._L.mkckks_share_key(self._h, _ptr(sk), _ptr(shares), nl, n_parties, threshold, sampler_key(key),
+                                             stream_id))
+
+    def combine_key_shares(self, inp, weights, out, m, nl):
+        """out = sum_j weights[j][i] * inp[j][i] mod q_i over m polynomials u64[nl][N]; `weights`: host u64[m][nl] below
+        their moduli; out may be inp."""
+        w = np.ascontiguousarray(weights, dtype=np.uint64)
+        if w.size != m * nl:
+            raise ValueError("combine_key_shares: need one weight per input and limb")
+        self._check(self._L.mkckks_combine_key_shares(self._h, _ptr(inp), w.ctypes.data, _ptr(out), m, nl))
+
+    def lagrange_at_zero(self, parties):
+        """Lagrange coefficients at 0 of the 1-based party indices `parties`: uint64[len(parties)][L] (host only)."""
+        p = np.ascontiguousarray(parties, dtype=np.uint32)
+        out = np.zeros((p.size, self.L), dtype=np.uint64)
+        self._check(self._L.mkckks_lagrange_at_zero(self._h, p.ctypes.data, p.size, out.ctypes.data))
+        return out

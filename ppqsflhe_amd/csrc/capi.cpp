@@ -47,6 +47,10 @@ int guarded(F &&f) {
     }
 }
 
+// one bound on the number of parties, three names: the header's, the sharing kernel's and the Lagrange arithmetic's
+static_assert(MKCKKS_MAX_PARTIES == mk::SHAMIR_MAX_PARTIES && MKCKKS_MAX_PARTIES == mk::ParamSet::LAGRANGE_MAX_PARTIES,
+              "MKCKKS_MAX_PARTIES, SHAMIR_MAX_PARTIES and LAGRANGE_MAX_PARTIES must agree");
+
 void need(bool ok, const char *what) {
     if (!ok) throw std::invalid_argument(what);
 }
@@ -507,6 +511,45 @@ int mkckks_fuse_shares_batch(mkckks_ctx *c, const uint64_t *shares, uint64_t *m,
         }
         if (!n_ct) return;
         c->eng->fuse_shares(shares, m, n_parties, n_ct, nl);
+    });
+}
+int mkckks_share_key(mkckks_ctx *c, const uint64_t *sk, uint64_t *shares, uint32_t nl, uint32_t n_parties, uint32_t threshold,
+                     const uint8_t *h_key32, uint32_t stream_id) {
+    return guarded([&] {
+        need(c && sk && shares && h_key32, "null argument");
+        const mk::ParamSet &ps = c->eng->params();
+        need(nl >= 1 && nl <= ps.L, "nl out of range");
+        need(threshold >= 1 && threshold <= n_parties && n_parties <= MKCKKS_MAX_PARTIES,
+             "need 1 <= threshold <= n_parties <= MKCKKS_MAX_PARTIES");
+        need((uint64_t)stream_id + threshold - 1 <= 0xFFFFFFFFull, "stream ids overflow 32 bits");
+        const size_t limb_bytes = (size_t)ps.n * sizeof(uint64_t);  // addresses only; the first nl limbs of sk are read
+        const uintptr_t i_lo = (uintptr_t)sk, i_hi = i_lo + limb_bytes * nl;
+        const uintptr_t o_lo = (uintptr_t)shares, o_hi = o_lo + limb_bytes * nl * n_parties;
+        need(!(o_lo < i_hi && i_lo < o_hi), "shares overlap the key");
+        c->eng->share_key(sk, shares, nl, n_parties, threshold, h_key32, stream_id);
+    });
+}
+int mkckks_combine_key_shares(mkckks_ctx *c, const uint64_t *in, const uint64_t *h_w, uint64_t *out, uint32_t m, uint32_t nl) {
+    return guarded([&] {
+        need(c && in && h_w && out, "null argument");
+        const mk::ParamSet &ps = c->eng->params();
+        need(m >= 1, "need m >= 1");
+        need(nl >= 1 && nl <= ps.L, "nl out of range");
+        for (uint32_t j = 0; j < m; ++j)
+            for (uint32_t i = 0; i < nl; ++i) need(h_w[(size_t)j * nl + i] < ps.moduli[i], "weight not below its modulus");
+        if (out != in) {  // in[0] is the one allowed alias; addresses only
+            const size_t poly_bytes = (size_t)nl * ps.n * sizeof(uint64_t);
+            const uintptr_t i_lo = (uintptr_t)in, i_hi = i_lo + poly_bytes * m;
+            const uintptr_t o_lo = (uintptr_t)out, o_hi = o_lo + poly_bytes;
+            need(!(o_lo < i_hi && i_lo < o_hi), "output overlaps the inputs");
+        }
+        c->eng->combine_key_shares(in, h_w, out, m, nl);
+    });
+}
+int mkckks_lagrange_at_zero(const mkckks_ctx *c, const uint32_t *h_parties, uint32_t n_active, uint64_t *h_out) {
+    return guarded([&] {
+        need(c && h_parties && h_out, "null argument");
+        c->eng->params().lagrange_at_zero(h_parties, n_active, h_out);
     });
 }
 int mkckks_reduce_mod_batch(mkckks_ctx *c, uint64_t *ct, uint32_t n_ct, uint32_t nl, uint32_t n_terms) {

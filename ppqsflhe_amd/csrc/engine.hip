@@ -163,6 +163,33 @@ __global__ void k_sum(const u64 *in, u64 *out, EwGeom g, const LimbConst *limb, 
     st2(out + off, r);
 }
 
+// out[slot] (+)= sum_{j < cnt} w[j][slot - slot0] * in[j][slot] over Q limbs slot0 + blockIdx.y (slot == limb id), one
+// polynomial u64[nl][N] per input (combine_key_shares).  Weights: canonical residues by value in the kernel arguments,
+// WSUM_IN inputs x WSUM_LIMBS limbs per launch (2 KiB); further inputs accumulate into `out`.  Every term is mul_mod
+// of two canonical residues, summed canonically.  A thread reads its words of every input (and of `out` when it
+// accumulates) before it writes them: out may be in[0].
+constexpr uint32_t WSUM_IN = 16, WSUM_LIMBS = 16;
+struct WsumTable {
+    u64 w[WSUM_IN][WSUM_LIMBS];
+};
+__global__ void k_wsum(const u64 *in, u64 *out, EwGeom g, const LimbConst *limb, uint32_t slot0, uint32_t cnt,
+                       size_t in_stride, int accumulate, WsumTable t) {
+    const uint32_t ls = blockIdx.y, slot = slot0 + ls;
+    const uint32_t idx = (blockIdx.x * EW_THREADS + threadIdx.x) * 2;
+    if (idx >= g.n) return;
+    const LimbConst lc = limb[slot];
+    const size_t off = (size_t)slot * g.n + idx;
+    ulong2 r{0, 0};
+    if (accumulate) r = ld2(out + off);
+    for (uint32_t j = 0; j < cnt; ++j) {
+        const ulong2 v = ld2(in + (size_t)j * in_stride + off);
+        const u64 w = t.w[j][ls];
+        r.x = add_mod(r.x, mul_mod(v.x, w, lc), lc.q);
+        r.y = add_mod(r.y, mul_mod(v.y, w, lc), lc.q);
+    }
+    st2(out + off, r);
+}
+
 // in-place word-wise reduction after an integer-sum collective
 __global__ void k_reduce(u64 *ct, EwGeom g, const LimbConst *limb, uint32_t slots) {
     EW_PROLOGUE(slots)
@@ -2304,6 +2331,27 @@ void Engine::fuse_shares(const u64 *shares, u64 *m, uint32_t n_parties, uint32_t
     MK_HIP(hipGetLastError());
 }
 
+void Engine::combine_key_shares(const u64 *in, const u64 *w, u64 *out, uint32_t m, uint32_t nl) {
+    need_device();
+    check_nl(nl);
+    if (!m) throw std::invalid_argument("need m >= 1");
+    EwGeom g{ps_.n, nl, ps_.L};
+    const size_t poly = (size_t)nl * ps_.n;
+    for (uint32_t l0 = 0; l0 < nl; l0 += WSUM_LIMBS) {
+        const uint32_t lcnt = std::min(WSUM_LIMBS, nl - l0);
+        for (uint32_t j0 = 0; j0 < m; j0 += WSUM_IN) {
+            const uint32_t cnt = std::min(WSUM_IN, m - j0);
+            WsumTable t{};
+            for (uint32_t j = 0; j < cnt; ++j)
+                for (uint32_t i = 0; i < lcnt; ++i) t.w[j][i] = w[(size_t)(j0 + j) * nl + l0 + i];
+            // the first chunk of a limb reads in[0] before it writes out, the later ones add to out: out may be in[0]
+            k_wsum<<<ew_grid(ps_.n, lcnt, 1), EW_THREADS, 0, stream_>>>(in + (size_t)j0 * poly, out, g, d_limb_, l0, cnt, poly,
+                                                                        j0 != 0, t);
+            MK_HIP(hipGetLastError());
+        }
+    }
+}
+
 // ---- randomness ------------------------------------------------------------------------------------
 
 static ChaChaKey load_key(const uint8_t *key32) {
@@ -2369,6 +2417,20 @@ void Engine::sample_uniform(u64 *out, uint32_t items, uint32_t nl, bool with_p, 
     if (!items) return;
     const uint32_t slots = nl + (with_p ? ps_.K : 0);
     k_sample_uniform<<<dim3((ps_.n + 255) / 256, slots, items), 256, 0, stream_>>>(out, ps_.n, nl, ps_.L, d_limb_, key, sid);
+    MK_HIP(hipGetLastError());
+}
+
+void Engine::share_key(const u64 *sk, u64 *shares, uint32_t nl, uint32_t n_parties, uint32_t threshold, const uint8_t *key32,
+                       uint32_t sid0) {
+    need_device();
+    check_nl(nl);
+    const ChaChaKey key = load_key(key32);
+    if (threshold < 1 || threshold > n_parties || n_parties > SHAMIR_MAX_PARTIES)
+        throw std::invalid_argument("need 1 <= threshold <= n_parties <= 64");
+    if ((uint64_t)sid0 + threshold - 1 > 0xFFFFFFFFull) throw std::invalid_argument("stream ids overflow 32 bits");
+    const uint32_t n = ps_.n, groups = (n_parties + SHAMIR_GROUP - 1) / SHAMIR_GROUP;
+    k_shamir_share<<<dim3((n / 8 + 255) / 256, nl, groups), 256, 0, stream_>>>(sk, shares, n, nl, n_parties, threshold, d_limb_,
+                                                                               key, sid0);
     MK_HIP(hipGetLastError());
 }
 

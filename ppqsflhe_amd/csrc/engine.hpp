@@ -14,6 +14,8 @@
 
 namespace mk {
 
+constexpr uint32_t SHAMIR_MAX_PARTIES = 64;  // parties of one key sharing: MKCKKS_MAX_PARTIES (capi.cpp asserts it)
+
 struct HipError : std::runtime_error {
     using std::runtime_error::runtime_error;
 };
@@ -150,6 +152,12 @@ public:
     void partial_decrypt(const u64 *ct, const u64 *sk, const int64_t *e, u64 *share, uint32_t n_ct, uint32_t nl_in,
                          uint32_t nl, bool lead);
     void fuse_shares(const u64 *shares, u64 *m, uint32_t n_parties, uint32_t n_ct, uint32_t nl);
+    // t-of-n sharing of a key.  share_key: shares u64[n_parties][nl][N], share p = sk + sum_{k=1}^{t-1} r_k (p+1)^k mod q_i
+    // with r_k = sample_uniform(1 poly, nl, Q only) of stream (key32, sid0 + k - 1), never written to memory.
+    // combine_key_shares: out u64[nl][N] = sum_{j<m} w[j][i] * in[j][i] mod q_i; w HOST u64[m][nl], canonical; out may be in[0]
+    void share_key(const u64 *sk, u64 *shares, uint32_t nl, uint32_t n_parties, uint32_t threshold, const uint8_t *key32,
+                   uint32_t sid0);
+    void combine_key_shares(const u64 *in, const u64 *w, u64 *out, uint32_t m, uint32_t nl);
     void lift_ntt(const double *coef, u64 *out, uint32_t n, uint32_t nl);
     void decrypt(const u64 *ct, const u64 *sk, u64 *m, uint32_t n_ct, uint32_t nl);
     // counter-based samplers (ChaCha20 block function under a 256-bit key): element i of stream sid is a pure

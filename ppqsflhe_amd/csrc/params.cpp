@@ -306,4 +306,27 @@ std::vector<u64> ParamSet::const_factors(uint32_t nl, uint32_t level, double ope
     return out;
 }
 
+void ParamSet::lagrange_at_zero(const uint32_t *parties, uint32_t n_active, u64 *out) const {
+    if (!n_active || n_active > LAGRANGE_MAX_PARTIES) throw std::invalid_argument("lagrange: need 1 <= n_active <= 64");
+    unsigned long long seen = 0;
+    for (uint32_t a = 0; a < n_active; ++a) {
+        const uint32_t j = parties[a];
+        if (j < 1 || j > LAGRANGE_MAX_PARTIES) throw std::invalid_argument("lagrange: party index outside [1, 64]");
+        if (seen >> (j - 1) & 1) throw std::invalid_argument("lagrange: duplicate party index");
+        seen |= 1ull << (j - 1);
+    }
+    for (uint32_t a = 0; a < n_active; ++a)
+        for (uint32_t l = 0; l < L; ++l) {
+            const u64 q = moduli[l], j = parties[a];
+            u64 num = 1, den = 1;  // prod m, prod (m - j) over the other members; indices <= 64 < q
+            for (uint32_t b = 0; b < n_active; ++b) {
+                if (b == a) continue;
+                const u64 m = parties[b];
+                num = h_mulmod(num, m, q);
+                den = h_mulmod(den, m > j ? m - j : q - (j - m), q);
+            }
+            out[(size_t)a * L + l] = h_mulmod(num, h_invmod(den, q), q);
+        }
+}
+
 }  // namespace mk

@@ -69,6 +69,11 @@ struct ParamSet {
     u64 q_inv_mod(uint32_t l, uint32_t i) const;
     // LeveledSHECKKSRNS::GetElementForEvalMult
     std::vector<u64> const_factors(uint32_t nl, uint32_t level, double operand) const;
+    // Lagrange coefficients at 0 of the 1-based evaluation points parties[0..n_active): out[a][l] =
+    // prod_{m in set, m != parties[a]} m (m - parties[a])^-1 mod q_l over the L limbs of Q.  Indices outside
+    // [1, LAGRANGE_MAX_PARTIES], a duplicate and an empty set throw std::invalid_argument
+    static constexpr uint32_t LAGRANGE_MAX_PARTIES = 64;
+    void lagrange_at_zero(const uint32_t *parties, uint32_t n_active, u64 *out) const;
 };
 
 }  // namespace mk

@@ -196,6 +196,50 @@ __global__ __launch_bounds__(256) void k_expand_seeded(u64 *ct, uint32_t n, uint
     for (int k = 0; k < 4; ++k) *reinterpret_cast<ulong2 *>(dst + 2 * k) = ulong2{w[2 * k], w[2 * k + 1]};
 }
 
+// ---- t-of-n key sharing (mkckks_share_key): share[p] = sk + sum_{k=1}^{t-1} r_k (p+1)^k mod q_i ----------------------
+// r_k is the polynomial of stream (key, sid0 + k - 1) in the seeded-ciphertext definition above (uniform_block8), and
+// it exists in registers only: r_k together with one share gives sk away, so the coefficient polynomials never reach
+// HBM.  One lane = one ChaCha20 block = 8 consecutive coefficients of one limb; blockIdx.z = a group of SHAMIR_GROUP
+// parties, each with its own 8 accumulator words (64 words a lane); the blocks are recomputed per group.  Horner from
+// k = t - 1 down to 1: acc = (acc + r_k) * x, x = p + 1 <= 64 (the group's tail past n_parties is computed and not
+// stored) -- mul_mod's product stays below 2^(k+7), exact for fp64-class and 60-bit limbs alike.  Per party the 64 B of
+// a lane go out as four 16-B stores: a wave writes 4 KiB, whole lines.
+constexpr uint32_t SHAMIR_GROUP = 8;
+__global__ __launch_bounds__(256) void k_shamir_share(const u64 *sk, u64 *shares, uint32_t n, uint32_t nl, uint32_t n_parties,
+                                                      uint32_t threshold, const LimbConst *limb, ChaChaKey key, uint32_t sid0) {
+    const uint32_t slot = blockIdx.y, j8 = blockIdx.x * blockDim.x + threadIdx.x, p0 = blockIdx.z * SHAMIR_GROUP;
+    if (j8 >= n / 8) return;
+    const LimbConst lc = limb[slot];
+    const uint64_t b = (uint64_t)slot * (n / 8) + j8;
+    u64 acc[SHAMIR_GROUP][8];
+#pragma unroll
+    for (uint32_t g = 0; g < SHAMIR_GROUP; ++g)
+#pragma unroll
+        for (int w = 0; w < 8; ++w) acc[g][w] = 0;
+#pragma unroll 1
+    for (uint32_t k = threshold - 1; k >= 1; --k) {
+        u64 r[8];
+        uniform_block8(key, sid0 + (k - 1), b, lc, r);
+#pragma unroll
+        for (uint32_t g = 0; g < SHAMIR_GROUP; ++g)
+#pragma unroll
+            for (int w = 0; w < 8; ++w) acc[g][w] = mul_mod(add_mod(acc[g][w], r[w], lc.q), (u64)(p0 + g + 1), lc);
+    }
+    const size_t off = (size_t)slot * n + (size_t)j8 * 8;
+    ulong2 s[4];
+#pragma unroll
+    for (int w = 0; w < 4; ++w) s[w] = *reinterpret_cast<const ulong2 *>(sk + off + 2 * w);
+#pragma unroll
+    for (uint32_t g = 0; g < SHAMIR_GROUP; ++g) {
+        if (p0 + g >= n_parties) break;  // wave-uniform
+        u64 *dst = shares + (size_t)(p0 + g) * nl * n + off;
+#pragma unroll
+        for (int w = 0; w < 4; ++w)
+            *reinterpret_cast<ulong2 *>(dst + 2 * w) =
+                ulong2{add_mod(acc[g][2 * w], s[w].x, lc.q), add_mod(acc[g][2 * w + 1], s[w].y, lc.q)};
+    }
+}
+
 // secret-key encryption with a seeded a: c0 = pt + ee - a*s mod q_i (the products of k_fma: mul_mod), where item t's a is
 // stream (key, sid0 + t); pt, ee, c0 u64[n_items][nl][N], s u64[.][N] (first nl limbs)
 __global__ __launch_bounds__(256) void k_encrypt_seeded(const u64 *pt, const u64 *ee, const u64 *s, u64 *c0, uint32_t n,
