@@ -169,6 +169,40 @@ int mkckks_reencrypt_accumulate_batch(mkckks_ctx *c, const uint64_t *d_ct, const
  * adding them in any order; the last ModDown pass of all clients and the sum are one kernel. */
 int mkckks_reencrypt_sum_batch(mkckks_ctx *c, const uint64_t *d_cts, const uint64_t *d_evks, uint64_t *d_out,
                                uint32_t n_clients, uint32_t n_ct, uint32_t nl);
+/* ---- weighted aggregation: sum_c w_c * x_c in place of the plain mean -----------------------------------------------
+ * The weighted form of the server loop (ReEncrypt x n, then per client cc->EvalMult(ct, w_c) as at
+ * aggregateEncryptedWeights.cpp:82-83, then the EvalAdd chain), with the weights folded into what the merged n-client
+ * flow already reads.  M_c = trunc(h_weights[c] * sf(sf_level) + 0.5), the 128-bit integer of EvalMult(ct, w_c), reduced
+ * modulo whichever limb it meets.  Hybrid key switching is linear in the key, so
+ *   M_c * ReEncrypt(ct_c, evk_c) ~ ReEncrypt((M_c * c0_c, c1_c), M_c * evk_c)      (equal up to ApproxModDown's rounding)
+ * and the weighted sum is DEFINED as the right-hand side, summed over the clients, followed by ONE mkckks_rescale_batch:
+ * the rescale's rounding error is not multiplied by the 2^p-sized constant as it is in rescale-then-EvalMult.
+ * sf_level: for noiseScaleDeg-2 inputs at level = L - nl pass level + 1 and rescale afterwards -- the result has the
+ * limbs, level, scale (S_in / q_{nl-1} * sf(level + 1)) and noiseScaleDeg (2) of mkckks_rescale_mult_const_batch(sum, .);
+ * for noiseScaleDeg-1 inputs pass level and do not rescale (the bookkeeping of mkckks_mult_const_batch).
+ * Headroom: before the rescale the encrypted coefficients are about S_in * sf(sf_level) * |sum_c w_c v_c|, which must
+ * stay below q_0 * ... * q_{nl-1} / 2, as in the compact-leg rule below: log2(S_in * sf(sf_level)) <
+ * log2(q_0 ... q_{nl-1}) - 1 leaves room for |values| <= 1 and no more.  The library cannot check it.
+ * All three: h_weights are HOST doubles, read before the call returns; a weight that is not finite or whose constant
+ * does not fit 125 bits -> MKCKKS_E_INVALID; a zero count is a no-op; host-only context -> MKCKKS_E_NODEVICE.  The
+ * constant tables are cached on the device per (weights, sf_level): a step that repeats them uploads nothing.
+ *
+ * (aggregateEncryptedWeights.cpp:82-83) d_evk_out[k] = M_k * d_evk_in[k] on all D limbs (Q and P) of n_keys eval keys
+ * u64[n_keys][beta][2][D][N].  Once per (key, weight, level).  d_evk_out must not overlap d_evk_in (MKCKKS_E_INVALID). */
+int mkckks_scale_evk_batch(mkckks_ctx *c, const uint64_t *d_evk_in, uint64_t *d_evk_out, uint32_t n_keys,
+                           const double *h_weights, uint32_t sf_level);
+/* (aggregateEncryptedWeights.cpp:82-83) d_out[b] = sum_c ReEncrypt((M_c * c0_c[b], c1_c[b]), d_evks_scaled[c]): layouts
+ * of mkckks_reencrypt_sum_batch; d_evks_scaled = mkckks_scale_evk_batch of the clients' keys with the SAME weights and
+ * level (a key scaled with other weights gives a wrong aggregate and no error).  d_out has nl limbs and is not yet
+ * rescaled; it must not overlap d_cts.  Bit-identical to the per-client chain on the scaled inputs. */
+int mkckks_reencrypt_wsum_batch(mkckks_ctx *c, const uint64_t *d_cts, const uint64_t *d_evks_scaled, uint64_t *d_out,
+                                uint32_t n_clients, uint32_t n_ct, uint32_t nl, const double *h_weights, uint32_t sf_level);
+/* (aggregateEncryptedWeights.cpp:82-83) d_out[b] = sum_k M_k * d_in[k][b], d_in u64[n_terms][n_ct][2][nl][N]: the
+ * in-domain clients, EvalMult(ct, w_k) and the EvalAdd chain in one pass.  first_is_sum != 0: term 0 is added as it is
+ * (the slot mkckks_reencrypt_wsum_batch wrote) and h_weights[0] is ignored.  d_out may be term 0 itself and must not
+ * overlap d_in otherwise. */
+int mkckks_eval_wsum_batch(mkckks_ctx *c, const uint64_t *d_in, uint64_t *d_out, uint32_t n_terms, uint32_t n_ct, uint32_t nl,
+                           const double *h_weights, uint32_t sf_level, int first_is_sum);
 /* fan-out form of the distribution leg (orchestration/server_fns.sh:76-80: changeCipherDomain.cpp:74 run n-1 times
  * on ONE input file, once per client key): d_out[k][b] = ReEncrypt(d_ct[b], d_evks[k]).
  * d_ct u64[n_ct][2][nl][N] (read-only), d_evks u64[n_keys][beta][2][D][N] (layout of mkckks_reencrypt_sum_batch),

@@ -74,6 +74,9 @@ SYMBOLS = {
     "mkckks_reencrypt_accumulate_batch": (_int, [_vp, _vp, _vp, _vp, _u32, _u32]),
     "mkckks_reencrypt_sum_batch": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u32]),
     "mkckks_reencrypt_fanout_batch": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u32]),
+    "mkckks_scale_evk_batch": (_int, [_vp, _vp, _vp, _u32, _vp, _u32]),
+    "mkckks_reencrypt_wsum_batch": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _u32]),
+    "mkckks_eval_wsum_batch": (_int, [_vp, _vp, _vp, _u32, _u32, _u32, _vp, _u32, _int]),
     "mkckks_compress_batch": (_int, [_vp, _vp, _vp, _u32, _u32, _u32]),
     "mkckks_reencrypt_fanout_compact_batch": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32]),
     "mkckks_modup_batch": (_int, [_vp, _vp, _vp, _u32, _u32]),
@@ -408,6 +411,24 @@ class Context:
 
     def reencrypt_sum(self, cts, evks, out, n_clients, n_ct, nl):
         self._check(self._L.mkckks_reencrypt_sum_batch(self._h, _ptr(cts), _ptr(evks), _ptr(out), n_clients, n_ct, nl))
+
+    # weighted aggregation: weights are host doubles, M_k = trunc(w_k * sf(sf_level) + 0.5) (include/mkckks.h)
+    def scale_evk(self, evks, out, n_keys, weights, sf_level):
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        assert w.size == n_keys
+        self._check(self._L.mkckks_scale_evk_batch(self._h, _ptr(evks), _ptr(out), n_keys, w.ctypes.data, sf_level))
+
+    def reencrypt_wsum(self, cts, evks_scaled, out, n_clients, n_ct, nl, weights, sf_level):
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        assert w.size == n_clients
+        self._check(self._L.mkckks_reencrypt_wsum_batch(self._h, _ptr(cts), _ptr(evks_scaled), _ptr(out), n_clients, n_ct, nl,
+                                                        w.ctypes.data, sf_level))
+
+    def eval_wsum(self, inp, out, n_terms, n_ct, nl, weights, sf_level, first_is_sum=False):
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        assert w.size == n_terms
+        self._check(self._L.mkckks_eval_wsum_batch(self._h, _ptr(inp), _ptr(out), n_terms, n_ct, nl, w.ctypes.data, sf_level,
+                                                   int(first_is_sum)))
 
     def reencrypt_fanout(self, ct, evks, out, n_keys, n_ct, nl):
         """out[k][b] = ReEncrypt(ct[b], evks[k]): one ciphertext batch into n_keys key domains (ModUp shared)."""

@@ -306,6 +306,27 @@ int mkckks_reencrypt_sum_batch(mkckks_ctx *c, const uint64_t *cts, const uint64_
         c->eng->reencrypt_sum(cts, evks, out, n_clients, n_ct, nl);
     });
 }
+int mkckks_scale_evk_batch(mkckks_ctx *c, const uint64_t *d_evk_in, uint64_t *d_evk_out, uint32_t n_keys,
+                           const double *h_weights, uint32_t sf_level) {
+    return guarded([&] {
+        need(c && (n_keys == 0 || (d_evk_in && d_evk_out && h_weights)), "null argument");
+        c->eng->scale_evk(d_evk_in, d_evk_out, n_keys, h_weights, sf_level);
+    });
+}
+int mkckks_reencrypt_wsum_batch(mkckks_ctx *c, const uint64_t *d_cts, const uint64_t *d_evks_scaled, uint64_t *d_out,
+                                uint32_t n_clients, uint32_t n_ct, uint32_t nl, const double *h_weights, uint32_t sf_level) {
+    return guarded([&] {
+        need(c && ((n_clients == 0 || n_ct == 0) || (d_cts && d_evks_scaled && d_out && h_weights)), "null argument");
+        c->eng->reencrypt_wsum(d_cts, d_evks_scaled, d_out, n_clients, n_ct, nl, h_weights, sf_level);
+    });
+}
+int mkckks_eval_wsum_batch(mkckks_ctx *c, const uint64_t *d_in, uint64_t *d_out, uint32_t n_terms, uint32_t n_ct, uint32_t nl,
+                           const double *h_weights, uint32_t sf_level, int first_is_sum) {
+    return guarded([&] {
+        need(c && ((n_terms == 0 || n_ct == 0) || (d_in && d_out && h_weights)), "null argument");
+        c->eng->eval_wsum(d_in, d_out, n_terms, n_ct, nl, h_weights, sf_level, first_is_sum != 0);
+    });
+}
 int mkckks_reencrypt_fanout_batch(mkckks_ctx *c, const uint64_t *ct, const uint64_t *evks, uint64_t *out, uint32_t n_keys,
                                   uint32_t n_ct, uint32_t nl) {
     return guarded([&] {

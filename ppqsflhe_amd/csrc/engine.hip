@@ -190,6 +190,74 @@ __global__ void k_wsum(const u64 *in, u64 *out, EwGeom g, const LimbConst *limb,
     st2(out + off, r);
 }
 
+// Weight tables of the weighted aggregation (Engine::weight_table): entry (k, limb id) = 4 words
+// { M_k mod q, Shoup companion, [P M_k mod q] as a double, that / q } -- the doubles on fp64-class Q limbs only.
+constexpr uint32_t WT_WORDS = 4;
+
+// out[key][j][comp][limb] = (M_key mod m_limb) * in[key][j][comp][limb] on all D limbs of an eval key u64[beta][2][D][N]:
+// grid (N / 512, D, n_keys * beta * 2), one limb per workgroup, streamed once (non-temporal both ways).
+__global__ void k_scale_keys(const u64 *in, u64 *out, uint32_t n, uint32_t D, uint32_t polys_per_key, const LimbConst *limb,
+                             const u64 *wt) {
+    const uint32_t l = blockIdx.y, poly = blockIdx.z;
+    const uint32_t idx = (blockIdx.x * EW_THREADS + threadIdx.x) * 2;
+    if (idx >= n) return;
+    const u64 q = limb[l].q;
+    const u64 *w = wt + ((size_t)(poly / polys_per_key) * D + l) * WT_WORDS;
+    const u64 f = w[0], f_sh = w[1];
+    const size_t off = ((size_t)poly * D + l) * n + idx;
+    ulong2 v = ld_stream2(reinterpret_cast<const ulong2 *>(in + off));
+    v.x = shoup_mul(v.x, f, f_sh, q);
+    v.y = shoup_mul(v.y, f, f_sh, q);
+    st_stream2(reinterpret_cast<ulong2 *>(out + off), v);
+}
+
+// out[item] = (M mod q) * c0 of in[item], c1 copied: the input of the per-client weighted re-encryption on the shapes
+// outside the merged flow.  in / out u64[items][2][nl][N]; w = the client's row of the weight table.
+__global__ void k_scale_c0(const u64 *in, u64 *out, EwGeom g, const LimbConst *limb, const u64 *w) {
+    EW_PROLOGUE(2 * g.nl)
+    const size_t off = ((size_t)item * 2 * g.nl + slot) * g.n + idx;
+    ulong2 v = ld_stream2(reinterpret_cast<const ulong2 *>(in + off));
+    if (slot < g.nl) {
+        const u64 q = limb[slot].q, f = w[slot * WT_WORDS], f_sh = w[slot * WT_WORDS + 1];
+        v.x = shoup_mul(v.x, f, f_sh, q);
+        v.y = shoup_mul(v.y, f, f_sh, q);
+    }
+    st2(out + off, v);
+}
+
+// out[item][slot] = sum_k (M_k mod q) * in[k][item][slot]: weighted n-ary EvalAdd, one pass over the n inputs and one
+// write.  Every product is canonical (< q < 2^61), as is term 0 when it enters as it is (first_is_sum), so the u64 sums
+// are reduced every 4 terms like k_sum's: 4 canonical terms + 1 reduced carry < 5 * 2^61 < 2^64.  A thread reads its
+// words of every input before it writes them: out may be term 0.
+__global__ void k_wsum_ct(const u64 *in, u64 *out, EwGeom g, const LimbConst *limb, uint32_t slots, uint32_t n_terms,
+                          size_t term_stride, const u64 *wt, uint32_t wt_limbs, int first_is_sum) {
+    EW_PROLOGUE(slots)
+    const uint32_t l = slot % g.nl;
+    const LimbConst lc = limb[l];
+    const size_t off = ((size_t)item * slots + slot) * g.n + idx;
+    u64 s0 = 0, s1 = 0;
+    uint32_t pending = 0;
+    for (uint32_t k = 0; k < n_terms; ++k) {
+        ulong2 v = ld_stream2(reinterpret_cast<const ulong2 *>(in + (size_t)k * term_stride + off));
+        if (k != 0 || !first_is_sum) {
+            const u64 *w = wt + ((size_t)k * wt_limbs + l) * WT_WORDS;
+            v.x = shoup_mul(v.x, w[0], w[1], lc.q);
+            v.y = shoup_mul(v.y, w[0], w[1], lc.q);
+        }
+        s0 += v.x;
+        s1 += v.y;
+        if (++pending == 4) {
+            s0 = reduce_word(s0, lc);
+            s1 = reduce_word(s1, lc);
+            pending = 1;
+        }
+    }
+    ulong2 r;
+    r.x = reduce_word(s0, lc);
+    r.y = reduce_word(s1, lc);
+    st_stream2(reinterpret_cast<ulong2 *>(out + off), r);
+}
+
 // in-place word-wise reduction after an integer-sum collective
 __global__ void k_reduce(u64 *ct, EwGeom g, const LimbConst *limb, uint32_t slots) {
     EW_PROLOGUE(slots)
@@ -646,6 +714,8 @@ Engine::~Engine() {
                     (void *)d_rot_, (void *)d_ksi_})
         if (p) (void)hipFree(p);
     for (void *p : owned_) (void)hipFree(p);
+    for (auto &kv : wt_cache_) (void)hipFree(kv.second);
+    if (wtmp_) (void)hipFree(wtmp_);
     if (up_stream_) {
         (void)hipStreamDestroy(up_stream_);
         (void)hipStreamDestroy(down_stream_);
@@ -1722,17 +1792,17 @@ void Engine::reencrypt_chunk(const u64 *ct, const u64 *evk, u64 *out, uint32_t c
     moddown_core(til, pc, conv, out, (size_t)nl * n, ct, ct_stride, 2 * cnt, nl, accumulate, p_rows);
 }
 
-template <int LOGC, int MINW>
+template <int LOGC, int MINW, bool W = false>
 static void launch_qsum3_fp(const QSumArgs &a, const NttTables &T, uint32_t nparts, hipStream_t s) {
     const uint32_t tiles = (1u << T.log_r1) / RowT<LOGC>::ROWS;
     const dim3 grid(tiles * a.nsel * a.cnt);
     switch (nparts) {
-        case 1: k_qsum3_fp<1, LOGC, MINW><<<grid, NTT_THREADS, 0, s>>>(a, T); break;
-        case 2: k_qsum3_fp<2, LOGC, MINW><<<grid, NTT_THREADS, 0, s>>>(a, T); break;
-        case 3: k_qsum3_fp<3, LOGC, MINW><<<grid, NTT_THREADS, 0, s>>>(a, T); break;
-        case 4: k_qsum3_fp<4, LOGC, MINW><<<grid, NTT_THREADS, 0, s>>>(a, T); break;
-        case 5: k_qsum3_fp<5, LOGC, MINW><<<grid, NTT_THREADS, 0, s>>>(a, T); break;
-        case 6: k_qsum3_fp<6, LOGC, MINW><<<grid, NTT_THREADS, 0, s>>>(a, T); break;
+        case 1: k_qsum3_fp<1, LOGC, MINW, W><<<grid, NTT_THREADS, 0, s>>>(a, T); break;
+        case 2: k_qsum3_fp<2, LOGC, MINW, W><<<grid, NTT_THREADS, 0, s>>>(a, T); break;
+        case 3: k_qsum3_fp<3, LOGC, MINW, W><<<grid, NTT_THREADS, 0, s>>>(a, T); break;
+        case 4: k_qsum3_fp<4, LOGC, MINW, W><<<grid, NTT_THREADS, 0, s>>>(a, T); break;
+        case 5: k_qsum3_fp<5, LOGC, MINW, W><<<grid, NTT_THREADS, 0, s>>>(a, T); break;
+        case 6: k_qsum3_fp<6, LOGC, MINW, W><<<grid, NTT_THREADS, 0, s>>>(a, T); break;
         default: throw std::invalid_argument("more than 6 key-switch digits unsupported");
     }
 }
@@ -1772,7 +1842,7 @@ bool Engine::qsum_ok(uint32_t nl) const {
 //   integer-class Q limbs (q_0): inner product, then row pass + tail + sum   k_row3_inner_int<.., false>, k_row3_tail_once
 //   fp64-class Q limbs: everything that is left, summed over clients        k_qsum3_fp
 void Engine::reencrypt_sum_merged(const u64 *cts, const u64 *evks, u64 *out, uint32_t n_clients, uint32_t n_ct,
-                                  uint32_t nl) {
+                                  uint32_t nl, const u64 *wt) {
     const uint32_t n = ps_.n, K = ps_.K, ext = nl + K, nparts = ps_.num_parts(nl), D = ps_.D;
     const size_t ct_words = (size_t)2 * nl * n, evk_words = (size_t)ps_.beta * 2 * D * n;
     const u64 *pinv = p_inverse(nl), *pq = p_doubles();
@@ -1844,10 +1914,19 @@ void Engine::reencrypt_sum_merged(const u64 *cts, const u64 *evks, u64 *out, uin
             if (n_intq) {  // q_0: row pass of the summed conversion, tail, sum over the group's clients
                 TailOnceArgs ta{convsum, til, ct0, out + (size_t)b0 * ct_words, pinv, pinv + nl,
                                 (size_t)cnt * 2 * n_intq * n, ct_cstride, ct_words, gc, nl, 2 * cnt, intq_mask, n_intq,
-                                g0 != 0 ? 1u : 0u};
+                                g0 != 0 ? 1u : 0u, wt ? wt + (size_t)g0 * D * WT_WORDS : nullptr, D};
                 const uint32_t tiles = (1u << tabs_.log_r1) / (wide_rows ? RowT<3>::ROWS : RowT<2>::ROWS);
                 const dim3 grid(tiles * n_intq * 2 * cnt);
-                if (wide_rows) with_int_arith(tabs_, [&](auto ar) {
+                if (wt) {  // weighted: M_c * c0 per client
+                    if (wide_rows) with_int_arith(tabs_, [&](auto ar) {
+                        k_row3_tail_once<3, decltype(ar)::value, true>
+                            <<<grid, NTT_THREADS, 0, main>>>(ta, tabs_);
+                    });
+                    else with_int_arith(tabs_, [&](auto ar) {
+                        k_row3_tail_once<2, decltype(ar)::value, true>
+                            <<<grid, NTT_THREADS, 0, main>>>(ta, tabs_);
+                    });
+                } else if (wide_rows) with_int_arith(tabs_, [&](auto ar) {
                     k_row3_tail_once<3, decltype(ar)::value>
                         <<<grid, NTT_THREADS, 0, main>>>(ta, tabs_);
                 });
@@ -1857,11 +1936,15 @@ void Engine::reencrypt_sum_merged(const u64 *cts, const u64 *evks, u64 *out, uin
                 });
             }
             QSumArgs qa{dig, convsum, ct0, evk0, out + (size_t)b0 * ct_words, pq, ct_cstride, ct_words, evk_words, ct_words,
-                        gc, cnt, nl, ext, D, ps_.alpha, fp_mask, (uint32_t)__builtin_popcountll(fp_mask), g0 != 0 ? 1u : 0u};
+                        gc, cnt, nl, ext, D, ps_.alpha, fp_mask, (uint32_t)__builtin_popcountll(fp_mask), g0 != 0 ? 1u : 0u,
+                        wt ? wt + (size_t)g0 * D * WT_WORDS : nullptr};
             // 256-point rows: 2 workgroups per CU -- at N = 2^16, L = 12 the kernel's 5 632 workgroups then fill the 512 resident
             // slots exactly 11 times (7.33 times 768 at 3 per CU: a last round a third full) and nothing is parked in scratch;
             // +0.45 % on the step after the eval-key bursts (it was +-0 before them)
-            if (wide_rows) launch_qsum3_fp<3, 3>(qa, tabs_, nparts, main);
+            if (wt) {
+                if (wide_rows) launch_qsum3_fp<3, 3, true>(qa, tabs_, nparts, main);
+                else launch_qsum3_fp<2, 2, true>(qa, tabs_, nparts, main);
+            } else if (wide_rows) launch_qsum3_fp<3, 3>(qa, tabs_, nparts, main);
             else launch_qsum3_fp<2, 2>(qa, tabs_, nparts, main);
             MK_HIP(hipGetLastError());
         }
@@ -1874,7 +1957,7 @@ void Engine::reencrypt_sum(const u64 *cts, const u64 *evks, u64 *out, uint32_t n
     if (!n_clients || !n_ct) return;
     const size_t ct_words = (size_t)2 * nl * ps_.n, evk_words = (size_t)ps_.beta * 2 * ps_.D * ps_.n;
     if (qsum_ok(nl)) {  // N = 2^14, 2^16, 2^17 with fp64-class Q limbs: every phase one launch over all (client, index) items
-        reencrypt_sum_merged(cts, evks, out, n_clients, n_ct, nl);
+        reencrypt_sum_merged(cts, evks, out, n_clients, n_ct, nl, nullptr);
         return;
     }
     // other ring sizes / arithmetic classes: one re-encryption per client with the accumulating tail
@@ -1891,6 +1974,114 @@ void Engine::reencrypt(const u64 *ct, const u64 *evk, u64 *out, uint32_t n_ct, u
         const uint32_t cnt = n_ct - done < knobs_.chunk ? n_ct - done : knobs_.chunk;
         reencrypt_chunk(ct + done * ct_stride, evk, out + done * ct_stride, cnt, nl, accumulate);
     }
+}
+
+// ---- weighted aggregation ("weighted aggregation") -------------------------------------------------------
+
+// Device table of the constants M_k = trunc(w_k * sf(sf_level) + 0.5) over all D limbs, WT_WORDS words per (k, limb).
+// Cached per (sf_level, weights) like rescale_consts, so a server step that repeats its weights uploads nothing and no
+// call synchronises per chunk; the cache is small and emptied (after one stream synchronisation) when it is full, since
+// a long-running server sees new weights every round.
+const u64 *Engine::weight_table(const double *w, uint32_t n, uint32_t sf_level) {
+    if (!w) throw std::invalid_argument("null weights");
+    std::string key((const char *)w, (size_t)n * sizeof(double));
+    key += "@" + std::to_string(sf_level);
+    auto it = wt_cache_.find(key);
+    if (it != wt_cache_.end()) return it->second;
+    const uint32_t D = ps_.D;
+    std::vector<u64> t((size_t)n * D * WT_WORDS, 0);
+    for (uint32_t k = 0; k < n; ++k) {
+        const std::vector<u64> f = ps_.const_factors_qp(sf_level, w[k]);  // throws on a weight that does not fit
+        for (uint32_t i = 0; i < D; ++i) {
+            u64 *e = &t[((size_t)k * D + i) * WT_WORDS];
+            const u64 q = ps_.moduli[i];
+            e[0] = f[i];
+            e[1] = h_shoup(f[i], q);
+            if (i < ps_.L && ps_.limb[i].fp) {
+                const u64 pmw = h_mulmod(ps_.p_mod(i), f[i], q);
+                const double d[2] = {(double)pmw, (double)((long double)pmw / (long double)q)};
+                std::memcpy(e + 2, d, sizeof(d));
+            }
+        }
+    }
+    if (wt_cache_.size() >= 64) {
+        MK_HIP(hipStreamSynchronize(stream_));
+        for (auto &kv : wt_cache_) MK_HIP(hipFree(kv.second));
+        wt_cache_.clear();
+    }
+    u64 *d = nullptr;
+    MK_HIP(hipMalloc(&d, t.size() * sizeof(u64)));
+    wt_cache_[key] = d;
+    MK_HIP(hipMemcpy(d, t.data(), t.size() * sizeof(u64), hipMemcpyHostToDevice));
+    return d;
+}
+
+void Engine::scale_evk(const u64 *in, u64 *out, uint32_t n_keys, const double *w, uint32_t sf_level) {
+    need_device();
+    if (!n_keys) return;
+    const uint32_t n = ps_.n, D = ps_.D, polys_per_key = 2 * ps_.beta;
+    const size_t bytes = (size_t)n_keys * polys_per_key * D * n * sizeof(u64);
+    if (ranges_overlap(in, bytes, out, bytes)) throw std::invalid_argument("output overlaps input");
+    if ((size_t)n_keys * polys_per_key > 65535) throw std::invalid_argument("too many keys in one call");
+    const u64 *wt = weight_table(w, n_keys, sf_level);
+    k_scale_keys<<<dim3((n / 2 + EW_THREADS - 1) / EW_THREADS, D, n_keys * polys_per_key), EW_THREADS, 0, stream_>>>(
+        in, out, n, D, polys_per_key, d_limb_, wt);
+    MK_HIP(hipGetLastError());
+}
+
+// sum over clients of ReEncrypt((M_c * c0_c[b], c1_c[b]), evk'_c) with evk'_c = M_c * evk_c made by scale_evk from the
+// same weights and level
+void Engine::reencrypt_wsum(const u64 *cts, const u64 *evks_scaled, u64 *out, uint32_t n_clients, uint32_t n_ct, uint32_t nl,
+                            const double *w, uint32_t sf_level) {
+    need_device();
+    check_nl(nl);
+    if (!n_clients || !n_ct) return;
+    const size_t ct_words = (size_t)2 * nl * ps_.n, evk_words = (size_t)ps_.beta * 2 * ps_.D * ps_.n;
+    if (ranges_overlap(cts, (size_t)n_clients * n_ct * ct_words * sizeof(u64), out, (size_t)n_ct * ct_words * sizeof(u64)))
+        throw std::invalid_argument("output overlaps input");
+    const u64 *wt = weight_table(w, n_clients, sf_level);
+    if (qsum_ok(nl)) {
+        reencrypt_sum_merged(cts, evks_scaled, out, n_clients, n_ct, nl, wt);
+        return;
+    }
+    // other ring sizes / arithmetic classes: the composition, chunk by chunk -- c0 scaled into a buffer of its own (the
+    // re-encryption owns the workspace), then the accumulating re-encryption with the scaled key
+    const uint32_t chunk = std::min(knobs_.chunk, n_ct);
+    if ((size_t)chunk * ct_words > wtmp_words_) {
+        MK_HIP(hipStreamSynchronize(stream_));
+        if (wtmp_) MK_HIP(hipFree(wtmp_));
+        wtmp_ = nullptr;
+        wtmp_words_ = 0;
+        MK_HIP(hipMalloc(&wtmp_, (size_t)chunk * ct_words * sizeof(u64)));
+        wtmp_words_ = (size_t)chunk * ct_words;
+    }
+    EwGeom g{ps_.n, nl, ps_.L};
+    for (uint32_t c = 0; c < n_clients; ++c)
+        for (uint32_t b0 = 0; b0 < n_ct; b0 += chunk) {
+            const uint32_t cnt = std::min(chunk, n_ct - b0);
+            k_scale_c0<<<ew_grid(ps_.n, 2 * nl, cnt), EW_THREADS, 0, stream_>>>(
+                cts + ((size_t)c * n_ct + b0) * ct_words, wtmp_, g, d_limb_, wt + (size_t)c * ps_.D * WT_WORDS);
+            MK_HIP(hipGetLastError());
+            reencrypt_chunk(wtmp_, evks_scaled + (size_t)c * evk_words, out + (size_t)b0 * ct_words, cnt, nl, c != 0);
+        }
+}
+
+void Engine::eval_wsum(const u64 *in, u64 *out, uint32_t n_terms, uint32_t n_ct, uint32_t nl, const double *w,
+                       uint32_t sf_level, bool first_is_sum) {
+    need_device();
+    check_nl(nl);
+    if (!n_terms || !n_ct) return;
+    const size_t term_words = (size_t)n_ct * 2 * nl * ps_.n;
+    // a thread reads its words of every term before it writes them, so out may be term 0 itself; any other overlap is a race
+    if (out != in && ranges_overlap(in, (size_t)n_terms * term_words * sizeof(u64), out, term_words * sizeof(u64)))
+        throw std::invalid_argument("output overlaps input (it may only be term 0 itself)");
+    std::vector<double> ww(w, w + n_terms);
+    if (first_is_sum) ww[0] = 1.0;  // ignored by the kernel; keeps the cache key and the range check independent of it
+    const u64 *wt = weight_table(ww.data(), n_terms, sf_level);
+    EwGeom g{ps_.n, nl, ps_.L};
+    k_wsum_ct<<<ew_grid(ps_.n, 2 * nl, n_ct), EW_THREADS, 0, stream_>>>(in, out, g, d_limb_, 2 * nl, n_terms, term_words, wt,
+                                                                      ps_.D, first_is_sum ? 1 : 0);
+    MK_HIP(hipGetLastError());
 }
 
 // the three instances of the fused fan-out kernels over one chunk of ciphertexts and one group of keys

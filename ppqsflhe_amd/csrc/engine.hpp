@@ -119,6 +119,15 @@ public:
 
     // out[b] = sum over clients of ReEncrypt(cts[c][b], evks[c]); cts [C][n_ct][2][nl][N], evks [C][beta][2][D][N]
     void reencrypt_sum(const u64 *cts, const u64 *evks, u64 *out, uint32_t n_clients, uint32_t n_ct, uint32_t nl);
+    // weighted aggregation, M_k = trunc(w[k] * sf(sf_level) + 0.5) reduced per limb (w: HOST doubles, read before return):
+    //   scale_evk:      out[k] = M_k * in[k] on all D limbs; eval keys [n_keys][beta][2][D][N]; out must not overlap in
+    //   reencrypt_wsum: out[b] = sum_c ReEncrypt((M_c * cts[c][b].c0, cts[c][b].c1), evks_scaled[c]), layouts of reencrypt_sum
+    //   eval_wsum:      out[b] = sum_k M_k * in[k][b]; first_is_sum: term 0 enters as it is
+    void scale_evk(const u64 *in, u64 *out, uint32_t n_keys, const double *w, uint32_t sf_level);
+    void reencrypt_wsum(const u64 *cts, const u64 *evks_scaled, u64 *out, uint32_t n_clients, uint32_t n_ct, uint32_t nl,
+                        const double *w, uint32_t sf_level);
+    void eval_wsum(const u64 *in, u64 *out, uint32_t n_terms, uint32_t n_ct, uint32_t nl, const double *w, uint32_t sf_level,
+                   bool first_is_sum);
     // out[k][b] = ReEncrypt(ct[b], evks[k]): ModUp (and, on the fused path, the digits' row transforms) once per
     // ciphertext; ct [n_ct][2][nl][N] read-only, evks [n_keys][beta][2][D][N], out [n_keys][n_ct][2][nl][N]
     void reencrypt_fanout(const u64 *ct, const u64 *evks, u64 *out, uint32_t n_keys, uint32_t n_ct, uint32_t nl);
@@ -205,7 +214,10 @@ private:
     void modup_core(const u64 *c1, size_t c1_stride, u64 *coef, u64 *dig, uint32_t cnt, uint32_t nl,
                     bool rows_int_only = false, uint32_t in_group = 0, size_t in_gstride = 0);
     bool qsum_ok(uint32_t nl) const;
-    void reencrypt_sum_merged(const u64 *cts, const u64 *evks, u64 *out, uint32_t n_clients, uint32_t n_ct, uint32_t nl);
+    // wt: weight table of the clients (weighted instance of the two Q-limb kernels), nullptr: the plain sum
+    void reencrypt_sum_merged(const u64 *cts, const u64 *evks, u64 *out, uint32_t n_clients, uint32_t n_ct, uint32_t nl,
+                              const u64 *wt);
+    const u64 *weight_table(const double *w, uint32_t n, uint32_t sf_level);
     const u64 *p_doubles();
     // returns true when the inverse ROW pass of the P limbs was done on the fly into `pc` (ModDown then starts with
     // the inverse column pass)
@@ -256,6 +268,9 @@ private:
     std::map<std::pair<uint32_t, uint32_t>, DevConv> modup_cache_;
     std::map<uint32_t, DevConv> moddown_cache_;
     std::map<std::string, u64 *> vec_cache_;
+    std::map<std::string, u64 *> wt_cache_;  // weight_table
+    u64 *wtmp_ = nullptr;                    // reencrypt_wsum outside the merged flow: a chunk with c0 scaled
+    size_t wtmp_words_ = 0;
     std::vector<void *> owned_;
 };
 

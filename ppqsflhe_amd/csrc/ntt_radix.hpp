@@ -1857,8 +1857,13 @@ struct TailOnceArgs {
     unsigned long long slot_mask;
     uint32_t nsel;
     uint32_t init_from_out;  // continue a running sum held in `out` (client groups)
+    // weighted instance (W): client c, limb t at wt + (c * wt_limbs + t) * 4: M_c mod q_t and its Shoup companion
+    const u64 *wt;
+    uint32_t wt_limbs;
 };
-template <int LOGC, int AR>
+// W: weighted aggregation -- c0 of client c enters as M_c * c0 (canonical, so the cadence of the sums holds); the
+// accumulators come from eval keys already scaled by M_c
+template <int LOGC, int AR, bool W = false>
 __global__ __launch_bounds__(NTT_THREADS, 3) void k_row3_tail_once(TailOnceArgs a, NttTables T) {
     using TL = RowT<LOGC>;
     constexpr int R = TL::R, S = TL::ROWS, TPR = TL::TPR, PAIRS = 4;
@@ -1912,8 +1917,14 @@ __global__ __launch_bounds__(NTT_THREADS, 3) void k_row3_tail_once(TailOnceArgs 
                 const ulong2 zz = ld_stream2(reinterpret_cast<const ulong2 *>(
                                                  a.cts + (size_t)cl * a.ct_cstride + (size_t)(poly >> 1) * a.ct_stride +
                                                  (size_t)sl * n + tile_off) + e);
-                zx += zz.x;
-                zy += zz.y;
+                if (W) {
+                    const u64 *w = a.wt + ((size_t)cl * a.wt_limbs + sl) * 4;
+                    zx += shoup_mul(zz.x, w[0], w[1], lc.q);
+                    zy += shoup_mul(zz.y, w[0], w[1], lc.q);
+                } else {
+                    zx += zz.x;
+                    zy += zz.y;
+                }
             }
             if ((cl & 7) == 7) {
                 tx = reduce_word(tx, lc);

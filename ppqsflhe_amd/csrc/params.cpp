@@ -288,22 +288,41 @@ u64 ParamSet::p_mod(uint32_t id) const {
 u64 ParamSet::p_inv_mod(uint32_t id) const { return h_invmod(p_mod(id), moduli[id]); }
 u64 ParamSet::q_inv_mod(uint32_t l, uint32_t i) const { return h_invmod(moduli[l] % moduli[i], moduli[i]); }
 
-std::vector<u64> ParamSet::const_factors(uint32_t nl, uint32_t level, double operand) const {
-    // EvalMult(ct, double): integer constant = trunc(operand * sf(level) + 0.5) as a 128-bit integer
-    double scale = sf.at(level);
+// EvalMult(ct, double): integer constant = trunc(operand * scale + 0.5) as a 128-bit integer, reduced modulo the `count`
+// limbs from `first` on (indices into moduli)
+static std::vector<u64> const_residues(const std::vector<u64> &moduli, double scale, double operand, uint32_t first,
+                                       uint32_t count) {
     int log_sf = (int)std::ceil(std::log2(std::fabs(scale)));
     int log_approx = log_sf > 125 ? log_sf - 125 : 0;
     __int128 big = (__int128)(operand / std::pow(2.0, log_approx) * scale + 0.5);
-    std::vector<u64> out(nl);
-    for (uint32_t i = 0; i < nl; ++i) {
-        __int128 m = (__int128)moduli[i];
+    std::vector<u64> out(count);
+    for (uint32_t i = 0; i < count; ++i) {
+        const u64 q = moduli[first + i];
+        __int128 m = (__int128)q;
         __int128 r = big % m;
         if (r < 0) r += m;
         u64 f = (u64)r;
-        if (log_approx > 0) f = h_mulmod(f, h_powmod(2, (u64)log_approx, moduli[i]), moduli[i]);
+        if (log_approx > 0) f = h_mulmod(f, h_powmod(2, (u64)log_approx, q), q);
         out[i] = f;
     }
     return out;
+}
+
+std::vector<u64> ParamSet::const_factors(uint32_t nl, uint32_t level, double operand) const {
+    return const_residues(moduli, sf.at(level), operand, 0, nl);
+}
+
+bool ParamSet::const_fits(uint32_t level, double operand) const {
+    if (level >= sf.size() || !std::isfinite(operand)) return false;
+    const double scale = sf[level];
+    const int log_sf = (int)std::ceil(std::log2(std::fabs(scale)));
+    const double v = operand / std::pow(2.0, log_sf > 125 ? log_sf - 125 : 0) * scale;
+    return std::isfinite(v) && std::fabs(v) < std::ldexp(1.0, 125);
+}
+
+std::vector<u64> ParamSet::const_factors_qp(uint32_t level, double operand) const {
+    if (!const_fits(level, operand)) throw std::invalid_argument("weight is not finite or its constant does not fit 125 bits");
+    return const_residues(moduli, sf[level], operand, 0, D);
 }
 
 void ParamSet::lagrange_at_zero(const uint32_t *parties, uint32_t n_active, u64 *out) const {

@@ -69,6 +69,11 @@ struct ParamSet {
     u64 q_inv_mod(uint32_t l, uint32_t i) const;
     // LeveledSHECKKSRNS::GetElementForEvalMult
     std::vector<u64> const_factors(uint32_t nl, uint32_t level, double operand) const;
+    // the same integer reduced modulo all D limbs of QP (weighted aggregation: the constant meets the eval key's P
+    // limbs too); the first nl entries are const_factors(nl, level, operand).  Throws std::invalid_argument unless
+    // const_fits: operand finite and |operand * sf(level)| < 2^125 (the 128-bit conversion is undefined beyond)
+    std::vector<u64> const_factors_qp(uint32_t level, double operand) const;
+    bool const_fits(uint32_t level, double operand) const;
     // Lagrange coefficients at 0 of the 1-based evaluation points parties[0..n_active): out[a][l] =
     // prod_{m in set, m != parties[a]} m (m - parties[a])^-1 mod q_l over the L limbs of Q.  Indices outside
     // [1, LAGRANGE_MAX_PARTIES], a duplicate and an empty set throw std::invalid_argument

@@ -37,13 +37,19 @@ struct QSumArgs {
     unsigned long long slot_mask;  // fp64-class Q limbs
     uint32_t nsel;
     uint32_t init_from_out;  // continue a running sum held in `out` (client groups)
+    // weighted instance (W): client c, limb t at wt + (c * D + t) * 4: M_c mod q_t, its Shoup companion, and on fp64-class
+    // Q limbs the doubles P * M_c mod q_t and that / q_t (Engine::weight_table)
+    const u64 *wt;
 };
 
 // Three-round row geometry (RowT<LOGC>: 8 words per thread, 256-point rows as 8 x 8 x 4, 512-point rows as 8 x 8 x 8): the
 // accumulators are 32 registers, every twiddle of the limb's rows is staged once (rounds A, B in LDS, round C parked in
 // LDS too: MK_QSUM_PARK_C) instead of being re-read from L2 per transform, and the kernel runs 3 waves per SIMD.  (A
 // two-round form with 16 words per thread and 2 waves was 1.5 % slower and is gone.)
-template <int NPARTS, int LOGC, int MINW>
+// W: weighted aggregation -- the key-switch part runs unchanged on eval keys already scaled by M_c; c0 enters with
+// P * M_c mod q_t in place of P mod q_t, read per client (wave-uniform).  The running sum taken over from `out` is already
+// weighted: the prologue keeps the plain P.  The factor's size does not enter fp_mulmod's bound, so the sums grow as below.
+template <int NPARTS, int LOGC, int MINW, bool W = false>
 __global__ __launch_bounds__(NTT_THREADS, MINW) void k_qsum3_fp(QSumArgs a, NttTables T) {
     using TL = RowT<LOGC>;
     constexpr int R = TL::R, S = TL::ROWS, TPR = TL::TPR, PAIRS = 4;
@@ -133,6 +139,8 @@ __global__ __launch_bounds__(NTT_THREADS, MINW) void k_qsum3_fp(QSumArgs a, NttT
         const u64 *ct = a.cts + (size_t)cl * a.ct_cstride + (size_t)b * a.ct_stride + (size_t)sl * n + tile_off;
         const u64 *ek = a.evk + (size_t)cl * a.evk_cstride + (size_t)sl * n + tile_off;
         {
+            const u64 *wc0 = W ? a.wt + ((size_t)cl * a.D + sl) * 4 : nullptr;
+            const double pmc = W ? bitsd(wc0[2]) : pm, pmqc = W ? bitsd(wc0[3]) : pmq;
             const u64 *y1 = ct + (size_t)a.nl * n;
             const u64 *e0 = ek + ((size_t)own * 2 + 0) * a.D * n, *e1 = ek + ((size_t)own * 2 + 1) * a.D * n;
 #pragma unroll
@@ -143,8 +151,8 @@ __global__ __launch_bounds__(NTT_THREADS, MINW) void k_qsum3_fp(QSumArgs a, NttT
                 const ulong2 bb = reinterpret_cast<const ulong2 *>(e0)[e];
                 const ulong2 aa = reinterpret_cast<const ulong2 *>(e1)[e];
                 const double yx = u52_to_double(yy.x), yz = u52_to_double(yy.y);
-                acc0[i].x += fp_mulmod_any(yx, u52_to_double(bb.x), q, qinv) + fp_mulmod(u52_to_double(zz.x), pm, pmq, q);
-                acc0[i].y += fp_mulmod_any(yz, u52_to_double(bb.y), q, qinv) + fp_mulmod(u52_to_double(zz.y), pm, pmq, q);
+                acc0[i].x += fp_mulmod_any(yx, u52_to_double(bb.x), q, qinv) + fp_mulmod(u52_to_double(zz.x), pmc, pmqc, q);
+                acc0[i].y += fp_mulmod_any(yz, u52_to_double(bb.y), q, qinv) + fp_mulmod(u52_to_double(zz.y), pmc, pmqc, q);
                 acc1[i].x += fp_mulmod_any(yx, u52_to_double(aa.x), q, qinv);
                 acc1[i].y += fp_mulmod_any(yz, u52_to_double(aa.y), q, qinv);
                 if (NPARTS > 4 || ND == 0) {

@@ -6,10 +6,30 @@
 // matching ciphertext is summed with one mkckks_eval_sum_batch and scaled by 1/n_files.  (serverRound does the
 // re-encryptions and this aggregation in one program.)  Seeded inputs (encryptModelWeights --seeded) are accepted per
 // blob: c1 is rebuilt on the device before the sum.
+// --weights w_1,...,w_n (anywhere after <cc_path>): the weighted mean sum_c w_c x_c / sum_c w_c in place of the plain
+// one, one non-negative number per input file in argument order (sample counts as they are).  One
+// mkckks_eval_wsum_batch (EvalMult(ct, w_c) per file + the EvalAdd chain) and one rescale; the same bytes as serverRound
+// --weights with every client marked "-".
 #include "hostlib.hpp"
 using namespace mkh;
 
 int main(int argc, char *argv[]) {
+    std::string weights_text;
+    bool have_weights = false;
+    std::vector<char *> av(argv, argv + argc);
+    for (size_t i = 1; i < av.size(); ++i)
+        if (std::string(av[i]) == "--weights") {
+            if (i + 1 >= av.size()) {
+                std::cerr << "[agg] ERROR: --weights needs a value" << std::endl;
+                return 1;
+            }
+            have_weights = true;
+            weights_text = av[i + 1];
+            av.erase(av.begin() + i, av.begin() + i + 2);
+            break;
+        }
+    argc = (int)av.size();
+    argv = av.data();
     if (argc < 5) {
         std::cerr << "Usage: " << argv[0] << " <cc_path> <client2_encfile> <client1to2_encfile> <output_aggfile>" << std::endl;
         return 1;
@@ -17,6 +37,14 @@ int main(int argc, char *argv[]) {
     const std::string cc_path = argv[1], output_file = argv[4];
     std::vector<std::string> in_paths{argv[2], argv[3]};
     for (int i = 5; i < argc; ++i) in_paths.push_back(argv[i]);
+    RoundWeights rw;
+    if (have_weights) {
+        const std::string err = parse_weights(weights_text, in_paths.size(), rw.w);
+        if (!err.empty()) {
+            std::cerr << "[agg] ERROR: " << err << std::endl;
+            return 1;
+        }
+    }
     CcFile cc;
     try {
         cc = read_cc(cc_path);
@@ -49,8 +77,18 @@ int main(int argc, char *argv[]) {
             uint64_t *d_in = s.to_device(flat.data(), flat.size());
             seeds.expand(s, d_in, first.nl, 0, n_files * B);
             uint64_t *d_sum = s.alloc<uint64_t>(B * words);
-            Session::check(mkckks_eval_sum_batch(s.ctx(), d_in, d_sum, (uint32_t)n_files, (uint32_t)B, first.nl));
-            finish_aggregate(s, items, d_sum, first, n_files, outputJson);
+            if (rw.on()) {
+                const std::string err = weights_headroom_error(s, first);
+                if (!err.empty()) {
+                    std::cerr << "[agg] ERROR: " << err << std::endl;
+                    return 1;
+                }
+                Session::check(mkckks_eval_wsum_batch(s.ctx(), d_in, d_sum, (uint32_t)n_files, (uint32_t)B, first.nl, rw.w.data(),
+                                                      weights_sf_level(first), 0));
+            } else {
+                Session::check(mkckks_eval_sum_batch(s.ctx(), d_in, d_sum, (uint32_t)n_files, (uint32_t)B, first.nl));
+            }
+            finish_aggregate(s, items, d_sum, first, n_files, outputJson, rw.on());
         }
         write_envelope(outputJson, output_file, binary);
     } catch (const std::exception &e) {

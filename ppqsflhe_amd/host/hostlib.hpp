@@ -25,6 +25,7 @@
 #include "base64.hpp"
 #include "json.hpp"
 #include "sampler.hpp"
+#include "weights.hpp"
 
 namespace mkh {
 
@@ -772,7 +773,31 @@ struct AggResult {
     Ciphertext meta;
 };
 
-inline AggResult scale_aggregate(Session &s, size_t B, uint64_t *d_sum, const Ciphertext &first, size_t n_clients) {
+// --weights: the scaling-factor level of the weight constants for inputs like `first` -- EvalMult(ct, w) on a
+// noiseScaleDeg-2 ciphertext multiplies by round(w * sf(level + 1)) (after its rescale), on a noiseScaleDeg-1 one by
+// round(w * sf(level))
+inline uint32_t weights_sf_level(const Ciphertext &first) { return first.noise_deg == 2 ? first.level + 1 : first.level; }
+// the headroom rule of include/mkckks.h: before the rescale the coefficients are about scale * sf * |sum w_c v_c|; refuse
+// when not even |values| <= 1 fit the ciphertext's modulus.  Returns the error text, empty when there is room.
+inline std::string weights_headroom_error(const Session &s, const Ciphertext &first) {
+    double log_q = 0;
+    for (uint32_t i = 0; i < first.nl; ++i) log_q += std::log2((double)s.moduli()[i]);
+    const double need = std::log2(first.scale) + std::log2(s.sf(weights_sf_level(first), false));
+    if (need < log_q - 1) return "";
+    return "--weights: no headroom: the weighted sum needs log2(scale * sf) = " + std::to_string(need) + " bits below the " +
+           std::to_string(log_q - 1) + " of these " + std::to_string(first.nl) + "-limb ciphertexts";
+}
+// The clients' weights as the weighted calls take them.  `order`: device order of the clients (the re-keyed ones first).
+struct RoundWeights {
+    std::vector<double> w;  // per client in device order, normalised; empty: the plain mean
+    uint32_t sf_level = 0;
+    bool on() const { return !w.empty(); }
+};
+
+// weighted (--weights): d_sum already is sum_c M_c * x_c (mkckks_reencrypt_wsum_batch / mkckks_eval_wsum_batch), so what
+// is left of EvalMult is its rescale -- the result's header is the same
+inline AggResult scale_aggregate(Session &s, size_t B, uint64_t *d_sum, const Ciphertext &first, size_t n_clients,
+                                 bool weighted = false) {
     const uint32_t N = s.N(), nl = first.nl;
     AggResult r;
     Ciphertext &res = r.meta;
@@ -782,13 +807,14 @@ inline AggResult scale_aggregate(Session &s, size_t B, uint64_t *d_sum, const Ci
         // EvalMult(ct, double): rescale first (ModReduceInternalInPlace), then the integer constant
         if (nl < 2) throw std::runtime_error("ciphertext has no limb left to rescale");
         r.d_out = s.alloc<uint64_t>(B * (size_t)2 * (nl - 1) * N);
-        Session::check(mkckks_rescale_mult_const_batch(s.ctx(), d_sum, r.d_out, (uint32_t)B, nl, operand));
+        if (weighted) Session::check(mkckks_rescale_batch(s.ctx(), d_sum, r.d_out, (uint32_t)B, nl));
+        else Session::check(mkckks_rescale_mult_const_batch(s.ctx(), d_sum, r.d_out, (uint32_t)B, nl, operand));
         res.nl = nl - 1;
         res.level = first.level + 1;
         res.scale = first.scale / (double)s.moduli()[nl - 1] * s.sf(res.level, false);
         res.noise_deg = 2;
     } else {
-        Session::check(mkckks_mult_const_batch(s.ctx(), d_sum, (uint32_t)B, nl, operand));
+        if (!weighted) Session::check(mkckks_mult_const_batch(s.ctx(), d_sum, (uint32_t)B, nl, operand));
         res.nl = nl;
         res.level = first.level;
         res.scale = first.scale * s.sf(first.level, false);
@@ -816,8 +842,8 @@ inline void store_agg_items(Session &s, const std::vector<AggItem> &items, const
 }
 
 inline AggResult finish_aggregate(Session &s, const std::vector<AggItem> &items, uint64_t *d_sum, const Ciphertext &first,
-                                  size_t n_clients, Json &outputJson) {
-    AggResult r = scale_aggregate(s, items.size(), d_sum, first, n_clients);
+                                  size_t n_clients, Json &outputJson, bool weighted = false) {
+    AggResult r = scale_aggregate(s, items.size(), d_sum, first, n_clients, weighted);
     store_agg_items(s, items, r.d_out, r.meta, outputJson);
     return r;
 }

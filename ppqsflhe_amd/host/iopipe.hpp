@@ -302,6 +302,7 @@ struct RoundPlan {
     const std::vector<std::string> *evk_names = nullptr;  // their file names (what the cache compares)
     size_t evk_words = 0;
     unsigned threads = 4;
+    RoundWeights weights;                     // --weights (device order); off: the plain mean
 };
 
 inline unsigned round_chunk(size_t B) {
@@ -317,7 +318,7 @@ class RoundCache {
 public:
     explicit RoundCache(Session &s) : s_(s) {}
     ~RoundCache() {
-        for (Slot *b : {&all, &sum, &out, &evk, &back, &back_evk, &hra, &hra_rand, &hra_pk})
+        for (Slot *b : {&all, &sum, &out, &evk, &evk_scaled, &back, &back_evk, &hra, &hra_rand, &hra_pk})
             if (b->p) mkckks_dev_free(s_.ctx(), b->p);
     }
     RoundCache(const RoundCache &) = delete;
@@ -350,6 +351,11 @@ public:
     Slot hra, hra_rand, hra_pk;          // --hra-back: the re-randomised aggregate (prefix), its randomness, the public key
     std::string hra_pk_name;             // public key resident in hra_pk.p (by file name, like the back keys)
     std::vector<std::string> evk_names;  // keys resident in evk.p, in order
+    // --weights: the keys of evk.p scaled by their clients' weight constants, and what they were scaled from -- key file
+    // names, weights and scaling-factor level.  A copy is only used when all three are the round's (a stale scaled key
+    // gives every client a wrong aggregate without any error); it is remade otherwise.
+    Slot evk_scaled;
+    std::string scaled_tag;
     std::unique_ptr<PinnedRing> ring, out_pin;
     std::string warm_shape;              // "<nl>/<chunk>/<n_pre>/<n_plain>/<rescale>" the kernels were launched with
 
@@ -400,8 +406,51 @@ inline AggResult run_round_pipeline(Session &s, const RoundPlan &plan, Json doc,
             for (size_t k = 0; k < n_pre; ++k)
                 Session::check(mkckks_upload(s.ctx(), d_evk + k * plan.evk_words, plan.evks[k], plan.evk_words * 8));
             cache.evk_names = *plan.evk_names;
+            cache.scaled_tag.clear();
         }
     }
+    const RoundWeights &rw = plan.weights;
+    const bool weighted = rw.on();
+    const uint64_t *d_evk_s = nullptr;
+    if (weighted && n_pre) {
+        std::string tag = std::to_string(rw.sf_level);
+        for (size_t k = 0; k < n_pre; ++k) {
+            char buf[40];
+            std::snprintf(buf, sizeof buf, "|%a|", rw.w[k]);
+            tag += buf + (*plan.evk_names)[k];
+        }
+        if (n_pre * plan.evk_words > cache.evk_scaled.words) cache.scaled_tag.clear();  // the array moves: nothing is kept
+        uint64_t *d = cache.grow(cache.evk_scaled, n_pre * plan.evk_words);
+        if (cache.scaled_tag != tag) {
+            cache.scaled_tag.clear();
+            Session::check(mkckks_scale_evk_batch(s.ctx(), d_evk, d, (uint32_t)n_pre, rw.w.data(), rw.sf_level));
+            cache.scaled_tag = tag;
+        }
+        d_evk_s = d;
+    }
+    // the weighted forms of the two sums and of the closing EvalMult (its rescale alone; nothing at noiseScaleDeg 1)
+    const double *w_terms = weighted ? rw.w.data() + n_pre - (n_pre ? 1 : 0) : nullptr;  // term 0 = the re-keyed clients' slot
+    auto sum_pre = [&](const uint64_t *cts, uint64_t *out, size_t cnt, uint32_t nl_) {
+        if (weighted)
+            Session::check(mkckks_reencrypt_wsum_batch(s.ctx(), cts, d_evk_s, out, (uint32_t)n_pre, (uint32_t)cnt, nl_, rw.w.data(),
+                                                       rw.sf_level));
+        else Session::check(mkckks_reencrypt_sum_batch(s.ctx(), cts, d_evk, out, (uint32_t)n_pre, (uint32_t)cnt, nl_));
+    };
+    auto sum_plain = [&](const uint64_t *terms, uint64_t *out, size_t cnt, uint32_t nl_) {
+        const uint32_t n_terms = (uint32_t)(n_plain + (n_pre ? 1 : 0));
+        if (weighted)
+            Session::check(mkckks_eval_wsum_batch(s.ctx(), terms, out, n_terms, (uint32_t)cnt, nl_, w_terms, rw.sf_level, n_pre ? 1 : 0));
+        else Session::check(mkckks_eval_sum_batch(s.ctx(), terms, out, n_terms, (uint32_t)cnt, nl_));
+    };
+    auto scale_sum = [&](uint64_t *sum, uint64_t *outp, size_t cnt, uint32_t nl_, bool rescale_) {
+        const double operand = 1.0 / (double)n_clients;
+        if (rescale_) {
+            if (weighted) Session::check(mkckks_rescale_batch(s.ctx(), sum, outp, (uint32_t)cnt, nl_));
+            else Session::check(mkckks_rescale_mult_const_batch(s.ctx(), sum, outp, (uint32_t)cnt, nl_, operand));
+        } else if (!weighted) {
+            Session::check(mkckks_mult_const_batch(s.ctx(), sum, (uint32_t)cnt, nl_, operand));
+        }
+    };
     std::unique_ptr<PinnedRing> &ring = cache.ring;
     cache.pinned(cache.ring, in_bytes, std::max(4u, std::min<unsigned>(16u, 2 * plan.threads)));
     PinnedRing &out_pin = cache.pinned(cache.out_pin, out_bytes, (unsigned)B);
@@ -435,7 +484,7 @@ inline AggResult run_round_pipeline(Session &s, const RoundPlan &plan, Json doc,
     const uint64_t blobs0 = head.size(), blob_size = sizeof(BlobHeader) + out_bytes;
     const BlobHeader out_hdr = header_of(res, N);
     const std::string shape = std::to_string(nl) + "/" + std::to_string(Bc) + "/" + std::to_string(n_pre) + "/" +
-                              std::to_string(n_plain) + "/" + std::to_string((int)rescale);
+                              std::to_string(n_plain) + "/" + std::to_string((int)rescale) + (weighted ? "/w" : "");
     if (cache.warm_shape != shape) {   // process warm-up, the last part of the setup: copy streams, the workspace of one chunk and the first launch of every
         // kernel of the round (the HIP runtime resolves a kernel when it is first launched: ~30 ms for this path), on
         // whatever the fresh buffers hold -- none of the kernels addresses memory by data, and chunk 0 is overwritten below
@@ -447,11 +496,9 @@ inline AggResult run_round_pipeline(Session &s, const RoundPlan &plan, Json doc,
         Session::check(mkckks_expand_seeded_batch(s.ctx(), d_all, 1, nl, warm_key, &warm_sid));
         const size_t cnt = std::min<size_t>(Bc, B);
         uint64_t *slot = d_all + n_pre * cnt * words;
-        if (n_pre) Session::check(mkckks_reencrypt_sum_batch(s.ctx(), d_all, d_evk, n_plain ? slot : d_sum, (uint32_t)n_pre, (uint32_t)cnt, nl));
-        if (n_plain)
-            Session::check(mkckks_eval_sum_batch(s.ctx(), n_pre ? slot : slot + cnt * words, d_sum, (uint32_t)(n_plain + (n_pre ? 1 : 0)), (uint32_t)cnt, nl));
-        if (rescale) Session::check(mkckks_rescale_mult_const_batch(s.ctx(), d_sum, d_out, (uint32_t)cnt, nl, 1.0 / (double)n_clients));
-        else Session::check(mkckks_mult_const_batch(s.ctx(), d_sum, (uint32_t)cnt, nl, 1.0 / (double)n_clients));
+        if (n_pre) sum_pre(d_all, n_plain ? slot : d_sum, cnt, nl);
+        if (n_plain) sum_plain(n_pre ? slot : slot + cnt * words, d_sum, cnt, nl);
+        scale_sum(d_sum, d_out, cnt, nl, rescale);
         Session::check(mkckks_fence_compute(s.ctx()));
         Session::check(mkckks_download_async(s.ctx(), out_pin.slot(0), rescale ? d_out : d_sum, out_bytes, &ticket));
         Session::check(mkckks_copy_wait(s.ctx(), ticket));
@@ -629,7 +676,6 @@ inline AggResult run_round_pipeline(Session &s, const RoundPlan &plan, Json doc,
         std::vector<uint8_t> seed_keys;
         std::vector<uint32_t> seed_sids;
         size_t uploaded = 0, computed = 0, downloaded = 0;
-        const double operand = 1.0 / (double)n_clients;
         while (downloaded < B) {
             bool progress = false;
             std::pair<unsigned, size_t> got{0, 0};
@@ -700,20 +746,11 @@ inline AggResult run_round_pipeline(Session &s, const RoundPlan &plan, Json doc,
                 }
                 lap(0);
                 if (n_pre)  // with clients already in the domain the re-encrypted sum is one more term of their EvalAdd
-                    Session::check(mkckks_reencrypt_sum_batch(s.ctx(), base, d_evk, n_plain ? slot : sum, (uint32_t)n_pre, (uint32_t)cnt, nl));
-                if (n_plain) {
-                    const uint64_t *terms = n_pre ? slot : slot + cnt * words;
-                    Session::check(mkckks_eval_sum_batch(s.ctx(), terms, sum, (uint32_t)(n_plain + (n_pre ? 1 : 0)), (uint32_t)cnt, nl));
-                }
+                    sum_pre(base, n_plain ? slot : sum, cnt, nl);
+                if (n_plain) sum_plain(n_pre ? slot : slot + cnt * words, sum, cnt, nl);
                 lap(1);
-                uint64_t *outp;
-                if (rescale) {
-                    outp = d_out + b0 * owords;
-                    Session::check(mkckks_rescale_mult_const_batch(s.ctx(), sum, outp, (uint32_t)cnt, nl, operand));
-                } else {
-                    Session::check(mkckks_mult_const_batch(s.ctx(), sum, (uint32_t)cnt, nl, operand));
-                    outp = sum;
-                }
+                uint64_t *outp = rescale ? d_out + b0 * owords : sum;
+                scale_sum(sum, outp, cnt, nl, rescale);
                 lap(2);
                 Session::check(mkckks_fence_compute(s.ctx()));
                 lap(3);

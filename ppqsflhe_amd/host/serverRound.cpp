@@ -27,6 +27,15 @@
 // a buffer of its own -- with --back-limbs only its k + 1-limb prefix -- and every keyed back entry is re-encrypted from
 // that buffer; all back keys of a round share the one mask, the key-switch noise is per key anyway.  The aggregate file
 // and "-" entries are untouched; the public key stays resident by file name.  Back files differ from run to run.
+// --weights w_1,...,w_n (anywhere after <output_aggfile>): the weighted mean sum_c w_c x_c / sum_c w_c in place of the plain
+// one -- federated averaging by sample count.  One non-negative number per client in argument order, not all zero.  The
+// weights ride in what the merged flow reads anyway: the re-encryption keys are scaled once per (key, weight, level) into
+// a buffer of their own (mkckks_scale_evk_batch; the unscaled keys stay resident by file name, the scaled copies are
+// remade whenever a key's weight or level differs from the one it was scaled with), the sum is
+// mkckks_reencrypt_wsum_batch (+ mkckks_eval_wsum_batch for the "-" clients) and ONE mkckks_rescale_batch closes it (for
+// noiseScaleDeg-1 inputs: nothing).  The output has the header of the plain mean's; --back, --back-limbs and --hra-back
+// work on it as they are.  Refused: a count of weights that is not the count of clients, a negative weight or one that is
+// no number, inputs without headroom for the weighted sum (include/mkckks.h).  Without --weights nothing changes.
 // Binary (MKWS) envelopes take the I/O pipeline of iopipe.hpp: files are indexed, not loaded; reader threads fill pinned
 // slots, uploads run beside the reads, residues are range-checked on the device, results are written by pwrite() from
 // pinned slots.  MKCKKS_SYNC_IO=1 forces the synchronous path (every ciphertext through read_envelope / decode_ct /
@@ -52,6 +61,8 @@ struct RoundArgs {
     std::string hra_pk;       // --hra-back: public key file of the aggregate's domain (empty: no re-randomisation)
     uint32_t hra_bits = HRA_SIGMA_BITS_DEFAULT;
     bool hra_bits_ok = true;  // false: --hra-sigma-bits was no integer in [6, 56] (reported by run_round)
+    bool have_weights = false;  // --weights given
+    std::string weights_text;   // its value (judged by run_round, which knows the clients)
 };
 // tokens: <output_aggfile> <rekey_1|-> <encfile_1> ... [--back <rekey_back_1> <output_encfile_1> ...]
 static bool parse_round(std::vector<std::string> t, RoundArgs &a) {
@@ -64,6 +75,16 @@ static bool parse_round(std::vector<std::string> t, RoundArgs &a) {
                 return false;
             compact = true;
             back_limbs = (uint32_t)std::atoi(t[i + 1].c_str());
+            t.erase(t.begin() + i, t.begin() + i + 2);
+            break;
+        }
+    bool have_weights = false;
+    std::string weights_text;
+    for (size_t i = 1; i < t.size(); ++i)
+        if (t[i] == "--weights") {  // one value, taken out the same way
+            if (i + 1 >= t.size()) return false;
+            have_weights = true;
+            weights_text = t[i + 1];
             t.erase(t.begin() + i, t.begin() + i + 2);
             break;
         }
@@ -102,6 +123,8 @@ static bool parse_round(std::vector<std::string> t, RoundArgs &a) {
     a.hra_bits_ok = hra_bits_ok;
     a.compact = compact;
     a.back_limbs = back_limbs;
+    a.have_weights = have_weights;
+    a.weights_text = weights_text;
     a.output_file = t[0];
     for (size_t i = 1; i + 1 < n_args; i += 2) {
         a.rekey_paths.push_back(t[i]);
@@ -148,6 +171,16 @@ static int run_round(Session &s, ServerState &st, const RoundArgs &a) {
     const size_t n_pre = order.size();
     for (size_t c = 0; c < n_clients; ++c)
         if (rekey_paths[c] == "-") order.push_back(c);
+    RoundWeights rw;  // --weights, in device order
+    if (a.have_weights) {
+        std::vector<double> w;
+        const std::string err = parse_weights(a.weights_text, n_clients, w);
+        if (!err.empty()) {
+            std::cerr << "[round] ERROR: " << err << std::endl;
+            return 1;
+        }
+        for (size_t k = 0; k < n_clients; ++k) rw.w.push_back(w[order[k]]);
+    }
     std::vector<const uint64_t *> evk_ptrs;
     std::vector<std::string> evk_names;
     for (size_t k = 0; k < n_pre; ++k) {
@@ -219,24 +252,37 @@ static int run_round(Session &s, ServerState &st, const RoundArgs &a) {
             st.pks[a.hra_pk] = std::move(pk);
         }
     }
+    auto first_header = [&] {
+        BlobHeader h0{};
+        if (piped) {
+            const BlobRef &blob0 = idx[0].blobs.at(blob_index(*items[0].blobs[0]));
+            if (blob0.size < sizeof(BlobHeader)) throw std::runtime_error("ciphertext blob too short");
+            pread_all(idx[0].fd, &h0, sizeof h0, blob0.offset);
+        } else {
+            const std::string &b = *items[0].blobs[0];
+            const bool raw = b.size() >= 4 && !std::memcmp(b.data(), "MKCK", 4);
+            const std::string head = raw ? b.substr(0, sizeof h0) : Base64Decode(b.substr(0, sizeof h0 / 3 * 4));
+            if (head.size() < sizeof h0) throw std::runtime_error("ciphertext blob too short");
+            std::memcpy(&h0, head.data(), sizeof h0);
+        }
+        return h0;
+    };
+    if (rw.on() && !items.empty()) {
+        const Ciphertext first = meta_of(first_header(), s);
+        const std::string err = weights_headroom_error(s, first);
+        if (!err.empty()) {
+            std::cerr << "[round] ERROR: " << err << std::endl;
+            return 1;
+        }
+        rw.sf_level = weights_sf_level(first);
+    }
     if (a.compact) {
         if (a.back_limbs < 1) {
             std::cerr << "[round] ERROR: --back-limbs must be at least 1" << std::endl;
             return 1;
         }
         if (!items.empty()) {
-            BlobHeader h0{};
-            if (piped) {
-                const BlobRef &blob0 = idx[0].blobs.at(blob_index(*items[0].blobs[0]));
-                if (blob0.size < sizeof(BlobHeader)) throw std::runtime_error("ciphertext blob too short");
-                pread_all(idx[0].fd, &h0, sizeof h0, blob0.offset);
-            } else {
-                const std::string &b = *items[0].blobs[0];
-                const bool raw = b.size() >= 4 && !std::memcmp(b.data(), "MKCK", 4);
-                const std::string head = raw ? b.substr(0, sizeof h0) : Base64Decode(b.substr(0, sizeof h0 / 3 * 4));
-                if (head.size() < sizeof h0) throw std::runtime_error("ciphertext blob too short");
-                std::memcpy(&h0, head.data(), sizeof h0);
-            }
+            const BlobHeader h0 = first_header();
             const bool rescale = h0.noise_deg == 2;
             const uint32_t agg_nl = rescale ? h0.limbs - 1 : h0.limbs, agg_deg = rescale ? 2 : h0.noise_deg + 1;
             if (agg_deg != 2) {
@@ -260,6 +306,7 @@ static int run_round(Session &s, ServerState &st, const RoundArgs &a) {
         plan.evk_names = &evk_names;
         plan.evk_words = evk_words;
         plan.threads = threads;
+        plan.weights = rw;
         RoundTimes tm;
         agg = run_round_pipeline(s, plan, outputJson, a.output_file, st.cache, tm);
         pinned_out = true;
@@ -293,14 +340,26 @@ static int run_round(Session &s, ServerState &st, const RoundArgs &a) {
             st.cache.evk_names.clear();
             for (size_t k = 0; k < n_pre; ++k) Session::check(mkckks_upload(s.ctx(), d_evk + k * evk_words, evk_ptrs[k], evk_words * 8));
             st.cache.evk_names = evk_names;
-            Session::check(mkckks_reencrypt_sum_batch(s.ctx(), d_all, d_evk, d_slot, (uint32_t)n_pre, (uint32_t)B, nl));
+            if (rw.on()) {  // this path uploads the keys every round, so their scaled copies are made every round
+                st.cache.scaled_tag.clear();
+                uint64_t *d_evk_s = st.cache.grow(st.cache.evk_scaled, n_pre * evk_words);
+                Session::check(mkckks_scale_evk_batch(s.ctx(), d_evk, d_evk_s, (uint32_t)n_pre, rw.w.data(), rw.sf_level));
+                Session::check(mkckks_reencrypt_wsum_batch(s.ctx(), d_all, d_evk_s, d_slot, (uint32_t)n_pre, (uint32_t)B, nl,
+                                                           rw.w.data(), rw.sf_level));
+            } else {
+                Session::check(mkckks_reencrypt_sum_batch(s.ctx(), d_all, d_evk, d_slot, (uint32_t)n_pre, (uint32_t)B, nl));
+            }
         }
         if (n_plain) {
             const uint64_t *d_terms = n_pre ? d_slot : d_slot + blk;
             d_sum = st.cache.grow(st.cache.sum, blk);
-            Session::check(mkckks_eval_sum_batch(s.ctx(), d_terms, d_sum, (uint32_t)(n_plain + (n_pre ? 1 : 0)), (uint32_t)B, nl));
+            if (rw.on())  // the slot of the re-keyed clients' sum is term 0 and enters as it is
+                Session::check(mkckks_eval_wsum_batch(s.ctx(), d_terms, d_sum, (uint32_t)(n_plain + (n_pre ? 1 : 0)), (uint32_t)B, nl,
+                                                      rw.w.data() + n_pre - (n_pre ? 1 : 0), rw.sf_level, n_pre ? 1 : 0));
+            else
+                Session::check(mkckks_eval_sum_batch(s.ctx(), d_terms, d_sum, (uint32_t)(n_plain + (n_pre ? 1 : 0)), (uint32_t)B, nl));
         }
-        agg = finish_aggregate(s, items, d_sum, first, n_clients, outputJson);
+        agg = finish_aggregate(s, items, d_sum, first, n_clients, outputJson, rw.on());
     }
     if (!pinned_out) write_envelope(outputJson, a.output_file, binary);
     if (int rc = run_back_leg(s, st, a, items, agg, outputJson, binary, pinned_out, threads)) return rc;
@@ -453,7 +512,7 @@ static int run_back_leg(Session &s, ServerState &st, const RoundArgs &a, const s
 int main(int argc, char *argv[]) {
     auto usage = [&] {
         std::cerr << "Usage: " << argv[0] << " <cc_path> <output_aggfile> <rekey_1|-> <encfile_1> [<rekey_2|-> <encfile_2> ...]"
-                  << " [--back <rekey_back_1|-> <output_encfile_1> ... [--back-limbs <k>] [--hra-back <target_domain_pubkey> [--hra-sigma-bits <s>]]]\n       " << argv[0]
+                  << " [--weights <w_1,...,w_n>] [--back <rekey_back_1|-> <output_encfile_1> ... [--back-limbs <k>] [--hra-back <target_domain_pubkey> [--hra-sigma-bits <s>]]]\n       " << argv[0]
                   << " <cc_path> --rounds <file with one such argument list (after <cc_path>) per line>" << std::endl;
         return 1;
     };
