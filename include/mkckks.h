@@ -354,7 +354,11 @@ int mkckks_encode_batch(mkckks_ctx *c, const double *d_vals, uint64_t *d_pt, uin
 /* ---- pt->GetRealPackedValue()  (decryptModelWeights.cpp:83,92,109) ------------
  * CRT interpolation of d_m u64[n][nl][N] (output of mkckks_decrypt_batch), / scale,
  * canonical embedding -> d_vals double[n][N/2]: the exact embedding, without upstream
- * Decode's noise estimate and flooding (those: mkckks_decode_flood_batch). */
+ * Decode's noise estimate and flooding (those: mkckks_decode_flood_batch).
+ * nl <= 32.  The centred lift is accumulated in fp64 (upstream and the oracle use long double), so the decrypted
+ * integers must stay below the largest double: any |x| <= Q / 2 up to nl = 20 with 50-bit scaling limbs (Q ~ 2^980);
+ * at deeper levels (Q ~ 2^1580 at nl = 32) only |x| < 2^1000 is supported -- a message at its scale, a long way below
+ * Q / 2 -- and a coefficient near Q / 2 decodes to +-inf where the oracle still returns a finite value. */
 int mkckks_decode_batch(mkckks_ctx *c, const uint64_t *d_m, double *d_vals, uint32_t n, uint32_t nl, double scale);
 /* ---- pt->GetRealPackedValue() after cc->Decrypt with upstream's decode-time noise flooding
  * (CKKSPackedEncoding::Decode as reached from decryptModelWeights.cpp:81-83,90-92,108-110; the defence against

@@ -61,6 +61,9 @@ TABLE = {
     "al5": ((12, 8, 40, 60, 2, 60, 20), (10, 4, 5, 2), _classes(10, 4, PM)),
     "al8": ((12, 14, 40, 60, 2, 60, 20), (16, 6, 8, 2), _classes(16, 6, PM)),
     "al8k8": ((12, 14, 40, 60, 2, 48, 20), (16, 8, 8, 2), _classes(16, 8, FP64)),  # aux_bits 49 still gives K = 7
+    # the deepest chain generate() accepts: L = 32 = CRT_MAX_LIMBS (decode's private digit array is full), four digits of 8
+    # with K = 7; the battery's nl = L, L - 1 (a last digit of 7) and 1 cover the full level, a partial digit and one limb
+    "d30": ((12, 30, 50, 60, 4, 60, 20), (32, 7, 8, 4), _classes(32, 7, PM)),
     # one pass radix and one generic (2^13, 2^15), both generic at the smallest ring: integer arithmetic only
     "r8": ((8, 3, 50, 60, 2, 60, 20), (5, 3, 3, 2), [0] * 8),
     "r13": ((13, 2, 50, 60, 2, 60, 20), (4, 2, 2, 2), [0] * 6),
