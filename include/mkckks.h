@@ -510,6 +510,90 @@ const char *mkckks_comm_library(void);
  * h_out: 2^20 words; *n_out = words written, 0 in a product build */
 int mkckks_debug_stamps(mkckks_ctx *c, unsigned long long *h_out, uint32_t region, size_t *n_out);
 
+/* ---- diagnostics for tests: run ONE arithmetic primitive of the library per element ("known-answer hook" of the
+ * modular arithmetic).  in: u64[n_in(op)][count] operand planes, out: u64[n_out(op)][count]; doubles travel as bit
+ * patterns; element i of every output plane depends on element i of the input planes only.  On a device context the
+ * pointers are device pointers and the op runs as one element-wise kernel on the context's stream, through the DEVICE
+ * form of the primitive; on a device = -1 context they are host pointers and the HOST form runs (the fp64 class has a
+ * device form only: MKCKKS_E_NODEVICE there).  q: any odd modulus with 2^17 < q < 2^60, need not belong to the context
+ * nor be prime; the reduction constants are built from it as the context's are.  Twiddle planes (always the LAST
+ * planes of `in`) hold the residue w < q only: the companion (Shoup: floor(w 2^64 / q); pseudo-Mersenne: the pair
+ * w << t, (w 2^32 mod q) << t; fp64: (double) w, w / q) is made by the code that fills the NTT tables.
+ * MKCKKS_E_INVALID: unknown op, an fp64 op with q >= 5 * 2^48, a pseudo-Mersenne op with a q that is not 2^k - c with
+ * c <= 2^(k-34) and 40 <= k <= 60, a twiddle >= q, overlapping in / out.  count == 0 is a no-op.
+ * Operands outside the domain a primitive documents give unspecified words (never a fault).
+ *
+ * op                    in planes                         out planes
+ * CSUB                  x, m                              x - m if x >= m else x          (x, m < 2^63)
+ * ADD_MOD / SUB_MOD     a, b                              canonical                       (a, b < q)
+ * SHOUP_LAZY / _MUL     a, w                              [0,2q) / canonical              (any a)
+ * MUL_MOD               a, b                              canonical                       (a, b < q)
+ * BARRETT_REDUCE128     hi, lo                            canonical                       (hi:lo < 2^(k+62))
+ * REDUCE_WIDE           hi, lo                            canonical                       (hi:lo < 2^124)
+ * REDUCE_WORD           x                                 canonical
+ * REDUCE_COLS_LAZY / _COLS   c0, c1, c2                   [0,4q) / canonical              (<= 4 products per column)
+ * REDUCE_COLS4          c0, c1a, c1b, c2                  canonical                       (<= 8 products per column)
+ * MAC128 / MAC128_SPLIT hi, lo, a, b                      hi', lo' = hi:lo + a b
+ * CT_BUTTERFLY_C4 / _NC, GS_BUTTERFLY      x, y, w        x', y'
+ * CANON8                v                                 canonical                       (v < 8q)
+ * RADIX_FORWARD4 / RADIX_INVERSE4          x[16], w[15]   x'[16]  (one register round; w[(1 << s) - 1 + g])
+ * PM_FOLD               x                                 < U + 2^30
+ * PM_LAZY               a, w                              < 2.375U                        (a < 8U)
+ * PM_REDUCE128          hi, lo                            canonical                       (hi:lo < 2^(2k+6))
+ * PM_REDUCE_COLS        c0, c1, c2                        < 2.1U
+ * CT_BUTTERFLY_PM_F / _PM_N, GS_BUTTERFLY_PM   x, y, w    x', y'
+ * RADIX_FORWARD_PM4 / RADIX_INVERSE_PM4    x[16], w[15]   x'[16]
+ * FP_MULMOD             y, w                              double
+ * FP_REDUCE             x                                 double
+ * FP_TO_CANONICAL       x                                 u64
+ * FP_MULMOD_ANY         y, e  (both doubles)              double
+ * U52_TO_DOUBLE         v (u64 < 2^52)                    double
+ * SPLIT30_D             canonical double                  low 30 bits, bits 30.. (the conversion kernels' split)
+ * CT_BUTTERFLY_FP / _FP_NR, GS_BUTTERFLY_FP    x, y, w    x', y'  (doubles)
+ * RADIX_FORWARD_FP4 / RADIX_INVERSE_FP4    x[16], w[15]   x'[16]  (doubles) */
+#define MKCKKS_OP_CSUB 0
+#define MKCKKS_OP_ADD_MOD 1
+#define MKCKKS_OP_SUB_MOD 2
+#define MKCKKS_OP_SHOUP_LAZY 3
+#define MKCKKS_OP_SHOUP_MUL 4
+#define MKCKKS_OP_MUL_MOD 5
+#define MKCKKS_OP_BARRETT_REDUCE128 6
+#define MKCKKS_OP_REDUCE_WIDE 7
+#define MKCKKS_OP_REDUCE_WORD 8
+#define MKCKKS_OP_REDUCE_COLS_LAZY 9
+#define MKCKKS_OP_REDUCE_COLS 10
+#define MKCKKS_OP_REDUCE_COLS4 11
+#define MKCKKS_OP_MAC128 12
+#define MKCKKS_OP_MAC128_SPLIT 13
+#define MKCKKS_OP_CT_BUTTERFLY_C4 14
+#define MKCKKS_OP_CT_BUTTERFLY_NC 15
+#define MKCKKS_OP_GS_BUTTERFLY 16
+#define MKCKKS_OP_CANON8 17
+#define MKCKKS_OP_RADIX_FORWARD4 18
+#define MKCKKS_OP_RADIX_INVERSE4 19
+#define MKCKKS_OP_PM_FOLD 20
+#define MKCKKS_OP_PM_LAZY 21
+#define MKCKKS_OP_PM_REDUCE128 22
+#define MKCKKS_OP_PM_REDUCE_COLS 23
+#define MKCKKS_OP_CT_BUTTERFLY_PM_F 24
+#define MKCKKS_OP_CT_BUTTERFLY_PM_N 25
+#define MKCKKS_OP_GS_BUTTERFLY_PM 26
+#define MKCKKS_OP_RADIX_FORWARD_PM4 27
+#define MKCKKS_OP_RADIX_INVERSE_PM4 28
+#define MKCKKS_OP_FP_MULMOD 29
+#define MKCKKS_OP_FP_REDUCE 30
+#define MKCKKS_OP_FP_TO_CANONICAL 31
+#define MKCKKS_OP_FP_MULMOD_ANY 32
+#define MKCKKS_OP_U52_TO_DOUBLE 33
+#define MKCKKS_OP_SPLIT30_D 34
+#define MKCKKS_OP_CT_BUTTERFLY_FP 35
+#define MKCKKS_OP_CT_BUTTERFLY_FP_NR 36
+#define MKCKKS_OP_GS_BUTTERFLY_FP 37
+#define MKCKKS_OP_RADIX_FORWARD_FP4 38
+#define MKCKKS_OP_RADIX_INVERSE_FP4 39
+#define MKCKKS_OP_COUNT 40
+int mkckks_debug_arith(mkckks_ctx *c, uint32_t op, uint64_t q, const uint64_t *in, uint64_t *out, size_t count);
+
 /* ---- introspection for tests: copy a CRT table to the host ---------------- */
 int mkckks_ctx_twiddles(const mkckks_ctx *c, uint32_t limb, int inverse, uint64_t *h_out /*N*/);
 

@@ -110,6 +110,50 @@ SYMBOLS = {
     "mkckks_reduce_scatter_sum_mod": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u32]),
     "mkckks_comm_library": (C.c_char_p, []),
     "mkckks_ctx_twiddles": (_int, [_vp, _u32, _int, _u64p]),
+    "mkckks_debug_arith": (_int, [_vp, _u32, C.c_uint64, _vp, _vp, _sz]),
+}
+# ops of mkckks_debug_arith (MKCKKS_OP_* of include/mkckks.h): name -> (id, input planes, output planes, twiddle planes)
+ARITH_OPS = {
+    "csub": (0, 2, 1, 0),
+    "add_mod": (1, 2, 1, 0),
+    "sub_mod": (2, 2, 1, 0),
+    "shoup_lazy": (3, 2, 1, 1),
+    "shoup_mul": (4, 2, 1, 1),
+    "mul_mod": (5, 2, 1, 0),
+    "barrett_reduce128": (6, 2, 1, 0),
+    "reduce_wide": (7, 2, 1, 0),
+    "reduce_word": (8, 1, 1, 0),
+    "reduce_cols_lazy": (9, 3, 1, 0),
+    "reduce_cols": (10, 3, 1, 0),
+    "reduce_cols4": (11, 4, 1, 0),
+    "mac128": (12, 4, 2, 0),
+    "mac128_split": (13, 4, 2, 0),
+    "ct_butterfly_c4": (14, 3, 2, 1),
+    "ct_butterfly_nc": (15, 3, 2, 1),
+    "gs_butterfly": (16, 3, 2, 1),
+    "canon8": (17, 1, 1, 0),
+    "radix_forward4": (18, 31, 16, 15),
+    "radix_inverse4": (19, 31, 16, 15),
+    "pm_fold": (20, 1, 1, 0),
+    "pm_lazy": (21, 2, 1, 1),
+    "pm_reduce128": (22, 2, 1, 0),
+    "pm_reduce_cols": (23, 3, 1, 0),
+    "ct_butterfly_pm_f": (24, 3, 2, 1),
+    "ct_butterfly_pm_n": (25, 3, 2, 1),
+    "gs_butterfly_pm": (26, 3, 2, 1),
+    "radix_forward_pm4": (27, 31, 16, 15),
+    "radix_inverse_pm4": (28, 31, 16, 15),
+    "fp_mulmod": (29, 2, 1, 1),
+    "fp_reduce": (30, 1, 1, 0),
+    "fp_to_canonical": (31, 1, 1, 0),
+    "fp_mulmod_any": (32, 2, 1, 0),
+    "u52_to_double": (33, 1, 1, 0),
+    "split30_d": (34, 1, 2, 0),
+    "ct_butterfly_fp": (35, 3, 2, 1),
+    "ct_butterfly_fp_nr": (36, 3, 2, 1),
+    "gs_butterfly_fp": (37, 3, 2, 1),
+    "radix_forward_fp4": (38, 31, 16, 15),
+    "radix_inverse_fp4": (39, 31, 16, 15),
 }
 COMM_ID_BYTES = 128
 E_PRECISION = -6  # MKCKKS_E_PRECISION: decode_flood's noise estimate exceeds the context's precision
@@ -289,6 +333,29 @@ class Context:
         out = np.zeros(self.N, dtype=np.uint64)
         self._check(self._L.mkckks_ctx_twiddles(self._h, limb, int(inverse), out.ctypes.data))
         return out
+
+    def debug_arith(self, op, q, operands):
+        """Diagnostics: run primitive `op` (a name of ARITH_OPS) once per element of the operand planes
+        uint64[n_in][count] under modulus q; returns uint64[n_out][count].  Device context: the device form, on the
+        stream; device=-1: the host form.  Doubles travel as bit patterns; twiddle planes hold w only."""
+        opid, n_in, n_out, _ = ARITH_OPS[op]
+        x = np.ascontiguousarray(operands, dtype=np.uint64)
+        assert x.ndim == 2 and x.shape[0] == n_in, (op, x.shape)
+        count = x.shape[1]
+        if self.device < 0:
+            out = np.zeros((n_out, count), dtype=np.uint64)
+            self._check(self._L.mkckks_debug_arith(self._h, opid, int(q), x.ctypes.data, out.ctypes.data, count))
+            return out
+        if count == 0:
+            self._check(self._L.mkckks_debug_arith(self._h, opid, int(q), None, None, 0))
+            return np.zeros((n_out, 0), dtype=np.uint64)
+        d_in, d_out = self.to_device(x), self.empty((n_out, count))
+        try:
+            self._check(self._L.mkckks_debug_arith(self._h, opid, int(q), d_in.ptr, d_out.ptr, count))
+            return d_out.to_host()
+        finally:
+            d_in.free()
+            d_out.free()
 
     def num_parts(self, nl):
         return min(self.beta, -(-nl // self.alpha))

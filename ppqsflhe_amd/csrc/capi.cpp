@@ -130,6 +130,15 @@ int mkckks_ctx_twiddles(const mkckks_ctx *c, uint32_t limb, int inverse, uint64_
     });
 }
 
+int mkckks_debug_arith(mkckks_ctx *c, uint32_t op, uint64_t q, const uint64_t *in, uint64_t *out, size_t count) {
+    return guarded([&] {
+        need(c, "null context");
+        need(op < MKCKKS_OP_COUNT, "unknown op");
+        need(count == 0 || (in && out), "null argument");
+        c->eng->debug_arith(op, q, in, out, count);
+    });
+}
+
 int mkckks_set_stream(mkckks_ctx *c, void *s) {
     return guarded([&] {
         need(c, "null context");

@@ -19,6 +19,8 @@
 #include "fanout_kernels.hpp"
 #include "codec_kernels.hpp"
 #include "sampler_kernels.hpp"
+#include "arith_probe_kernels.hpp"
+#include "../../include/mkckks.h"
 
 #include <cmath>
 #include <cstdio>
@@ -646,18 +648,10 @@ Engine::Engine(const ParamSet &ps, int device) : ps_(ps), device_(device), knobs
     MK_HIP(hipMalloc(&d_itw_sh_, tbytes));
     std::vector<u64> w, wsh;
     auto as_fp = [&](uint32_t i) {  // (w, Shoup companion) -> (double w, double w/q) bit patterns
-        const long double q = (long double)ps_.moduli[i];
-        for (uint32_t k = 0; k < n; ++k) {
-            const double wd = (double)w[k], wq = (double)((long double)w[k] / q);
-            std::memcpy(&w[k], &wd, 8);
-            std::memcpy(&wsh[k], &wq, 8);
-        }
+        for (uint32_t k = 0; k < n; ++k) fp_table_entry(w[k], ps_.moduli[i], w[k], wsh[k]);
     };
     auto as_pm = [&](uint32_t i) {  // (w, Shoup companion) -> (w << t, (w * 2^32 mod q) << t), see pm_lazy
-        for (uint32_t k = 0; k < n; ++k) {
-            wsh[k] = pm_tw_companion(w[k], ps_.limb[i]);
-            w[k] = pm_tw(w[k], ps_.limb[i]);
-        }
+        for (uint32_t k = 0; k < n; ++k) pm_table_entry(w[k], ps_.limb[i], w[k], wsh[k]);
     };
     for (uint32_t i = 0; i < D; ++i) {
         ps_.twiddles(i, false, w, wsh);
@@ -2754,6 +2748,96 @@ void Engine::decode_flood(const u64 *m, double *vals, uint32_t cnt, uint32_t nl,
             throw PrecisionError(std::string("The decryption failed because the approximation error is too high. "
                                              "Check the parameters.") + detail);
         }
+}
+
+// the op ids of the public header are the probe's
+#define X(name, id, n_in, n_out, n_tw, twk, cls, host) static_assert(MKCKKS_OP_##name == id, "MKCKKS_OP_" #name);
+MK_PROBE_OPS(X)
+#undef X
+static_assert(MKCKKS_OP_COUNT == POP_COUNT, "MKCKKS_OP_COUNT");
+// diagnostics (tests/test_device_arith.py): one primitive per element, device form on a device context, host form on a
+// device = -1 context.  Companions of the twiddle planes are made here with the table code of the NTT tables.
+void Engine::debug_arith(uint32_t op, u64 q, const u64 *in, u64 *out, size_t count) {
+    ProbeDesc d;
+    if (!probe_desc(op, d)) throw std::invalid_argument("debug_arith: unknown op");
+    if (!(q & 1) || q <= (1ull << 17) || q >= (1ull << 60))
+        throw std::invalid_argument("debug_arith: q must be odd with 2^17 < q < 2^60");
+    if (d.cls == PCL_FP && q >= (5ull << 48)) throw std::invalid_argument("debug_arith: fp64 op with q >= 5 * 2^48");
+    if (d.cls == PCL_PM && !pm_eligible(q)) throw std::invalid_argument("debug_arith: q is not pseudo-Mersenne");
+    {
+        const uintptr_t a = (uintptr_t)in, b = (uintptr_t)out;
+        const uintptr_t an = (uintptr_t)d.n_in * count * sizeof(u64), bn = (uintptr_t)d.n_out * count * sizeof(u64);
+        if (a < b + bn && b < a + an && count) throw std::invalid_argument("debug_arith: in and out overlap");
+    }
+    if (device_ < 0 && !d.host) throw NoDevice("debug_arith: this op has a device form only");
+    if (!count) return;
+    ProbeK K;
+    K.lc = make_limb_const(q, 1);
+    K.P = PmK{};
+    if (d.cls == PCL_FP) K.lc.fp = 1;
+    if (d.cls == PCL_PM) {
+        K.lc.pm = 1;
+        K.lc.pm_c = (uint32_t)(((u64)1 << K.lc.k) - q);
+        K.P = pm_consts(K.lc);
+    }
+    const uint32_t n_data = d.n_in - d.n_tw, n_exp = n_data + 2 * d.n_tw;
+    // expanded twiddle planes: [n_tw][count] table entries, then [n_tw][count] companions
+    std::vector<u64> tw;
+    auto expand = [&](const u64 *w) {
+        const size_t m = (size_t)d.n_tw * count;
+        tw.resize(2 * m);
+        for (size_t j = 0; j < m; ++j) {
+            if (w[j] >= q) throw std::invalid_argument("debug_arith: twiddle not below q");
+            if (d.tw == PTW_SHOUP) { tw[j] = w[j]; tw[m + j] = h_shoup(w[j], q); }
+            else if (d.tw == PTW_PM) pm_table_entry(w[j], K.lc, tw[j], tw[m + j]);
+            else fp_table_entry(w[j], q, tw[j], tw[m + j]);
+        }
+    };
+    if (device_ < 0) {
+        std::vector<u64> exp;
+        const u64 *src = in;
+        if (d.n_tw) {
+            expand(in + (size_t)n_data * count);
+            exp.assign(in, in + (size_t)n_data * count);
+            exp.insert(exp.end(), tw.begin(), tw.end());
+            src = exp.data();
+        }
+        switch (op) {
+#define X(name, id, n_in, n_out, n_tw, twk, cls, host) \
+    case id: for (size_t i = 0; i < count; ++i) probe_hd<id>(K, src, out, count, i); break;
+            MK_PROBE_OPS(X)
+#undef X
+        }
+        return;
+    }
+    MK_HIP(hipSetDevice(device_));
+    const u64 *src = in;
+    u64 *d_exp = nullptr;
+    if (d.n_tw) {
+        std::vector<u64> w((size_t)d.n_tw * count);
+        MK_HIP(hipMemcpyAsync(w.data(), in + (size_t)n_data * count, w.size() * sizeof(u64), hipMemcpyDeviceToHost, stream_));
+        MK_HIP(hipStreamSynchronize(stream_));
+        expand(w.data());
+        MK_HIP(hipMalloc(&d_exp, (size_t)n_exp * count * sizeof(u64)));
+        hipError_t e = hipMemcpyAsync(d_exp, in, (size_t)n_data * count * sizeof(u64), hipMemcpyDeviceToDevice, stream_);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(d_exp + (size_t)n_data * count, tw.data(), tw.size() * sizeof(u64), hipMemcpyHostToDevice, stream_);
+        if (e != hipSuccess) { (void)hipFree(d_exp); MK_HIP(e); }
+        src = d_exp;
+    }
+    const unsigned grid = (unsigned)std::min<size_t>((count + PROBE_THREADS - 1) / PROBE_THREADS, 4096);
+    switch (op) {
+#define X(name, id, n_in, n_out, n_tw, twk, cls, host) \
+    case id: k_arith_probe<id, host != 0><<<grid, PROBE_THREADS, 0, stream_>>>(K, src, out, count); break;
+        MK_PROBE_OPS(X)
+#undef X
+    }
+    hipError_t e = hipGetLastError();
+    if (d_exp) {  // the staging buffer goes away with the call: wait for the kernel first
+        if (e == hipSuccess) e = hipStreamSynchronize(stream_);
+        (void)hipFree(d_exp);
+    }
+    MK_HIP(e);
 }
 
 void Engine::host_twiddles(uint32_t limb, bool inverse, std::vector<u64> &out) const {

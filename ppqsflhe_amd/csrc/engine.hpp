@@ -193,6 +193,11 @@ public:
                       uint32_t sid, double *h_log2);
 
     void host_twiddles(uint32_t limb, bool inverse, std::vector<u64> &out) const;
+    // diagnostics: run primitive `op` (arith_probe_kernels.hpp; MKCKKS_OP_* of mkckks.h) once per element on operand
+    // planes in u64[n_in][count] -> out u64[n_out][count], modulus q (odd, 2^17 < q < 2^60, need not belong to the
+    // context).  Device context: device pointers, device form, on the stream.  device = -1: host pointers, host form;
+    // device-only ops throw NoDevice
+    void debug_arith(uint32_t op, u64 q, const u64 *in, u64 *out, size_t count);
     // diagnostic builds (-DMK_STAMP=1, MKCKKS_STAMPS=1): copy one region of in-kernel phase stamps (2^20 words) to the
     // host and clear it; 0 words in a product build
     size_t debug_stamps(unsigned long long *h_out, uint32_t region);

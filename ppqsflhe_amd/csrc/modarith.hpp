@@ -265,6 +265,10 @@ MK_HD u64 pm_reduce128(u64 hi, u64 lo, const PmK &P, u64 q) {
 
 // Barrett reduction of a 128-bit x = hi:lo with x < 2^(k+62) (k = bitlen q) to [0,q).
 // qhat = mulhi64(x >> (k-2), mu), mu = floor(2^(62+k)/q): qhat in {Q-2,Q-1,Q}.
+// (X/q - qhat's real value = (f1 m + a f2 - f1 f2) / 2^64 with a = x / 2^(k-2) < 2^64, m = 2^(62+k)/q <= 2^63 and the two
+// truncated fractions f1, f2 = frac(m) < 1: below 2^(k-2)/q + f2 < 1.5.  Q-2, i.e. the subtraction of 2q, needs
+// 2^(k-2)/q + f2 > 1 and x near 2^(k+62): no prime next to a power of two gets there, since f2 is small for those; a general
+// q does -- tests/test_device_arith.py has one.)
 MK_HD u64 barrett_reduce128(u64 hi, u64 lo, const LimbConst &L) {
     u64 y = (hi << (64 - L.sh)) | (lo >> L.sh);
     u64 qh = mulhi64(y, L.mu);
@@ -356,6 +360,8 @@ MK_HD void mac_cols(Cols &c, uint32_t a0, uint32_t a1, uint32_t b0, uint32_t b1)
 }
 // S = c0 + c1*2^30 + c2*2^60 < 2^(k+62)  ->  S mod q.  The Barrett window floor(S / 2^sh) is assembled from
 // the three columns (under-estimate by <= 2), so qhat in {Q-3..Q} and the remainder is below 4q.
+// (Tighter, with the terms of barrett_reduce128: the error is below 2 * 2^(k-2)/q + (q/2^k) f2 < 1.5 for columns of <= 4
+// products, so qhat >= Q-2 and the remainder stays below 2.5q; consumers may keep relying on 4q.)
 MK_HD u64 reduce_cols_lazy(const Cols &c, const LimbConst &L) {  // result in [0, 4q)
     const u64 lo = c.c0 + (c.c1 << 30) + (c.c2 << 60);
     // sh in [16,58] (q of 18..60 bits).  For sh <= 30 only c0 is floored; a q below 2^30 has b1 = 0, so c2 = 0 and

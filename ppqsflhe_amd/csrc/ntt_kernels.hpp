@@ -100,20 +100,20 @@ MK_D void ct_butterfly(u64 &x, u64 &y, u64 w, u64 wp, u64 q, u64 q2) {
 }
 // the two halves of the every-other-stage schedule used by the register kernels (values < 8q throughout):
 // "c4": x in [0,8q) is first brought to [0,4q); outputs < 6q.   "nc": x in [0,6q) as is; outputs < 8q.
-MK_D void ct_butterfly_c4(u64 &x, u64 &y, u64 w, u64 wp, u64 q, u64 q2, u64 q4) {
+MK_HD void ct_butterfly_c4(u64 &x, u64 &y, u64 w, u64 wp, u64 q, u64 q2, u64 q4) {
     u64 u = csub(x, q4);
     u64 v = shoup_lazy(y, w, wp, q);
     x = u + v;
     y = u - v + q2;
 }
-MK_D void ct_butterfly_nc(u64 &x, u64 &y, u64 w, u64 wp, u64 q, u64 q2) {
+MK_HD void ct_butterfly_nc(u64 &x, u64 &y, u64 w, u64 wp, u64 q, u64 q2) {
     u64 v = shoup_lazy(y, w, wp, q);
     u64 u = x;
     x = u + v;
     y = u - v + q2;
 }
 // inverse GS butterfly on (x, y) in [0,2q): x' = x + y, y' = (x - y) w (lazy)
-MK_D void gs_butterfly(u64 &x, u64 &y, u64 w, u64 wp, u64 q, u64 q2) {
+MK_HD void gs_butterfly(u64 &x, u64 &y, u64 w, u64 wp, u64 q, u64 q2) {
     u64 s = x + y;
     u64 d = x + q2 - y;
     x = csub(s, q2);
@@ -126,31 +126,33 @@ MK_D void gs_butterfly(u64 &x, u64 &y, u64 w, u64 wp, u64 q, u64 q2) {
 // next round's first stage) are written for.
 // u - v + 3q.  3q is taken as an opaque wave-uniform pair (PmK is per limb, and a limb is fixed per workgroup): written
 // as 3 * q the compiler rebuilds it per butterfly with a multiply-add by 3 and a 32-bit add for the high word.
-MK_D u64 pm_diff(u64 u, u64 v, const PmK &P) {
+MK_HD u64 pm_diff(u64 u, u64 v, const PmK &P) {
     u64 q3 = P.q3;
+#if defined(__HIP_DEVICE_COMPILE__)
     asm("" : "+s"(q3));
+#endif
     return (u + q3) - v;
 }
-MK_D void ct_butterfly_pm_f(u64 &x, u64 &y, u64 w, u64 wx, const PmK &P) {
+MK_HD void ct_butterfly_pm_f(u64 &x, u64 &y, u64 w, u64 wx, const PmK &P) {
     const u64 u = pm_fold(x, P);
     const u64 v = pm_lazy(y, w, wx, P);
     x = u + v;
     y = pm_diff(u, v, P);
 }
-MK_D void ct_butterfly_pm_n(u64 &x, u64 &y, u64 w, u64 wx, const PmK &P) {
+MK_HD void ct_butterfly_pm_n(u64 &x, u64 &y, u64 w, u64 wx, const PmK &P) {
     const u64 v = pm_lazy(y, w, wx, P);
     const u64 u = x;
     x = u + v;
     y = pm_diff(u, v, P);
 }
 // inverse: x, y < 2.375U -> x' = fold(x + y) < 1.001U, d = x - y + 3q < 5.375U, y' = d w < 2.375U
-MK_D void gs_butterfly_pm(u64 &x, u64 &y, u64 w, u64 wx, const PmK &P) {
+MK_HD void gs_butterfly_pm(u64 &x, u64 &y, u64 w, u64 wx, const PmK &P) {
     const u64 s = x + y;
     const u64 d = pm_diff(x, y, P);
     x = pm_fold(s, P);
     y = pm_lazy(d, w, wx, P);
 }
-MK_D u64 canon8(u64 v, u64 q, u64 q2) {  // [0,8q) -> [0,q)
+MK_HD u64 canon8(u64 v, u64 q, u64 q2) {  // [0,8q) -> [0,q)
     return csub(csub(csub(v, q2 + q2), q2), q);
 }
 

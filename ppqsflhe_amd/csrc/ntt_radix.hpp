@@ -211,7 +211,7 @@ MK_D void load_rowb_twiddles(const u64 *__restrict__ twb_limb, uint32_t row, int
 // before the butterfly (outputs < 6q), odd stages skip the correction (outputs < 8q) -- half the
 // conditional subtractions of the classic Harvey schedule; 8q < 2^63 since q < 2^60.
 template <int LOG_H>
-MK_D void radix_forward(u64 (&x)[1 << LOG_H], const u64 (&w)[(1 << LOG_H) - 1], const u64 (&wp)[(1 << LOG_H) - 1],
+MK_HD void radix_forward(u64 (&x)[1 << LOG_H], const u64 (&w)[(1 << LOG_H) - 1], const u64 (&wp)[(1 << LOG_H) - 1],
                         u64 q, u64 q2) {
     constexpr int H = 1 << LOG_H;
     const u64 q4 = q2 + q2;
@@ -229,7 +229,7 @@ MK_D void radix_forward(u64 (&x)[1 << LOG_H], const u64 (&w)[(1 << LOG_H) - 1], 
 
 // log2(H) inverse stages on H registers (stage order reversed); values stay in [0,2q)
 template <int LOG_H>
-MK_D void radix_inverse(u64 (&x)[1 << LOG_H], const u64 (&w)[(1 << LOG_H) - 1], const u64 (&wp)[(1 << LOG_H) - 1],
+MK_HD void radix_inverse(u64 (&x)[1 << LOG_H], const u64 (&w)[(1 << LOG_H) - 1], const u64 (&wp)[(1 << LOG_H) - 1],
                         u64 q, u64 q2) {
     constexpr int H = 1 << LOG_H;
 #pragma unroll
@@ -246,7 +246,7 @@ MK_D void radix_inverse(u64 (&x)[1 << LOG_H], const u64 (&w)[(1 << LOG_H) - 1], 
 // the same rounds with the pseudo-Mersenne butterflies (LimbConst::pm; bounds next to ct_butterfly_pm_f): inputs < 8U,
 // outputs < 7.001U forward; inputs and outputs < 2.375U inverse
 template <int LOG_H>
-MK_D void radix_forward_pm(u64 (&x)[1 << LOG_H], const u64 (&w)[(1 << LOG_H) - 1], const u64 (&wx)[(1 << LOG_H) - 1],
+MK_HD void radix_forward_pm(u64 (&x)[1 << LOG_H], const u64 (&w)[(1 << LOG_H) - 1], const u64 (&wx)[(1 << LOG_H) - 1],
                            const PmK &P) {
     constexpr int H = 1 << LOG_H;
 #pragma unroll
@@ -261,7 +261,7 @@ MK_D void radix_forward_pm(u64 (&x)[1 << LOG_H], const u64 (&w)[(1 << LOG_H) - 1
     }
 }
 template <int LOG_H>
-MK_D void radix_inverse_pm(u64 (&x)[1 << LOG_H], const u64 (&w)[(1 << LOG_H) - 1], const u64 (&wx)[(1 << LOG_H) - 1],
+MK_HD void radix_inverse_pm(u64 (&x)[1 << LOG_H], const u64 (&w)[(1 << LOG_H) - 1], const u64 (&wx)[(1 << LOG_H) - 1],
                            const PmK &P) {
     constexpr int H = 1 << LOG_H;
 #pragma unroll

@@ -2,6 +2,7 @@
 #include "params.hpp"
 
 #include <cmath>
+#include <cstring>
 #include <stdexcept>
 #include <string>
 
@@ -139,6 +140,37 @@ u64 product_mod(const std::vector<u64> &mods, const std::vector<uint32_t> &ids, 
 
 }  // namespace
 
+LimbConst make_limb_const(u64 q, u64 n) {
+    LimbConst c{};
+    c.q = q; c.q2 = 2 * q;
+    c.k = 64 - (uint32_t)__builtin_clzll(q);
+    c.sh = c.k - 2;
+    c.mu = (u64)(((u128)1 << (62 + c.k)) / q);
+    c.c64 = (u64)(((u128)1 << 64) % q);
+    c.ninv = h_invmod(n % q, q);
+    c.ninv_sh = h_shoup(c.ninv, q);
+    c.qd = (double)q;
+    c.qinv = (double)(1.0L / (long double)q);
+    c.ninv_d = (double)c.ninv;
+    c.ninv_qd = (double)((long double)c.ninv / (long double)q);
+    c.fp = 0;  // the engine decides (needs both passes on the radix kernels)
+    c.pm = 0;  // the engine decides (integer limbs of the form 2^k - c)
+    c.pm_c = 0;
+    c.pad_ = 0;
+    return c;
+}
+
+void fp_table_entry(u64 w, u64 q, u64 &wd_bits, u64 &wq_bits) {
+    const double wd = (double)w, wq = (double)((long double)w / (long double)q);
+    std::memcpy(&wd_bits, &wd, 8);
+    std::memcpy(&wq_bits, &wq, 8);
+}
+
+void pm_table_entry(u64 w, const LimbConst &L, u64 &wt, u64 &wxt) {
+    wxt = pm_tw_companion(w, L);
+    wt = pm_tw(w, L);
+}
+
 void ParamSet::generate(uint32_t log_n_, uint32_t depth, uint32_t sbits, uint32_t fbits, uint32_t dn,
                         uint32_t abits, uint32_t ebits) {
     if (log_n_ < 8 || log_n_ > 17) throw std::invalid_argument("log_n must be in [8,17]");
@@ -206,22 +238,7 @@ void ParamSet::generate(uint32_t log_n_, uint32_t depth, uint32_t sbits, uint32_
     for (uint32_t i = 0; i < D; ++i) {
         u64 q = moduli[i];
         roots[i] = h_min_primitive_root(walk.step, q);
-        LimbConst &c = limb[i];
-        c.q = q; c.q2 = 2 * q;
-        c.k = 64 - (uint32_t)__builtin_clzll(q);
-        c.sh = c.k - 2;
-        c.mu = (u64)(((u128)1 << (62 + c.k)) / q);
-        c.c64 = (u64)(((u128)1 << 64) % q);
-        c.ninv = h_invmod(n % q, q);
-        c.ninv_sh = h_shoup(c.ninv, q);
-        c.qd = (double)q;
-        c.qinv = (double)(1.0L / (long double)q);
-        c.ninv_d = (double)c.ninv;
-        c.ninv_qd = (double)((long double)c.ninv / (long double)q);
-        c.fp = 0;  // the engine decides (needs both passes on the radix kernels)
-        c.pm = 0;  // the engine decides (integer limbs of the form 2^k - c)
-        c.pm_c = 0;
-        c.pad_ = 0;
+        limb[i] = make_limb_const(q, n);
     }
 
     // scaling factors (FLEXIBLEAUTOEXT): sf[0] = extra limb, sf[1] = q_{L-2}, then sf^2/q going down

@@ -24,6 +24,13 @@ bool h_is_prime(u64 n);
 u64 h_shoup(u64 w, u64 q);
 u64 h_min_primitive_root(u64 order, u64 q);
 
+// reduction constants of one modulus q (odd, 2^17 < q < 2^60) for ring dimension n; fp / pm are left 0 for the engine
+LimbConst make_limb_const(u64 q, u64 n);
+// NTT table entries of the twiddle w as the fp64 and the pseudo-Mersenne limbs hold them (the engine's tables and the
+// arithmetic probe are built from these): (double) w and w / q as bit patterns; w << t and (w * 2^32 mod q) << t
+void fp_table_entry(u64 w, u64 q, u64 &wd_bits, u64 &wq_bits);
+void pm_table_entry(u64 w, const LimbConst &L, u64 &wt, u64 &wxt);
+
 // Tables for one approximate base conversion (ApproxSwitchCRTBasis):
 // source limbs S = {s_i}, target limbs T = {t_j}.
 struct BaseConvTable {

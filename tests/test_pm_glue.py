@@ -9,6 +9,8 @@ bound and every stored bit rests on each of them returning the same 64-bit word 
   carry seen.
 * GPU (`-m gpu`): the HIP kernels that are built from these primitives against the oracle, bit for bit, at the smallest
   ring the radix kernels and the merged n-client flow serve (the reference's N = 2^14, L = 4, dnum = 2).
+* The device forms themselves, one primitive at a time and at the edges of their ranges (a just below 8U, X just below
+  2^(2k+6), both values of every carry), are compared word for word with the host forms in tests/test_device_arith.py.
 """
 import os
 import re

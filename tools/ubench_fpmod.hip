@@ -86,17 +86,11 @@ __global__ void k_check_pm(const u64 *seeds, u64 q, uint32_t k, unsigned long lo
     atomicAdd(carries, ncarry);
 }
 
-// v = y*w - b*q exactly, |v| <= 1.5 q for |y| <= 2^52  (y, w integers held in doubles; wq = w/q rounded)
-__device__ __forceinline__ double fp_mulmod(double y, double w, double wq, double q) {
-    double h = y * w;
-    double l = fma(y, w, -h);
-    double b = rint(y * wq);
-    double c = fma(-b, q, h);
-    return c + l;
-}
-__device__ __forceinline__ double fp_reduce(double x, double q, double qinv) {  // |result| <= q/2 (+1)
-    return fma(-rint(x * qinv), q, x);
-}
+// the library's own fp64 primitives (modarith.hpp: __dmul_rn / __fma_rn, no contraction left to the compiler): what is
+// timed and checked here is the code that ships.  v = y*w - b*q exactly, |v| <= 1.5 q for |y| <= 2^52 (y, w integers held in
+// doubles; wq = w/q rounded); fp_reduce: |result| <= q/2 (+1)
+using mk::fp_mulmod;
+using mk::fp_reduce;
 
 // exactness: random |y| <= 4q, w < q; compare (fp result mod q) with integer y*w mod q
 __global__ void k_check(const u64 *seeds, u64 q, unsigned long long *bad, double *maxabs, int iters) {
