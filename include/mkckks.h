@@ -437,6 +437,42 @@ int mkckks_partial_decrypt_batch(mkckks_ctx *c, const uint64_t *d_ct, const uint
  * caller guarantees that exactly ONE share was made with lead != 0 (the hosts check it from the share headers). */
 int mkckks_fuse_shares_batch(mkckks_ctx *c, const uint64_t *d_shares, uint64_t *d_m, uint32_t n_parties, uint32_t n_ct,
                              uint32_t nl);
+/* ---- collective public-key switch: deliver the joint-key aggregate instead of opening it ----------------------------
+ * (Mouchet et al., "Multiparty homomorphic encryption from ring-learning-with-errors", the PCKS protocol.)  Each party
+ * adds to its c1 * s_p term an encryption of zero under the RECIPIENT's public key pk = (b, a); for t < n_ct, i < nl, in
+ * EVALUATION form with canonical residues:
+ *     share[t][0][i] = ct[t][1][i] * sk[i] + (lead ? ct[t][0][i] : 0) + pk[0][i] * NTT_i(v_t) + NTT_i(e0_t)   mod q_i
+ *     share[t][1][i] =                                                  pk[1][i] * NTT_i(v_t) + NTT_i(e1_t)   mod q_i
+ * Layouts and contracts of the two entry points it merges: d_ct u64[n_ct][2][nl_in][N] read at its first nl limbs (a
+ * lower level is a prefix); d_sk u64[D][N] addressed by limb id, limbs < nl only, so a key share u64[L][N]
+ * (lambda_j * sigma_j of the t-of-n section below) is a key; d_pk u64[2][D][N] the recipient's public key, addressed by
+ * limb id; d_v int8[n_ct][N] ternary; d_e0 / d_e1 int64[n_ct][N] with |e| < 2^62 (mkckks_sample_gauss_wide keeps it);
+ * d_share out u64[n_ct][2][nl][N].  Every pointer is required.  1 <= nl <= nl_in <= L; d_share must not overlap d_ct
+ * (MKCKKS_E_INVALID); n_ct == 0 is a no-op; a host-only context returns MKCKKS_E_NODEVICE.
+ * Fusion needs no entry point of its own: the component-wise sum of the parties' shares is mkckks_eval_sum_batch, and
+ * the result is decrypted by mkckks_decrypt_batch under the recipient's secret key.
+ * The algebra: with S = sum_p s_p the joint secret, U = sum_p v_p, E0 = sum_p e0_p, E1 = sum_p e1_p and exactly one lead,
+ *     sum_p share_p = (c0 + c1 * S + b * U + E0,  a * U + E1),
+ * a ciphertext under the recipient's key s_out (b = -a * s_out + e_pk): it decrypts to m + e_agg + U * e_pk + E0 + E1 * s_out.
+ * Nobody on the way sees m: c1 * S exists only masked by b * U.
+ * Noise rule: per-coefficient variance n * (sigma0^2 + h * sigma1^2 + (2N/3) * sigma_pk^2) for n parties, sigma0 / sigma1
+ * the deviations of e0 / e1, sigma_pk that of the recipient key's error and h the number of non-zero coefficients of
+ * s_out; the decoded values carry a Gaussian error of standard deviation sqrt(that * N / 2) / scale.  With a smudging
+ * sigma0 >= 2^10 and the standard sigma1 this is mkckks_partial_decrypt_batch's rule sigma0 * sqrt(n * N / 2) / scale to
+ * within 10^-3.
+ * Composition equality: the share is bit-identical to, in this order, mkckks_partial_decrypt_batch(e = 0),
+ * mkckks_ntt_forward_batch, and mkckks_rerandomize_batch on the ciphertext whose component 0 is that result and whose
+ * component 1 is zero -- at three times the passes, and with the unsmudged INTT(c1 * s_p) in memory on the way.
+ * Security rules: e0 is the SMUDGING error (wide: mkckks_sample_gauss_wide at the deployment's sigma, as in
+ * mkckks_partial_decrypt_batch), e1 an ordinary encryption error (the scheme's standard sigma).  The recipient can compute
+ * share0 + share1 * s_out = c1 * s_p (+ c0) + smudge (+ small) for every party: the view mkckks_partial_decrypt_batch
+ * gives everybody.  So "ONE share per ciphertext per party" becomes a budget: r recipients of one aggregate receive r
+ * independently smudged copies of c1 * s_p, which average the smudging down by sqrt(r) -- add log2(r) / 2 bits of
+ * smudging for r recipients.  Fresh (v, e0, e1) per call, drawn under keys that key nothing else.  With key shares, all
+ * shares that are summed must have been made with the SAME set T and for the SAME recipient, or they sum to noise. */
+int mkckks_switch_share_batch(mkckks_ctx *c, const uint64_t *d_ct, const uint64_t *d_sk, const uint64_t *d_pk,
+                              const int8_t *d_v, const int64_t *d_e0, const int64_t *d_e1, uint64_t *d_share, uint32_t n_ct,
+                              uint32_t nl_in, uint32_t nl, int lead);
 
 /* ==== t-of-n threshold decryption: Shamir shares of the joint secret ============================================
  * (Mouchet et al., "An efficient threshold access-structure for RLWE-based multiparty homomorphic encryption".)

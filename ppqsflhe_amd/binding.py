@@ -86,6 +86,7 @@ SYMBOLS = {
     "mkckks_keygen_join": (_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "mkckks_partial_decrypt_batch": (_int, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _int]),
     "mkckks_fuse_shares_batch": (_int, [_vp, _vp, _vp, _u32, _u32, _u32]),
+    "mkckks_switch_share_batch": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _int]),
     "mkckks_share_key": (_int, [_vp, _vp, _vp, _u32, _u32, _u32, C.c_char_p, _u32]),
     "mkckks_combine_key_shares": (_int, [_vp, _vp, _vp, _vp, _u32, _u32]),
     "mkckks_lagrange_at_zero": (_int, [_vp, _vp, _u32, _vp]),
@@ -610,6 +611,20 @@ class Context:
     def fuse_shares(self, shares, m, n_parties, n_ct, nl):
         """m = sum of shares[p] (MultipartyDecryptFusion), in the layout of `decrypt`; m may be shares[0]."""
         self._check(self._L.mkckks_fuse_shares_batch(self._h, _ptr(shares), _ptr(m), n_parties, n_ct, nl))
+
+    def switch_share(self, ct, sk, pk, v, e0, e1, nl, lead=False, out=None):
+        """One party's share of the collective key switch of ct u64[n_ct][2][nl_in][N] (a joint-key ciphertext batch) to
+        the RECIPIENT's public key pk, on the first nl limbs: (c1 * sk (+ c0 when lead) + pk0 * NTT(v) + NTT(e0),
+        pk1 * NTT(v) + NTT(e1)), u64[n_ct][2][nl][N], returned (or written to `out`).  v int8 ternary, e0 int64 smudging
+        errors, e1 int64 encryption errors, fresh for every call; exactly one party passes lead.  The parties' shares sum
+        (eval_sum) to a ciphertext under the recipient's key.  sk may be a key share lambda_j * sigma_j."""
+        n_ct, parts, nl_in, n = ct.shape
+        if parts != 2 or n != self.N:
+            raise ValueError("switch_share: ct must be shaped [n_ct][2][nl_in][N]")
+        share = self.empty((n_ct, 2, nl, n), np.uint64) if out is None else out
+        self._check(self._L.mkckks_switch_share_batch(self._h, _ptr(ct), _ptr(sk), _ptr(pk), _ptr(v), _ptr(e0), _ptr(e1),
+                                                      _ptr(share), n_ct, nl_in, nl, int(bool(lead))))
+        return share
 
     # ---- t-of-n threshold decryption (include/mkckks.h: "t-of-n threshold decryption")
     def share_key(self, sk, shares, nl, n_parties, threshold, key, stream_id=0):

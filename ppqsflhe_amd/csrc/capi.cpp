@@ -526,6 +526,21 @@ int mkckks_partial_decrypt_batch(mkckks_ctx *c, const uint64_t *ct, const uint64
         c->eng->partial_decrypt(ct, sk, e, share, n_ct, nl_in, nl, lead != 0);
     });
 }
+int mkckks_switch_share_batch(mkckks_ctx *c, const uint64_t *ct, const uint64_t *sk, const uint64_t *pk, const int8_t *v,
+                              const int64_t *e0, const int64_t *e1, uint64_t *share, uint32_t n_ct, uint32_t nl_in, uint32_t nl,
+                              int lead) {
+    return guarded([&] {
+        need(c && ct && sk && pk && v && e0 && e1 && share, "null argument");
+        const mk::ParamSet &ps = c->eng->params();
+        need(nl >= 1 && nl <= nl_in && nl_in <= ps.L, "need 1 <= nl <= nl_in <= L");
+        const size_t item_bytes = (size_t)n_ct * 2 * ps.n * sizeof(uint64_t);  // addresses only
+        const uintptr_t i_lo = (uintptr_t)ct, i_hi = i_lo + item_bytes * nl_in;
+        const uintptr_t o_lo = (uintptr_t)share, o_hi = o_lo + item_bytes * nl;
+        need(!(o_lo < i_hi && i_lo < o_hi), "share overlaps the ciphertexts");
+        if (!n_ct) return;
+        c->eng->switch_share(ct, sk, pk, v, e0, e1, share, n_ct, nl_in, nl, lead != 0);
+    });
+}
 int mkckks_fuse_shares_batch(mkckks_ctx *c, const uint64_t *shares, uint64_t *m, uint32_t n_parties, uint32_t n_ct,
                              uint32_t nl) {
     return guarded([&] {

@@ -2505,6 +2505,91 @@ void Engine::partial_decrypt(const u64 *ct, const u64 *sk, const int64_t *e, u64
     }
 }
 
+// ---- collective public-key switch: one party's share (Mouchet et al., PCKS) -----------------------------------------
+
+template <int COL_H, int ROW_H>
+static void launch_kswitch(LiftIo li, KswitchArgs ka, const NttTables &T, uint32_t cnt, hipStream_t s) {
+    const uint32_t r1 = 1u << T.log_r1, r2 = 1u << T.log_r2;
+    NttIo sel{};
+    sel.nslots = sel.nl = ka.nl;
+    for (int fp = 0; fp < 2; ++fp) {
+        const unsigned long long mask = class_mask(sel, T.h_fp_of, T.L, fp != 0);
+        const uint32_t nsel = (uint32_t)__builtin_popcountll(mask);
+        if (!nsel) continue;
+        li.slot_mask = ka.slot_mask = mask;
+        li.nsel = ka.nsel = nsel;
+        const dim3 cgrid(r2 / (256u >> COL_H), 3 * nsel, cnt), rgrid((r1 / (256u >> ROW_H)) * nsel * cnt);
+        if (fp) {
+            k_lift_col<COL_H, AR_FP><<<cgrid, NTT_THREADS, 0, s>>>(li, T);
+            k_kswitch_row<ROW_H, AR_FP><<<rgrid, NTT_THREADS, 0, s>>>(ka, T);
+        } else {
+            with_int_arith(T, [&](auto ar) {
+                k_lift_col<COL_H, decltype(ar)::value><<<cgrid, NTT_THREADS, 0, s>>>(li, T);
+                k_kswitch_row<ROW_H, decltype(ar)::value><<<rgrid, NTT_THREADS, 0, s>>>(ka, T);
+            });
+        }
+    }
+}
+template <int COL_H>
+static void launch_kswitch_c(const LiftIo &li, const KswitchArgs &ka, const NttTables &T, uint32_t cnt, int row_h, hipStream_t s) {
+    switch (row_h) {
+        case 4: launch_kswitch<COL_H, 4>(li, ka, T, cnt, s); break;
+        case 3: launch_kswitch<COL_H, 3>(li, ka, T, cnt, s); break;
+        default: launch_kswitch<COL_H, 2>(li, ka, T, cnt, s);
+    }
+}
+
+void Engine::switch_share(const u64 *ct, const u64 *sk, const u64 *pk, const int8_t *v, const int64_t *e0, const int64_t *e1,
+                          u64 *share, uint32_t n_ct, uint32_t nl_in, uint32_t nl, bool lead) {
+    need_device();
+    check_nl(nl);
+    check_nl(nl_in);
+    if (nl > nl_in) throw std::invalid_argument("need nl <= nl_in");
+    if (!n_ct) return;
+    const uint32_t n = ps_.n, D = ps_.D;
+    const size_t poly = (size_t)nl * n;
+    // fused: lift inside the column pass, c1 * s (+ c0) and the mask inside the row pass's copy-outs (two-round rows only);
+    // the library switches take the composition
+    const int col_h = fast_log_h(tabs_.log_r1, 1u << tabs_.log_r2), row_h = fast_row(tabs_.log_r2, 1u << tabs_.log_r1);
+    const bool fused = col_h != 0 && row_h >= 2 && row_h <= 4 && !knobs_.generic_ntt && !knobs_.no_fp64 && !knobs_.no_pm;
+    const uint32_t chunk = knobs_.chunk;
+    const uint32_t cmax = n_ct < chunk ? n_ct : chunk;
+    u64 *ws = workspace((fused ? 3 : 4) * poly * cmax);
+    for (uint32_t b0 = 0; b0 < n_ct; b0 += chunk) {
+        const uint32_t cnt = n_ct - b0 < chunk ? n_ct - b0 : chunk;
+        const u64 *cin = ct + (size_t)b0 * 2 * nl_in * n;
+        u64 *cout = share + (size_t)b0 * 2 * poly;
+        const int8_t *vb = v + (size_t)b0 * n;
+        const int64_t *e0b = e0 + (size_t)b0 * n, *e1b = e1 + (size_t)b0 * n;
+        if (fused) {
+            const LiftIo li{vb, e0b, e1b, ws, nl, 0, 0};
+            const KswitchArgs ka{ws, cin, sk, pk, cout, nl_in, nl, D, lead ? 1u : 0u, 0, 0};
+            switch (col_h) {
+                case 4: launch_kswitch_c<4>(li, ka, tabs_, cnt, row_h, stream_); break;
+                case 3: launch_kswitch_c<3>(li, ka, tabs_, cnt, row_h, stream_); break;
+                default: launch_kswitch_c<2>(li, ka, tabs_, cnt, row_h, stream_);
+            }
+            MK_HIP(hipGetLastError());
+        } else {  // Engine::rerandomize's composition on the ciphertext (c1 * s (+ c0), 0): x from one k_fma into the workspace
+            u64 *ve = ws, *e0e = ve + poly * cnt, *e1e = e0e + poly * cnt, *x = ws + 3 * poly * cmax;
+            EwGeom g{n, nl, ps_.L};
+            k_lift<int8_t><<<ew_grid(n, nl, cnt), EW_THREADS, 0, stream_>>>(vb, ve, g, d_limb_, nl);
+            k_lift<int64_t><<<ew_grid(n, nl, cnt), EW_THREADS, 0, stream_>>>(e0b, e0e, g, d_limb_, nl);
+            k_lift<int64_t><<<ew_grid(n, nl, cnt), EW_THREADS, 0, stream_>>>(e1b, e1e, g, d_limb_, nl);
+            MK_HIP(hipGetLastError());
+            ntt_launch(ve, 3 * cnt, nl, nl, false, nullptr, nullptr);
+            const size_t cstride = (size_t)2 * nl_in * n;
+            Opnd c1{cin + (size_t)nl_in * n, cstride, 0}, s{sk, 0, 1}, c0{lead ? cin : nullptr, cstride, 0}, none{nullptr, 0, 0};
+            k_fma<<<ew_grid(n, nl, cnt), EW_THREADS, 0, stream_>>>(c1, s, c0, none, nullptr, 0, x, poly, 0, g, d_limb_, nl);
+            Opnd p0{pk, 0, 1}, p1{pk + (size_t)D * n, 0, 1}, vv{ve, poly, 0}, z0{e0e, poly, 0}, z1{e1e, poly, 0}, xx{x, poly, 0};
+            k_fma<<<ew_grid(n, nl, cnt), EW_THREADS, 0, stream_>>>(p0, vv, z0, xx, nullptr, 0, cout, 2 * poly, 0, g, d_limb_, nl);
+            k_fma<<<ew_grid(n, nl, cnt), EW_THREADS, 0, stream_>>>(p1, vv, z1, none, nullptr, 0, cout + poly, 2 * poly, 0, g,
+                                                                 d_limb_, nl);
+            MK_HIP(hipGetLastError());
+        }
+    }
+}
+
 void Engine::fuse_shares(const u64 *shares, u64 *m, uint32_t n_parties, uint32_t n_ct, uint32_t nl) {
     need_device();
     check_nl(nl);

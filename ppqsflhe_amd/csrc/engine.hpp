@@ -161,6 +161,12 @@ public:
     void partial_decrypt(const u64 *ct, const u64 *sk, const int64_t *e, u64 *share, uint32_t n_ct, uint32_t nl_in,
                          uint32_t nl, bool lead);
     void fuse_shares(const u64 *shares, u64 *m, uint32_t n_parties, uint32_t n_ct, uint32_t nl);
+    // collective public-key switch, one party's share: share[t] = (c1 * sk (+ c0 when lead) + pk0 * NTT(v) + NTT(e0),
+    // pk1 * NTT(v) + NTT(e1)) on the first nl limbs of ct u64[n_ct][2][nl_in][N]; pk the RECIPIENT's; v, e0, e1 as
+    // rerandomize; share u64[n_ct][2][nl][N], EVALUATION, canonical, never ct.  The parties' shares sum to a ciphertext
+    // under pk (eval_sum)
+    void switch_share(const u64 *ct, const u64 *sk, const u64 *pk, const int8_t *v, const int64_t *e0, const int64_t *e1,
+                      u64 *share, uint32_t n_ct, uint32_t nl_in, uint32_t nl, bool lead);
     // t-of-n sharing of a key.  share_key: shares u64[n_parties][nl][N], share p = sk + sum_{k=1}^{t-1} r_k (p+1)^k mod q_i
     // with r_k = sample_uniform(1 poly, nl, Q only) of stream (key32, sid0 + k - 1), never written to memory.
     // combine_key_shares: out u64[nl][N] = sum_{j<m} w[j][i] * in[j][i] mod q_i; w HOST u64[m][nl], canonical; out may be in[0]

@@ -2438,6 +2438,90 @@ __global__ __launch_bounds__(NTT_THREADS) void k_rerand_row(RerandArgs a, NttTab
 }
 
 // =====================================================================================
+// Collective public-key switch, one party's share (mkckks_switch_share_batch; Engine::switch_share):
+//   share0 = ct1 * s (+ ct0 on the lead share) + b * NTT(v) + NTT(e0),  share1 = a * NTT(v) + NTT(e1)   per limb,
+// (b, a) the RECIPIENT's public key.  k_lift_col unchanged, then k_rerand_row's row pass with another copy-out: c1 * s
+// exists only in registers, between its two loads and the store of share0.
+// =====================================================================================
+
+struct KswitchArgs {
+    const u64 *col;    // [items][3][nl][N] from k_lift_col
+    const u64 *ct;     // [items][2][nl_in][N], first nl limbs read
+    const u64 *sk;     // [D][N] (or a key share [L][N]), addressed by limb id, limbs < nl only
+    const u64 *pk;     // [2][D][N], addressed by limb id
+    u64 *out;          // [items][2][nl][N]; never ct
+    uint32_t nl_in, nl, D, lead;
+    unsigned long long slot_mask;
+    uint32_t nsel;
+};
+
+// k_rerand_row (VLDS layout: V in a tile of its own, E0 / E1 through a second one) whose copy-outs form the share: E0's
+// loads the thread's pairs of c1 and s (and c0 when lead) beside b and writes c1 s (+ c0) + (b V + E0); E1's writes
+// a V + E1 and loads no ciphertext.  Products as k_fma / k_pdec_row (mul_mod on canonical words, every arithmetic class).
+// A kernel of its own, not a mode of k_rerand_row: the instance the re-encryption round ships does not move.
+template <int LOG_H, int AR>
+__global__ __launch_bounds__(NTT_THREADS) void k_kswitch_row(KswitchArgs a, NttTables T) {
+    using TL = RowTile<LOG_H>;
+    using TA = RowTwA<LOG_H>;
+    constexpr int H = TL::H, S = TL::S, R = TL::R, PAIRS = S * R / 2 / NTT_THREADS;
+    __shared__ u64 lds[2 * TL::WORDS + 2 * TA::WORDS];
+    u64 *lds_e = lds + TL::WORDS;  // tile of E0 / E1
+    u64 *twa = lds_e + TL::WORDS, *twa_sh = twa + TA::WORDS;
+    const uint32_t n = 1u << T.log_n, r1 = 1u << T.log_r1;
+    const uint32_t tiles = r1 / S, groups = tiles * a.nsel, items = gridDim.x / groups;
+    uint32_t grp, item;
+    group_member(blockIdx.x, groups, items, T.cu_affine, grp, item);
+    const uint32_t sl = nth_set_bit(a.slot_mask, grp / tiles);  // Q limb: slot == limb id
+    const LimbConst lc = T.limb[sl];
+    if ((lc.fp != 0) != (AR == AR_FP)) return;  // block-uniform
+    const uint32_t row0 = (grp % tiles) * S;
+    const int g = threadIdx.x / H, j = threadIdx.x % H;
+    const size_t poly = (size_t)a.nl * n, tile = (size_t)sl * n + (size_t)row0 * R;
+    const u64 *col = a.col + (size_t)item * 3 * poly + tile;
+    const u64 *twb = T.twb + (size_t)sl * 2 * n;
+    stage_twiddles_wave<LOG_H>(twa, twa_sh, T.tw + (size_t)sl * n, T.tw_sh + (size_t)sl * n, r1 + row0);
+    wave_lds_sync();
+
+    rerand_row_forward<LOG_H, AR>(col, lds, twa, twa_sh, twb, row0, g, j, lc);
+    const ulong2 *pk0 = reinterpret_cast<const ulong2 *>(a.pk + tile), *pk1 = reinterpret_cast<const ulong2 *>(a.pk + (size_t)a.D * n + tile);
+    const ulong2 *c0 = reinterpret_cast<const ulong2 *>(a.ct + (size_t)item * 2 * a.nl_in * n + tile);
+    const ulong2 *c1 = c0 + (size_t)a.nl_in * n / 2;
+    const ulong2 *sk = reinterpret_cast<const ulong2 *>(a.sk + tile);
+    u64 *o0 = a.out + (size_t)item * 2 * poly + tile;
+    rerand_row_forward<LOG_H, AR>(col + poly, lds_e, twa, twa_sh, twb, row0, g, j, lc);
+#pragma unroll
+    for (int i = 0; i < PAIRS; ++i) {
+        const int e = wave_pair<LOG_H>(i);
+        const int gg = (2 * e) / R, xx = (2 * e) % R;
+        const ulong2 c = ld_pass2(c1 + e), s = sk[e], k = pk0[e];
+        ulong2 x{mul_mod(c.x, s.x, lc), mul_mod(c.y, s.y, lc)};
+        if (a.lead) {
+            const ulong2 b = ld_pass2(c0 + e);
+            x.x = add_mod(x.x, b.x, lc.q);
+            x.y = add_mod(x.y, b.y, lc.q);
+        }
+        const u64 bvx = mul_mod(k.x, lds[TL::at(gg, xx)], lc), bvy = mul_mod(k.y, lds[TL::at(gg, xx + 1)], lc);
+        ulong2 r;
+        r.x = add_mod(x.x, add_mod(bvx, lds_e[TL::at(gg, xx)], lc.q), lc.q);
+        r.y = add_mod(x.y, add_mod(bvy, lds_e[TL::at(gg, xx + 1)], lc.q), lc.q);
+        st_pass2(reinterpret_cast<ulong2 *>(o0) + e, r);
+    }
+
+    rerand_row_forward<LOG_H, AR>(col + 2 * poly, lds_e, twa, twa_sh, twb, row0, g, j, lc);
+    u64 *o1 = o0 + poly;
+#pragma unroll
+    for (int i = 0; i < PAIRS; ++i) {
+        const int e = wave_pair<LOG_H>(i);
+        const int gg = (2 * e) / R, xx = (2 * e) % R;
+        const ulong2 k = pk1[e];
+        ulong2 r;
+        r.x = add_mod(mul_mod(k.x, lds[TL::at(gg, xx)], lc), lds_e[TL::at(gg, xx)], lc.q);
+        r.y = add_mod(mul_mod(k.y, lds[TL::at(gg, xx + 1)], lc), lds_e[TL::at(gg, xx + 1)], lc.q);
+        st_pass2(reinterpret_cast<ulong2 *>(o1) + e, r);
+    }
+}
+
+// =====================================================================================
 // Partial (threshold) decryption (mkckks_partial_decrypt_batch; Engine::partial_decrypt):
 //   share = INTT(c1 * s (+ c0 on the lead share)) + (e mod q)   per limb, COEFFICIENT format, canonical.
 // The mirror image of k_lift_col / k_rerand_row: the product is formed in the loads of the first inverse pass and the

@@ -113,6 +113,8 @@ struct BlobHeader {
 static_assert(sizeof(BlobHeader) == 48, "blob header layout");
 
 enum : uint32_t { KIND_CT = 1, KIND_PK = 2, KIND_SK = 3, KIND_RK = 4, KIND_CT_SEEDED = 5 };
+// 6: decryption share (share.hpp), 7: key share (keyshare.hpp), 8: key-switch share (switchshare.hpp)
+enum : uint32_t { KIND_SWITCH_SHARE = 8 };
 
 // Seeded ciphertext (KIND_CT_SEEDED, written by encryptModelWeights --seeded): the header of a full ciphertext with
 // parts = 1, then this trailer, then c0 as u64[nl][N] -- 48 + 40 + 8 nl N bytes.  c1 is regenerated on the device from
