@@ -14,6 +14,7 @@
 // workgroup (blockIdx.y), so all per-limb constants sit in SGPRs.
 #include "engine.hpp"
 #include "comm.hpp"
+#include "dispatch.hpp"
 #include "ntt_radix.hpp"
 #include "qsum_kernels.hpp"
 #include "fanout_kernels.hpp"
@@ -718,8 +719,6 @@ Engine::~Engine() {
     }
 }
 
-Lanes Engine::lanes() const { return Lanes{stream_}; }
-
 void Engine::need_device() const {
     if (device_ < 0) throw NoDevice("host-only context: no device operations");
 }
@@ -947,25 +946,13 @@ int Engine::conv_src_mode(const DevConv &cv) const {
     return (!fp_of_[cv.src_id[0]] && rest_fp) ? 2 : -1;
 }
 
-template <int N_IN>
-static void launch_baseconv_n(const u64 *in, size_t in_stride, u64 *out, size_t out_stride, const DevConv &cv,
-                              const LimbConst *limb, uint32_t n, uint32_t items, int prescaled, hipStream_t s) {
-    dim3 grid((n + EW_THREADS - 1) / EW_THREADS, items);
-    k_baseconv<N_IN><<<grid, EW_THREADS, 0, s>>>(in, in_stride, out, out_stride, cv, limb, n, prescaled);
-}
 static void launch_baseconv(const u64 *in, size_t in_stride, u64 *out, size_t out_stride, const DevConv &cv,
                             const LimbConst *limb, uint32_t n, uint32_t items, int prescaled, hipStream_t s) {
-    switch (cv.n_in) {
-        case 1: launch_baseconv_n<1>(in, in_stride, out, out_stride, cv, limb, n, items, prescaled, s); break;
-        case 2: launch_baseconv_n<2>(in, in_stride, out, out_stride, cv, limb, n, items, prescaled, s); break;
-        case 3: launch_baseconv_n<3>(in, in_stride, out, out_stride, cv, limb, n, items, prescaled, s); break;
-        case 4: launch_baseconv_n<4>(in, in_stride, out, out_stride, cv, limb, n, items, prescaled, s); break;
-        case 5: launch_baseconv_n<5>(in, in_stride, out, out_stride, cv, limb, n, items, prescaled, s); break;
-        case 6: launch_baseconv_n<6>(in, in_stride, out, out_stride, cv, limb, n, items, prescaled, s); break;
-        case 7: launch_baseconv_n<7>(in, in_stride, out, out_stride, cv, limb, n, items, prescaled, s); break;
-        case 8: launch_baseconv_n<8>(in, in_stride, out, out_stride, cv, limb, n, items, prescaled, s); break;
-        default: throw std::invalid_argument("base conversion fan-in unsupported");
-    }
+    const dim3 grid((n + EW_THREADS - 1) / EW_THREADS, items);
+    if (!dispatch<1, 2, 3, 4, 5, 6, 7, 8>(cv.n_in, [&](auto n_in) {
+            k_baseconv<decltype(n_in)::value><<<grid, EW_THREADS, 0, s>>>(in, in_stride, out, out_stride, cv, limb, n, prescaled);
+        }))
+        throw std::invalid_argument("base conversion fan-in unsupported");
     MK_HIP(hipGetLastError());
 }
 
@@ -984,15 +971,6 @@ static int fast_row(uint32_t log_r2, uint32_t rows) {
     return fast_log_h(log_r2, rows);
 }
 
-// The integer and the fp64 instance of a pass touch disjoint limbs and are launched one after the other on the same
-// stream (forking them onto two streams was measured slower: -5 %, event round trips).
-template <typename FInt, typename FFp>
-static void launch_two_classes(const Lanes &ln, bool has_int, bool has_fp, FInt &&launch_int, FFp &&launch_fp) {
-    if (has_int) launch_int(ln.main);
-    if (has_fp) launch_fp(ln.main);
-}
-
-// slots of `io` whose limb runs on the fp64 (want_fp) or the integer instance; fp_of: per-limb-id class (host copy)
 // the integer instance of a radix kernel in the context's integer arithmetic: f(integral_constant<int, AR_PM | AR_INT>)
 template <typename F>
 static void with_int_arith(const NttTables &T, F &&f) {
@@ -1000,6 +978,7 @@ static void with_int_arith(const NttTables &T, F &&f) {
     else f(std::integral_constant<int, AR_INT>{});
 }
 
+// slots of `io` whose limb runs on the fp64 (want_fp) or the integer instance; fp_of: per-limb-id class (host copy)
 static unsigned long long class_mask(const NttIo &io, const unsigned char *fp_of, uint32_t L, bool want_fp) {
     unsigned long long m = 0;
     for (uint32_t b = 0; b < io.nslots; ++b) {
@@ -1009,104 +988,96 @@ static unsigned long long class_mask(const NttIo &io, const unsigned char *fp_of
     return m;
 }
 
+// the slots of a pass (or the targets of a conversion) by arithmetic class
+struct ClassMasks {
+    unsigned long long integer = 0, fp = 0;
+};
+// classes: bit 0 keeps the integer limbs, bit 1 the fp64 limbs
+static ClassMasks slot_classes(const NttIo &io, const NttTables &T, unsigned classes = 3) {
+    ClassMasks m;
+    if (classes & 1) m.integer = class_mask(io, T.h_fp_of, T.L, false);
+    if (classes & 2) m.fp = class_mask(io, T.h_fp_of, T.L, true);
+    return m;
+}
+// the first nl limbs of the chain
+static ClassMasks limb_classes(uint32_t nl, const NttTables &T) {
+    NttIo sel{};
+    sel.nslots = sel.nl = nl;
+    return slot_classes(sel, T);
+}
+static ClassMasks target_classes(const DevConv &cv, const NttTables &T, unsigned classes = 3) {
+    ClassMasks m;
+    for (uint32_t j = 0; j < cv.n_out; ++j) {
+        const bool fp = T.h_fp_of[cv.dst_id[j]] != 0;
+        if (fp && (classes & 2)) m.fp |= 1ull << j;
+        if (!fp && (classes & 1)) m.integer |= 1ull << j;
+    }
+    return m;
+}
+
+// The integer and the fp64 instance of a pass touch disjoint limbs and are launched one after the other on the same
+// stream (forking them onto two streams was measured slower: -5 %, event round trips): f(ar, mask, nsel) for each class
+// that has slots, the integer class first; ar is integral_constant<int, AR_PM | AR_INT> or <int, AR_FP>
+template <typename F>
+static void for_each_class(const NttTables &T, const ClassMasks &m, F &&f) {
+    if (m.integer) with_int_arith(T, [&](auto ar) { f(ar, m.integer, (uint32_t)__builtin_popcountll(m.integer)); });
+    if (m.fp) f(std::integral_constant<int, AR_FP>{}, m.fp, (uint32_t)__builtin_popcountll(m.fp));
+}
+
+// workgroups along a pass of the radix-2^LOG_H kernels: one takes 256 >> LOG_H columns (rows)
+template <int LOG_H>
+static uint32_t col_tiles(const NttTables &T) { return (1u << T.log_r2) / (256u >> LOG_H); }
+template <int LOG_H>
+static uint32_t row_tiles(const NttTables &T) { return (1u << T.log_r1) / (256u >> LOG_H); }
+
 template <bool INV>
 static void launch_col(const NttIo &io0, const NttTables &T, uint32_t n_polys, const u64 *scale, const u64 *scale_sh,
-                       const Lanes &ln, int pack = 0) {
+                       hipStream_t s, int pack = 0) {
     const uint32_t r1 = 1u << T.log_r1, r2 = 1u << T.log_r2;
-    NttIo io = io0, iof = io0;
-    io.slot_mask = class_mask(io0, T.h_fp_of, T.L, false);
-    iof.slot_mask = class_mask(io0, T.h_fp_of, T.L, true);
-    io.nsel = (uint32_t)__builtin_popcountll(io.slot_mask);
-    iof.nsel = (uint32_t)__builtin_popcountll(iof.slot_mask);
-    const uint32_t items = n_polys * io.nsel, itemsf = n_polys * iof.nsel;
-    switch (fast_log_h(T.log_r1, r2)) {
-        case 4:
-            launch_two_classes(ln, items != 0, itemsf != 0,
-                [&](hipStream_t s) { with_int_arith(T, [&](auto ar) {
-                    k_ntt_col_r<4, INV, decltype(ar)::value>
-                        <<<dim3(r2 / 16, items), NTT_THREADS, 0, s>>>(io, T, scale, scale_sh, pack);
-                }); },
-                [&](hipStream_t s) { k_ntt_col_r<4, INV, AR_FP><<<dim3(r2 / 16, itemsf), NTT_THREADS, 0, s>>>(iof, T, scale, scale_sh, pack); });
-            break;
-        case 3:
-            launch_two_classes(ln, items != 0, itemsf != 0,
-                [&](hipStream_t s) { with_int_arith(T, [&](auto ar) {
-                    k_ntt_col_r<3, INV, decltype(ar)::value>
-                        <<<dim3(r2 / 32, items), NTT_THREADS, 0, s>>>(io, T, scale, scale_sh, pack);
-                }); },
-                [&](hipStream_t s) { k_ntt_col_r<3, INV, AR_FP><<<dim3(r2 / 32, itemsf), NTT_THREADS, 0, s>>>(iof, T, scale, scale_sh, pack); });
-            break;
-        case 2:
-            launch_two_classes(ln, items != 0, itemsf != 0,
-                [&](hipStream_t s) { with_int_arith(T, [&](auto ar) {
-                    k_ntt_col_r<2, INV, decltype(ar)::value>
-                        <<<dim3(r2 / 64, items), NTT_THREADS, 0, s>>>(io, T, scale, scale_sh, pack);
-                }); },
-                [&](hipStream_t s) { k_ntt_col_r<2, INV, AR_FP><<<dim3(r2 / 64, itemsf), NTT_THREADS, 0, s>>>(iof, T, scale, scale_sh, pack); });
-            break;
-        default:
-            if (pack) throw std::logic_error("packed output needs the radix column kernel");
-            k_ntt_col<INV><<<dim3(r2 / NTT_COLS, n_polys * io0.nslots), NTT_THREADS, (size_t)r1 * NTT_COLS * sizeof(u64), ln.main>>>(
-                io0, T, scale, scale_sh);
-    }
+    const bool radix = dispatch<2, 3, 4>(fast_log_h(T.log_r1, r2), [&](auto log_h) {
+        constexpr int LOG_H = decltype(log_h)::value;
+        for_each_class(T, slot_classes(io0, T), [&](auto ar, unsigned long long mask, uint32_t nsel) {
+            NttIo io = io0;
+            io.slot_mask = mask;
+            io.nsel = nsel;
+            k_ntt_col_r<LOG_H, INV, decltype(ar)::value>
+                <<<dim3(col_tiles<LOG_H>(T), n_polys * nsel), NTT_THREADS, 0, s>>>(io, T, scale, scale_sh, pack);
+        });
+    });
+    if (radix) return;
+    if (pack) throw std::logic_error("packed output needs the radix column kernel");
+    k_ntt_col<INV><<<dim3(r2 / NTT_COLS, n_polys * io0.nslots), NTT_THREADS, (size_t)r1 * NTT_COLS * sizeof(u64), s>>>(
+        io0, T, scale, scale_sh);
 }
 
 static bool row_tail_supported(const NttTables &T) { return fast_row(T.log_r2, 1u << T.log_r1) != 0; }
 
 template <bool INV>
-static void launch_row(const NttIo &io0, const NttTables &T, uint32_t n_polys, const TailArgs &tail, const Lanes &ln,
+static void launch_row(const NttIo &io0, const NttTables &T, uint32_t n_polys, const TailArgs &tail, hipStream_t s,
                        unsigned classes = 3) {  // bit 0: integer limbs, bit 1: fp64 limbs
     const uint32_t n = 1u << T.log_n, r1 = 1u << T.log_r1;
-    NttIo io = io0, iof = io0;
-    io.slot_mask = class_mask(io0, T.h_fp_of, T.L, false);
-    iof.slot_mask = class_mask(io0, T.h_fp_of, T.L, true);
-    io.nsel = (uint32_t)__builtin_popcountll(io.slot_mask);
-    iof.nsel = (uint32_t)__builtin_popcountll(iof.slot_mask);
-    const uint32_t items = (classes & 1) ? n_polys * io.nsel : 0, itemsf = (classes & 2) ? n_polys * iof.nsel : 0;
-    switch (fast_row(T.log_r2, r1)) {
-        case 9:
-            launch_two_classes(ln, items != 0, itemsf != 0,
-                [&](hipStream_t s) { with_int_arith(T, [&](auto ar) {
-                    k_ntt_row3<INV, decltype(ar)::value>
-                        <<<dim3((r1 / 4) * items), NTT_THREADS, 0, s>>>(io, T, tail);
-                }); },
-                [&](hipStream_t s) { k_ntt_row3<INV, AR_FP><<<dim3((r1 / 4) * itemsf), NTT_THREADS, 0, s>>>(iof, T, tail); });
-            break;
-        case 4:
-            launch_two_classes(ln, items != 0, itemsf != 0,
-                [&](hipStream_t s) { with_int_arith(T, [&](auto ar) {
-                    k_ntt_row_r<4, INV, decltype(ar)::value>
-                        <<<dim3((r1 / 16) * items), NTT_THREADS, 0, s>>>(io, T, tail);
-                }); },
-                [&](hipStream_t s) { k_ntt_row_r<4, INV, AR_FP><<<dim3((r1 / 16) * itemsf), NTT_THREADS, 0, s>>>(iof, T, tail); });
-            break;
-        case 3:
-            launch_two_classes(ln, items != 0, itemsf != 0,
-                [&](hipStream_t s) { with_int_arith(T, [&](auto ar) {
-                    k_ntt_row_r<3, INV, decltype(ar)::value>
-                        <<<dim3((r1 / 32) * items), NTT_THREADS, 0, s>>>(io, T, tail);
-                }); },
-                [&](hipStream_t s) { k_ntt_row_r<3, INV, AR_FP><<<dim3((r1 / 32) * itemsf), NTT_THREADS, 0, s>>>(iof, T, tail); });
-            break;
-        case 2:
-            launch_two_classes(ln, items != 0, itemsf != 0,
-                [&](hipStream_t s) { with_int_arith(T, [&](auto ar) {
-                    k_ntt_row_r<2, INV, decltype(ar)::value>
-                        <<<dim3((r1 / 64) * items), NTT_THREADS, 0, s>>>(io, T, tail);
-                }); },
-                [&](hipStream_t s) { k_ntt_row_r<2, INV, AR_FP><<<dim3((r1 / 64) * itemsf), NTT_THREADS, 0, s>>>(iof, T, tail); });
-            break;
-        default: {
-            if (tail.enabled) throw std::logic_error("fused tail needs the radix row kernel");
-            const uint32_t tile = n < (uint32_t)NTT_TILE ? n : (uint32_t)NTT_TILE;
-            k_ntt_row<INV><<<dim3(n / tile, n_polys * io0.nslots), NTT_THREADS, (size_t)tile * sizeof(u64), ln.main>>>(io0, T);
-        }
-    }
+    const bool radix = dispatch<2, 3, 4, 9>(fast_row(T.log_r2, r1), [&](auto row_h) {
+        constexpr int ROW_H = decltype(row_h)::value;
+        for_each_class(T, slot_classes(io0, T, classes), [&](auto ar, unsigned long long mask, uint32_t nsel) {
+            NttIo io = io0;
+            io.slot_mask = mask;
+            io.nsel = nsel;
+            if constexpr (ROW_H == 9)
+                k_ntt_row3<INV, decltype(ar)::value><<<dim3((r1 / 4) * n_polys * nsel), NTT_THREADS, 0, s>>>(io, T, tail);
+            else
+                k_ntt_row_r<ROW_H, INV, decltype(ar)::value>
+                    <<<dim3(row_tiles<ROW_H>(T) * n_polys * nsel), NTT_THREADS, 0, s>>>(io, T, tail);
+        });
+    });
+    if (radix) return;
+    if (tail.enabled) throw std::logic_error("fused tail needs the radix row kernel");
+    const uint32_t tile = n < (uint32_t)NTT_TILE ? n : (uint32_t)NTT_TILE;
+    k_ntt_row<INV><<<dim3(n / tile, n_polys * io0.nslots), NTT_THREADS, (size_t)tile * sizeof(u64), s>>>(io0, T);
 }
 
 // two-pass launcher: reads `io.in`, leaves the result in `io.out` (may be the same buffer)
 static void ntt_passes(NttIo io, const NttTables &T, uint32_t n_polys, bool inverse, const u64 *scale,
-                       const u64 *scale_sh, const Lanes &s, int pack = 0) {
+                       const u64 *scale_sh, hipStream_t s, int pack = 0) {
     if (n_polys == 0 || io.nslots == 0) return;
     NttIo second = io;  // second pass runs in place on the output
     second.in_group = 0;
@@ -1127,136 +1098,88 @@ static void ntt_passes(NttIo io, const NttTables &T, uint32_t n_polys, bool inve
 // base conversion fused into the forward column pass of every converted limb (k_conv_col); false when the
 // column pass of this ring size has no radix kernel (the caller then runs k_baseconv + a plain column pass)
 template <int LOG_H, int N_IN, int SRCMODE>
-static void launch_conv_col_n(const ConvIo &io, const ConvIo &iof, const dim3 &grid, const dim3 &gridf, const NttTables &T,
-                              const DevConv &cv, const Lanes &ln) {
-    if constexpr (LOG_H >= 3) {
-        // two targets of a class per workgroup (k_conv_col2): half the source traffic through each CU's L1; the last
-        // workgroup of an odd target count carries one
-        const uint32_t per = grid.x / (io.nsel ? io.nsel : 1), perf = gridf.x / (iof.nsel ? iof.nsel : 1);
-        if (io.nsel) with_int_arith(T, [&](auto ar) {
+static void launch_conv_col_n(const ConvIo &io0, const NttTables &T, const DevConv &cv, hipStream_t s, unsigned classes) {
+    for_each_class(T, target_classes(cv, T, classes), [&](auto ar, unsigned long long mask, uint32_t nsel) {
+        ConvIo io = io0;
+        io.target_mask = mask;
+        io.nsel = nsel;
+        if constexpr (LOG_H >= 3)
+            // two targets of a class per workgroup (k_conv_col2): half the source traffic through each CU's L1; the last
+            // workgroup of an odd target count carries one
             k_conv_col2<LOG_H, N_IN, decltype(ar)::value, DevConv, SRCMODE>
-                <<<dim3(per * ((io.nsel + 1) / 2)), NTT_THREADS, 0, ln.main>>>(io, T, cv);
-        });
-        if (iof.nsel)
-            k_conv_col2<LOG_H, N_IN, AR_FP, DevConv, SRCMODE><<<dim3(perf * ((iof.nsel + 1) / 2)), NTT_THREADS, 0, ln.main>>>(iof, T, cv);
-    } else {
-        launch_two_classes(ln, io.nsel != 0, iof.nsel != 0,
-            [&](hipStream_t s) { with_int_arith(T, [&](auto ar) {
-                k_conv_col<LOG_H, N_IN, decltype(ar)::value, DevConv, SRCMODE>
-                    <<<grid, NTT_THREADS, 0, s>>>(io, T, cv);
-            }); },
-            [&](hipStream_t s) { k_conv_col<LOG_H, N_IN, AR_FP, DevConv, SRCMODE><<<gridf, NTT_THREADS, 0, s>>>(iof, T, cv); });
-    }
+                <<<dim3(io.items * col_tiles<LOG_H>(T) * ((nsel + 1) / 2)), NTT_THREADS, 0, s>>>(io, T, cv);
+        else
+            k_conv_col<LOG_H, N_IN, decltype(ar)::value, DevConv, SRCMODE>
+                <<<dim3(io.items * col_tiles<LOG_H>(T) * nsel), NTT_THREADS, 0, s>>>(io, T, cv);
+    });
 }
 template <int LOG_H, int N_IN>
-static void launch_conv_col_m(const ConvIo &io, const ConvIo &iof, const dim3 &grid, const dim3 &gridf, const NttTables &T,
-                              const DevConv &cv, const Lanes &ln, int srcmode) {
+static void launch_conv_col_m(const ConvIo &io, const NttTables &T, const DevConv &cv, hipStream_t s, int srcmode,
+                              unsigned classes) {
     if constexpr (N_IN <= 4 && LOG_H >= 3) {
-        if (srcmode == 1) return launch_conv_col_n<LOG_H, N_IN, 1>(io, iof, grid, gridf, T, cv, ln);
-        if (srcmode == 2) return launch_conv_col_n<LOG_H, N_IN, (N_IN > 1 ? 2 : 0)>(io, iof, grid, gridf, T, cv, ln);
+        if (srcmode == 1) return launch_conv_col_n<LOG_H, N_IN, 1>(io, T, cv, s, classes);
+        if (srcmode == 2) return launch_conv_col_n<LOG_H, N_IN, (N_IN > 1 ? 2 : 0)>(io, T, cv, s, classes);
     }
     if (srcmode != 0) throw std::logic_error("double conversion sources: unsupported shape");
-    launch_conv_col_n<LOG_H, N_IN, 0>(io, iof, grid, gridf, T, cv, ln);
+    launch_conv_col_n<LOG_H, N_IN, 0>(io, T, cv, s, classes);
 }
 // srcmode: form of the sources in io.in (see src_is_double): 0 = packed 30-bit halves, 1 / 2 = doubles
-template <int LOG_H>
-static void launch_conv_col_h(const ConvIo &io0, const NttTables &T, const DevConv &cv, const Lanes &ln, int srcmode,
-                              unsigned classes) {  // classes: bit 0 integer-class targets, bit 1 fp64-class targets
-    const uint32_t tiles = (1u << T.log_r2) / (256u >> LOG_H);
-    ConvIo io = io0, iof = io0;
-    io.target_mask = iof.target_mask = 0;
-    for (uint32_t j = 0; j < cv.n_out; ++j) {
-        const bool fp = T.h_fp_of[cv.dst_id[j]] != 0;
-        if (fp && (classes & 2)) iof.target_mask |= 1ull << j;
-        if (!fp && (classes & 1)) io.target_mask |= 1ull << j;
-    }
-    io.nsel = (uint32_t)__builtin_popcountll(io.target_mask);
-    iof.nsel = (uint32_t)__builtin_popcountll(iof.target_mask);
-    const dim3 grid(io.items * tiles * io.nsel), gridf(io.items * tiles * iof.nsel);
-    switch (cv.n_in) {
-        case 1: launch_conv_col_m<LOG_H, 1>(io, iof, grid, gridf, T, cv, ln, srcmode); break;
-        case 2: launch_conv_col_m<LOG_H, 2>(io, iof, grid, gridf, T, cv, ln, srcmode); break;
-        case 3: launch_conv_col_m<LOG_H, 3>(io, iof, grid, gridf, T, cv, ln, srcmode); break;
-        case 4: launch_conv_col_m<LOG_H, 4>(io, iof, grid, gridf, T, cv, ln, srcmode); break;
-        case 5: launch_conv_col_m<LOG_H, 5>(io, iof, grid, gridf, T, cv, ln, srcmode); break;
-        case 6: launch_conv_col_m<LOG_H, 6>(io, iof, grid, gridf, T, cv, ln, srcmode); break;
-        case 7: launch_conv_col_m<LOG_H, 7>(io, iof, grid, gridf, T, cv, ln, srcmode); break;
-        case 8: launch_conv_col_m<LOG_H, 8>(io, iof, grid, gridf, T, cv, ln, srcmode); break;
-        default: throw std::invalid_argument("base conversion fan-in unsupported");
-    }
+// classes: bit 0 integer-class targets, bit 1 fp64-class targets
+static bool launch_conv_col(const ConvIo &io, const NttTables &T, const DevConv &cv, hipStream_t s, int srcmode = 0,
+                            unsigned classes = 3) {
+    const bool radix = dispatch<2, 3, 4>(fast_log_h(T.log_r1, 1u << T.log_r2), [&](auto log_h) {
+        if (!dispatch<1, 2, 3, 4, 5, 6, 7, 8>(cv.n_in, [&](auto n_in) {
+                launch_conv_col_m<decltype(log_h)::value, decltype(n_in)::value>(io, T, cv, s, srcmode, classes);
+            }))
+            throw std::invalid_argument("base conversion fan-in unsupported");
+    });
+    if (radix) MK_HIP(hipGetLastError());
+    return radix;
 }
 // the group's ONE ModDown conversion (k_conv_col_psum), one instance per arithmetic class of the targets
 template <int LOG_H, int N_IN>
-static void launch_conv_col_psum_n(const ConvIo &io, const ConvIo &iof, uint32_t tiles, const NttTables &T, const DevConv &cv,
-                                   hipStream_t s) {
-    if (io.nsel) with_int_arith(T, [&](auto ar) {
-        k_conv_col_psum<LOG_H, N_IN, decltype(ar)::value, DevConv>
-            <<<dim3(io.items * tiles * io.nsel), NTT_THREADS, 0, s>>>(io, T, cv);
+static void launch_conv_col_psum_n(const ConvIo &io0, const NttTables &T, const DevConv &cv, hipStream_t s) {
+    for_each_class(T, target_classes(cv, T), [&](auto ar, unsigned long long mask, uint32_t nsel) {
+        ConvIo io = io0;
+        io.target_mask = mask;
+        io.nsel = nsel;
+        if constexpr (decltype(ar)::value == AR_FP)
+            // fp64-class targets two per workgroup (+0.2 % on the step at C3, +0.9 % at N = 2^17, L = 20)
+            k_conv_col_psum2<LOG_H, N_IN, DevConv>
+                <<<dim3(io.items * col_tiles<LOG_H>(T) * ((nsel + 1) / 2)), NTT_THREADS, 0, s>>>(io, T, cv);
+        else
+            k_conv_col_psum<LOG_H, N_IN, decltype(ar)::value, DevConv>
+                <<<dim3(io.items * col_tiles<LOG_H>(T) * nsel), NTT_THREADS, 0, s>>>(io, T, cv);
     });
-    if (iof.nsel)  // fp64-class targets two per workgroup (+0.2 % on the step at C3, +0.9 % at N = 2^17, L = 20)
-        k_conv_col_psum2<LOG_H, N_IN, DevConv><<<dim3(iof.items * tiles * ((iof.nsel + 1) / 2)), NTT_THREADS, 0, s>>>(iof, T, cv);
-}
-template <int LOG_H>
-static void launch_conv_col_psum_h(const ConvIo &io0, const NttTables &T, const DevConv &cv, hipStream_t s) {
-    const uint32_t tiles = (1u << T.log_r2) / (256u >> LOG_H);
-    ConvIo io = io0, iof = io0;
-    io.target_mask = iof.target_mask = 0;
-    for (uint32_t j = 0; j < cv.n_out; ++j) (T.h_fp_of[cv.dst_id[j]] ? iof.target_mask : io.target_mask) |= 1ull << j;
-    io.nsel = (uint32_t)__builtin_popcountll(io.target_mask);
-    iof.nsel = (uint32_t)__builtin_popcountll(iof.target_mask);
-    switch (cv.n_in) {
-        case 1: launch_conv_col_psum_n<LOG_H, 1>(io, iof, tiles, T, cv, s); break;
-        case 2: launch_conv_col_psum_n<LOG_H, 2>(io, iof, tiles, T, cv, s); break;
-        case 3: launch_conv_col_psum_n<LOG_H, 3>(io, iof, tiles, T, cv, s); break;
-        case 4: launch_conv_col_psum_n<LOG_H, 4>(io, iof, tiles, T, cv, s); break;
-        case 5: launch_conv_col_psum_n<LOG_H, 5>(io, iof, tiles, T, cv, s); break;
-        case 6: launch_conv_col_psum_n<LOG_H, 6>(io, iof, tiles, T, cv, s); break;
-        case 7: launch_conv_col_psum_n<LOG_H, 7>(io, iof, tiles, T, cv, s); break;
-        case 8: launch_conv_col_psum_n<LOG_H, 8>(io, iof, tiles, T, cv, s); break;
-        default: throw std::invalid_argument("base conversion fan-in unsupported");
-    }
 }
 static void launch_conv_col_psum(const ConvIo &io, const NttTables &T, const DevConv &cv, hipStream_t s) {
-    switch (fast_log_h(T.log_r1, 1u << T.log_r2)) {
-        case 4: launch_conv_col_psum_h<4>(io, T, cv, s); break;
-        case 3: launch_conv_col_psum_h<3>(io, T, cv, s); break;
-        default: throw std::logic_error("summed conversion needs 64- or 256-point columns");
-    }
+    if (!dispatch<3, 4>(fast_log_h(T.log_r1, 1u << T.log_r2), [&](auto log_h) {
+            if (!dispatch<1, 2, 3, 4, 5, 6, 7, 8>(cv.n_in, [&](auto n_in) {
+                    launch_conv_col_psum_n<decltype(log_h)::value, decltype(n_in)::value>(io, T, cv, s);
+                }))
+                throw std::invalid_argument("base conversion fan-in unsupported");
+        }))
+        throw std::logic_error("summed conversion needs 64- or 256-point columns");
     MK_HIP(hipGetLastError());
 }
 // inverse column pass of the P limbs of every client of a group, summed over the clients as integers (k_icol_sum)
 static void launch_icol_sum(const u64 *pc, u64 *psum, const NttTables &T, const u64 *scale, const u64 *scale_sh, uint32_t K,
                             uint32_t n_polys, uint32_t n_clients, size_t in_cstride, hipStream_t s) {
-    const uint32_t r2 = 1u << T.log_r2;
-    switch (fast_log_h(T.log_r1, r2)) {
-        case 4: with_int_arith(T, [&](auto ar) {
-            k_icol_sum<4, decltype(ar)::value>
-                <<<dim3(r2 / 16, n_polys * K), NTT_THREADS, 0, s>>>(pc, psum, T, scale, scale_sh, K, n_clients, in_cstride);
-        }); break;
-        case 3: with_int_arith(T, [&](auto ar) {
-            k_icol_sum<3, decltype(ar)::value>
-                <<<dim3(r2 / 32, n_polys * K), NTT_THREADS, 0, s>>>(pc, psum, T, scale, scale_sh, K, n_clients, in_cstride);
-        }); break;
-        default: throw std::logic_error("summed conversion needs 64- or 256-point columns");
-    }
+    if (!dispatch<3, 4>(fast_log_h(T.log_r1, 1u << T.log_r2), [&](auto log_h) {
+            constexpr int LOG_H = decltype(log_h)::value;
+            with_int_arith(T, [&](auto ar) {
+                k_icol_sum<LOG_H, decltype(ar)::value><<<dim3(col_tiles<LOG_H>(T), n_polys * K), NTT_THREADS, 0, s>>>(
+                    pc, psum, T, scale, scale_sh, K, n_clients, in_cstride);
+            });
+        }))
+        throw std::logic_error("summed conversion needs 64- or 256-point columns");
     MK_HIP(hipGetLastError());
-}
-static bool launch_conv_col(const ConvIo &io, const NttTables &T, const DevConv &cv, const Lanes &s, int srcmode = 0,
-                            unsigned classes = 3) {
-    switch (fast_log_h(T.log_r1, 1u << T.log_r2)) {
-        case 4: launch_conv_col_h<4>(io, T, cv, s, srcmode, classes); break;
-        case 3: launch_conv_col_h<3>(io, T, cv, s, srcmode, classes); break;
-        case 2: launch_conv_col_h<2>(io, T, cv, s, srcmode, classes); break;
-        default: return false;
-    }
-    MK_HIP(hipGetLastError());
-    return true;
 }
 
 void Engine::ntt_launch(u64 *d, uint32_t n_polys, uint32_t nl, uint32_t ext, bool inverse, const u64 *scale,
                         const u64 *scale_sh) {
     NttIo io{d, d, (size_t)ext * ps_.n, (size_t)ext * ps_.n, 0, 0, 0, ext, nl};
-    ntt_passes(io, tabs_, n_polys, inverse, scale, scale_sh, lanes());
+    ntt_passes(io, tabs_, n_polys, inverse, scale, scale_sh, stream_);
 }
 
 void Engine::ntt_forward(u64 *d, uint32_t n_polys, uint32_t nl, bool with_p) {
@@ -1328,15 +1251,10 @@ void Engine::mult_const(u64 *ct, uint32_t n_ct, uint32_t nl, const std::vector<u
 template <int LOG_H>
 static void launch_switch_col(const u64 *last, u64 *out, const NttTables &T, uint32_t n_targets, uint32_t items, u64 q_last,
                               hipStream_t s) {
-    unsigned long long mi = 0, mf = 0;
-    for (uint32_t i = 0; i < n_targets; ++i) (T.h_fp_of[i] ? mf : mi) |= 1ull << i;
-    const uint32_t tiles = (1u << T.log_r2) / (256u >> LOG_H);
-    const uint32_t ni = (uint32_t)__builtin_popcountll(mi), nf = (uint32_t)__builtin_popcountll(mf);
-    if (ni) with_int_arith(T, [&](auto ar) {
+    for_each_class(T, limb_classes(n_targets, T), [&](auto ar, unsigned long long mask, uint32_t nsel) {
         k_switch_col<LOG_H, decltype(ar)::value>
-            <<<dim3(tiles, ni, items), NTT_THREADS, 0, s>>>(last, out, T, n_targets, q_last, mi);
+            <<<dim3(col_tiles<LOG_H>(T), nsel, items), NTT_THREADS, 0, s>>>(last, out, T, n_targets, q_last, mask);
     });
-    if (nf) k_switch_col<LOG_H, AR_FP><<<dim3(tiles, nf, items), NTT_THREADS, 0, s>>>(last, out, T, n_targets, q_last, mf);
 }
 
 const u64 *Engine::rescale_consts(uint32_t nl, const std::vector<u64> *factors) {
@@ -1364,20 +1282,19 @@ void Engine::rescale_core(const u64 *in, uint32_t in_limbs, u64 *out, uint32_t i
     const uint32_t n = ps_.n, last = nl - 1;
     // 1. dropped limb -> COEFFICIENT format
     NttIo io{in, d_last, (size_t)in_limbs * n, (size_t)n, last, 0, last, 1, nl};
-    ntt_passes(io, tabs_, items, true, nullptr, nullptr, lanes());
+    ntt_passes(io, tabs_, items, true, nullptr, nullptr, stream_);
     const int col_h = fast_log_h(tabs_.log_r1, 1u << tabs_.log_r2);
     if (col_h >= 2 && row_tail_supported(tabs_)) {
         // 2. centred switch of modulus fused into the forward column pass of every remaining limb; 3. row pass with
         // 4. (c_i - tmp_i) * q_last^-1 [* constant] in its copy-out (the ModDown tail with til = the input ciphertext)
-        switch (col_h) {
-            case 4: launch_switch_col<4>(d_last, d_tmp, tabs_, last, items, ps_.moduli[last], stream_); break;
-            case 3: launch_switch_col<3>(d_last, d_tmp, tabs_, last, items, ps_.moduli[last], stream_); break;
-            default: launch_switch_col<2>(d_last, d_tmp, tabs_, last, items, ps_.moduli[last], stream_); break;
-        }
+        if (!dispatch<2, 3, 4>(col_h, [&](auto log_h) {
+                launch_switch_col<decltype(log_h)::value>(d_last, d_tmp, tabs_, last, items, ps_.moduli[last], stream_);
+            }))
+            throw std::logic_error("fused rescale: no switch kernel for this column radix");
         MK_HIP(hipGetLastError());
         NttIo row{d_tmp, out, (size_t)last * n, (size_t)last * n, 0, 0, 0, last, last};
         TailArgs tail{in, nullptr, d_c, d_c + last, 0, in_limbs, 1, 0u, group, out_gstride};
-        launch_row<false>(row, tabs_, items, tail, lanes());
+        launch_row<false>(row, tabs_, items, tail, stream_);
         MK_HIP(hipGetLastError());
         return;
     }
@@ -1487,18 +1404,18 @@ void Engine::modup_core(const u64 *c1, size_t c1_stride, u64 *coef, u64 *dig, ui
         const DevConv &cv = modup_conv(nl, part);
         if (conv_src_mode(cv) < 0 || (conv_src_mode(cv) != 0 && cv.n_in > 4)) doubles = false;
     }
-    ntt_passes(s1, tabs_, cnt, true, fold, fold + D, lanes(), fused ? (doubles ? 2 : 1) : 0);
+    ntt_passes(s1, tabs_, cnt, true, fold, fold + D, stream_, fused ? (doubles ? 2 : 1) : 0);
     for (uint32_t part = 0; part < nparts && fused; ++part) {
         // S2+S3a: base conversion fused into the column pass of each complement limb
         ConvIo io{coef, dig + (size_t)part * ext * n, (size_t)nl * n, dstride, cnt, 0, 0};
         const DevConv &cv = modup_conv(nl, part);
-        launch_conv_col(io, tabs_, cv, lanes(), doubles ? conv_src_mode(cv) : 0);
+        launch_conv_col(io, tabs_, cv, stream_, doubles ? conv_src_mode(cv) : 0);
     }
     if (fused) {
         // S3b: one row pass over every converted limb of every digit (own limbs skipped)
         NttIo row{dig, dig, (size_t)ext * n, (size_t)ext * n, 0, 0, 0, ext, nl, nparts, ps_.alpha};
         // (rows_int_only: the fp64 limbs finish their transform inside the fused inner-product kernel)
-        if (!skip_rows_) launch_row<false>(row, tabs_, cnt * nparts, TailArgs{}, lanes(), rows_int_only ? 1u : 3u);
+        if (!skip_rows_) launch_row<false>(row, tabs_, cnt * nparts, TailArgs{}, stream_, rows_int_only ? 1u : 3u);
         MK_HIP(hipGetLastError());
         return;
     }
@@ -1510,11 +1427,11 @@ void Engine::modup_core(const u64 *c1, size_t c1_stride, u64 *coef, u64 *dig, ui
         launch_baseconv(coef, (size_t)nl * n, d, dstride, cv, d_limb_, n, cnt, 1, stream_);
         if (lo > 0) {
             NttIo a{d, d, dstride, dstride, 0, 0, 0, lo, nl};
-            ntt_passes(a, tabs_, cnt, false, nullptr, nullptr, lanes());
+            ntt_passes(a, tabs_, cnt, false, nullptr, nullptr, stream_);
         }
         if (hi < ext) {
             NttIo b{d, d, dstride, dstride, hi, hi, hi, ext - hi, nl};
-            ntt_passes(b, tabs_, cnt, false, nullptr, nullptr, lanes());
+            ntt_passes(b, tabs_, cnt, false, nullptr, nullptr, stream_);
         }
     }
 }
@@ -1529,17 +1446,17 @@ void Engine::moddown_convert(const u64 *til, u64 *pc, u64 *conv, uint32_t cnt, u
     NttIo s5{til, pc, (size_t)ext * n, (size_t)K * n, nl, 0, nl, K, nl};
     const DevConv &cv = moddown_conv(nl);
     if (!rows_done) {
-        ntt_passes(s5, tabs_, cnt, true, fold, fold + D, lanes(), 1);
+        ntt_passes(s5, tabs_, cnt, true, fold, fold + D, stream_, 1);
     } else {
         NttIo second = s5;
         second.in = s5.out;
         second.in_stride = s5.out_stride;
         second.in_slot0 = s5.out_slot0;
-        launch_col<true>(second, tabs_, cnt, fold, fold + D, lanes(), 1);
+        launch_col<true>(second, tabs_, cnt, fold, fold + D, stream_, 1);
         MK_HIP(hipGetLastError());
     }
     ConvIo io{pc, conv, (size_t)K * n, (size_t)nl * n, cnt, 0, 0};
-    launch_conv_col(io, tabs_, cv, lanes());
+    launch_conv_col(io, tabs_, cv, stream_);
 }
 
 // ApproxModDown on `cnt` polynomials til[item][ext][N] -> out[item] (items out_stride apart, nl limbs each);
@@ -1558,7 +1475,7 @@ void Engine::moddown_core(const u64 *til, u64 *pc, u64 *conv, u64 *out, size_t o
         // row pass of the converted limbs with the (ctilde_Q - conv) * P^-1 (+ c0) tail in its copy-out
         NttIo row{conv, out, (size_t)nl * n, out_stride, 0, 0, 0, nl, nl};
         TailArgs tail{til, add, pinv, pinv + nl, add_stride, ext, 1, accumulate ? 1u : 0u, group, out_gstride};
-        launch_row<false>(row, tabs_, cnt, tail, lanes());
+        launch_row<false>(row, tabs_, cnt, tail, stream_);
         MK_HIP(hipGetLastError());
         return;
     }
@@ -1566,11 +1483,11 @@ void Engine::moddown_core(const u64 *til, u64 *pc, u64 *conv, u64 *out, size_t o
     if (conv_fused) {  // fused conversion + column pass, plain row pass, tail as its own kernel
         moddown_convert(til, pc, conv, cnt, nl, p_rows_done);
         NttIo row{conv, conv, (size_t)nl * n, (size_t)nl * n, 0, 0, 0, nl, nl};
-        launch_row<false>(row, tabs_, cnt, TailArgs{}, lanes());
+        launch_row<false>(row, tabs_, cnt, TailArgs{}, stream_);
     } else {
         if (p_rows_done) throw std::logic_error("fused P-limb inverse needs the radix kernels");
         NttIo s5{til, pc, (size_t)ext * n, (size_t)K * n, nl, 0, nl, K, nl};
-        ntt_passes(s5, tabs_, cnt, true, fold, fold + D, lanes(), 0);
+        ntt_passes(s5, tabs_, cnt, true, fold, fold + D, stream_, 0);
         launch_baseconv(pc, (size_t)K * n, conv, (size_t)nl * n, cv, d_limb_, n, cnt, 1, stream_);
         ntt_launch(conv, cnt, nl, nl, false, nullptr, nullptr);
     }
@@ -1625,15 +1542,8 @@ static void launch_row_inner_fp(const InnerArgs &a, const NttTables &T, hipStrea
 }
 template <int LOG_H>
 static void launch_row_inner_fp_n(const InnerArgs &a, const NttTables &T, uint32_t nparts, hipStream_t s) {
-    switch (nparts) {
-        case 1: launch_row_inner_fp<LOG_H, 1>(a, T, s); break;
-        case 2: launch_row_inner_fp<LOG_H, 2>(a, T, s); break;
-        case 3: launch_row_inner_fp<LOG_H, 3>(a, T, s); break;
-        case 4: launch_row_inner_fp<LOG_H, 4>(a, T, s); break;
-        case 5: launch_row_inner_fp<LOG_H, 5>(a, T, s); break;
-        case 6: launch_row_inner_fp<LOG_H, 6>(a, T, s); break;
-        default: throw std::invalid_argument("more than 6 key-switch digits unsupported");
-    }
+    if (!dispatch<1, 2, 3, 4, 5, 6>(nparts, [&](auto np) { launch_row_inner_fp<LOG_H, decltype(np)::value>(a, T, s); }))
+        throw std::invalid_argument("more than 6 key-switch digits unsupported");
 }
 
 // 256-point rows have two implementations of the fused kernels: two rounds of radix 16 (16 words per thread, 2 waves
@@ -1642,15 +1552,10 @@ static void launch_row_inner_fp_n(const InnerArgs &a, const NttTables &T, uint32
 template <int LOGC>
 static void launch_row3_inner_fp_n(const InnerArgs &a, const NttTables &T, uint32_t nparts, hipStream_t s) {
     const dim3 grid(((1u << T.log_r1) / RowT<LOGC>::ROWS) * a.nsel * a.items);
-    switch (nparts) {
-        case 1: k_row3_inner_fp<1, LOGC><<<grid, NTT_THREADS, 0, s>>>(a, T); break;
-        case 2: k_row3_inner_fp<2, LOGC><<<grid, NTT_THREADS, 0, s>>>(a, T); break;
-        case 3: k_row3_inner_fp<3, LOGC><<<grid, NTT_THREADS, 0, s>>>(a, T); break;
-        case 4: k_row3_inner_fp<4, LOGC><<<grid, NTT_THREADS, 0, s>>>(a, T); break;
-        case 5: k_row3_inner_fp<5, LOGC><<<grid, NTT_THREADS, 0, s>>>(a, T); break;
-        case 6: k_row3_inner_fp<6, LOGC><<<grid, NTT_THREADS, 0, s>>>(a, T); break;
-        default: throw std::invalid_argument("more than 6 key-switch digits unsupported");
-    }
+    if (!dispatch<1, 2, 3, 4, 5, 6>(nparts, [&](auto np) {
+            k_row3_inner_fp<decltype(np)::value, LOGC><<<grid, NTT_THREADS, 0, s>>>(a, T);
+        }))
+        throw std::invalid_argument("more than 6 key-switch digits unsupported");
 }
 
 template <int LOGC, bool INVP>
@@ -1659,33 +1564,13 @@ static void launch_row3_inner_int_k(const InnerArgs &a, const NttTables &T, uint
     if (!a.nsel || !a.items) return;
     // a workgroup walks up to inner_walk_len(nparts) ciphertext indices of one client
     const dim3 grid(((1u << T.log_r1) / RowT<LOGC>::ROWS) * a.nsel * inner_walks(a, nparts));
-    switch (nparts) {
-        case 1: with_int_arith(T, [&](auto ar) {
-            k_row3_inner_int<1, LOGC, INVP, decltype(ar)::value>
-                <<<grid, NTT_THREADS, 0, s>>>(a, T, L, pc, K);
-        }); break;
-        case 2: with_int_arith(T, [&](auto ar) {
-            k_row3_inner_int<2, LOGC, INVP, decltype(ar)::value>
-                <<<grid, NTT_THREADS, 0, s>>>(a, T, L, pc, K);
-        }); break;
-        case 3: with_int_arith(T, [&](auto ar) {
-            k_row3_inner_int<3, LOGC, INVP, decltype(ar)::value>
-                <<<grid, NTT_THREADS, 0, s>>>(a, T, L, pc, K);
-        }); break;
-        case 4: with_int_arith(T, [&](auto ar) {
-            k_row3_inner_int<4, LOGC, INVP, decltype(ar)::value>
-                <<<grid, NTT_THREADS, 0, s>>>(a, T, L, pc, K);
-        }); break;
-        case 5: with_int_arith(T, [&](auto ar) {
-            k_row3_inner_int<5, LOGC, INVP, decltype(ar)::value>
-                <<<grid, NTT_THREADS, 0, s>>>(a, T, L, pc, K);
-        }); break;
-        case 6: with_int_arith(T, [&](auto ar) {
-            k_row3_inner_int<6, LOGC, INVP, decltype(ar)::value>
-                <<<grid, NTT_THREADS, 0, s>>>(a, T, L, pc, K);
-        }); break;
-        default: throw std::invalid_argument("more than 6 key-switch digits unsupported");
-    }
+    if (!dispatch<1, 2, 3, 4, 5, 6>(nparts, [&](auto np) {
+            with_int_arith(T, [&](auto ar) {
+                k_row3_inner_int<decltype(np)::value, LOGC, INVP, decltype(ar)::value>
+                    <<<grid, NTT_THREADS, 0, s>>>(a, T, L, pc, K);
+            });
+        }))
+        throw std::invalid_argument("more than 6 key-switch digits unsupported");
 }
 // integer slots of the extended basis: Q slots (q0) keep their accumulators in til; P slots continue into the inverse
 // row pass when `pc` is given (its own kernel instance: different epilogue, different register budget)
@@ -1737,16 +1622,21 @@ bool Engine::keyswitch_digits(const u64 *c1, size_t ct_stride, const u64 *evk, u
     if (fuse) {
         InnerArgs a{dig, c1, evk, til, ct_stride, nl, ext, D, ps_.alpha, cnt, fp_mask,
                     (uint32_t)__builtin_popcountll(fp_mask)};
-        if (row_h == 9) launch_row3_inner_fp_n<3>(a, tabs_, nparts, stream_);
-        else if (row_h == 4) launch_row_inner_fp_n<4>(a, tabs_, nparts, stream_);
-        else launch_row_inner_fp_n<3>(a, tabs_, nparts, stream_);
+        if (!dispatch<3, 4, 9>(row_h, [&](auto rh) {
+                if constexpr (decltype(rh)::value == 9) launch_row3_inner_fp_n<3>(a, tabs_, nparts, stream_);
+                else launch_row_inner_fp_n<decltype(rh)::value>(a, tabs_, nparts, stream_);
+            }))
+            throw std::logic_error("fused fp64 inner product: no kernel for this row radix");
     }
     const unsigned long long mask = fuse ? (all_mask & ~fp_mask) : all_mask;
     if (fuse_int) {  // integer limbs: row pass + inner product in one three-round kernel as well
         InnerArgs a{dig, c1, evk, til, ct_stride, nl, ext, D, ps_.alpha, cnt, mask, (uint32_t)__builtin_popcountll(mask)};
         u64 *pc_fused = pc;
-        if (row_h == 9) launch_row3_inner_int_n<3>(a, tabs_, nparts, ps_.L, pc_fused, ps_.K, stream_);
-        else launch_row3_inner_int_n<2>(a, tabs_, nparts, ps_.L, pc_fused, ps_.K, stream_);
+        // 256-point rows: 8 x 8 x 4 (LOGC 2); 512-point rows: 8 x 8 x 8 (LOGC 3)
+        if (!dispatch<4, 9>(row_h, [&](auto rh) {
+                launch_row3_inner_int_n<decltype(rh)::value == 9 ? 3 : 2>(a, tabs_, nparts, ps_.L, pc_fused, ps_.K, stream_);
+            }))
+            throw std::logic_error("fused integer inner product: no kernel for this row radix");
         MK_HIP(hipGetLastError());
         return pc_fused != nullptr;
     }
@@ -1759,15 +1649,10 @@ void Engine::inner_product_all(const u64 *c1, size_t ct_stride, const u64 *evk, 
                                uint32_t nl, unsigned long long mask) {
     const uint32_t n = ps_.n, ext = nl + ps_.K, nparts = ps_.num_parts(nl), D = ps_.D;
     EwGeom g{n, nl, ps_.L};
-    switch (nparts) {
-        case 1: launch_inner<1>(dig, c1, ct_stride, evk, til, g, d_limb_, ext, D, ps_.alpha, cnt, mask, stream_); break;
-        case 2: launch_inner<2>(dig, c1, ct_stride, evk, til, g, d_limb_, ext, D, ps_.alpha, cnt, mask, stream_); break;
-        case 3: launch_inner<3>(dig, c1, ct_stride, evk, til, g, d_limb_, ext, D, ps_.alpha, cnt, mask, stream_); break;
-        case 4: launch_inner<4>(dig, c1, ct_stride, evk, til, g, d_limb_, ext, D, ps_.alpha, cnt, mask, stream_); break;
-        case 5: launch_inner<5>(dig, c1, ct_stride, evk, til, g, d_limb_, ext, D, ps_.alpha, cnt, mask, stream_); break;
-        case 6: launch_inner<6>(dig, c1, ct_stride, evk, til, g, d_limb_, ext, D, ps_.alpha, cnt, mask, stream_); break;
-        default: throw std::invalid_argument("more than 6 key-switch digits unsupported");
-    }
+    if (!dispatch<1, 2, 3, 4, 5, 6>(nparts, [&](auto np) {
+            launch_inner<decltype(np)::value>(dig, c1, ct_stride, evk, til, g, d_limb_, ext, D, ps_.alpha, cnt, mask, stream_);
+        }))
+        throw std::invalid_argument("more than 6 key-switch digits unsupported");
     MK_HIP(hipGetLastError());
 }
 
@@ -1790,15 +1675,10 @@ template <int LOGC, int MINW, bool W = false>
 static void launch_qsum3_fp(const QSumArgs &a, const NttTables &T, uint32_t nparts, hipStream_t s) {
     const uint32_t tiles = (1u << T.log_r1) / RowT<LOGC>::ROWS;
     const dim3 grid(tiles * a.nsel * a.cnt);
-    switch (nparts) {
-        case 1: k_qsum3_fp<1, LOGC, MINW, W><<<grid, NTT_THREADS, 0, s>>>(a, T); break;
-        case 2: k_qsum3_fp<2, LOGC, MINW, W><<<grid, NTT_THREADS, 0, s>>>(a, T); break;
-        case 3: k_qsum3_fp<3, LOGC, MINW, W><<<grid, NTT_THREADS, 0, s>>>(a, T); break;
-        case 4: k_qsum3_fp<4, LOGC, MINW, W><<<grid, NTT_THREADS, 0, s>>>(a, T); break;
-        case 5: k_qsum3_fp<5, LOGC, MINW, W><<<grid, NTT_THREADS, 0, s>>>(a, T); break;
-        case 6: k_qsum3_fp<6, LOGC, MINW, W><<<grid, NTT_THREADS, 0, s>>>(a, T); break;
-        default: throw std::invalid_argument("more than 6 key-switch digits unsupported");
-    }
+    if (!dispatch<1, 2, 3, 4, 5, 6>(nparts, [&](auto np) {
+            k_qsum3_fp<decltype(np)::value, LOGC, MINW, W><<<grid, NTT_THREADS, 0, s>>>(a, T);
+        }))
+        throw std::invalid_argument("more than 6 key-switch digits unsupported");
 }
 
 // per Q limb: P mod q, (P mod q)/q, P^-1 mod q, (P^-1 mod q)/q as doubles (fp64-class limbs; zeros elsewhere)
@@ -1850,6 +1730,12 @@ void Engine::reencrypt_sum_merged(const u64 *cts, const u64 *evks, u64 *out, uin
     for (uint32_t k = 0; k < K; ++k) max_p = std::max(max_p, ps_.moduli[ps_.L + k]);
     const uint32_t group = std::min({n_clients, knobs_.qsum_group, (uint32_t)std::min<u64>(64, ~0ull / max_p)});
     const bool wide_rows = fast_row(tabs_.log_r2, 1u << tabs_.log_r1) == 9;  // N = 2^17: 512-point rows, three-round kernels
+    // the kernel instances of this call, f(lc, w): LOGC 2 (256-point rows) or 3 (512-point), w = std::bool_constant<weighted>
+    auto with_rows_and_weight = [&](auto &&f) {
+        dispatch<2, 3>(wide_rows ? 3 : 2, [&](auto lc) {
+            dispatch<0, 1>(wt ? 1 : 0, [&](auto w) { f(lc, std::bool_constant<decltype(w)::value != 0>{}); });
+        });
+    };
     // One stream: running the memory-bound sums of group g on a second stream beside the multiply-bound phases of group
     // g+1 was measured neutral to slightly negative (20.47 k against 20.59 k ct/s at groups of 4): both kinds of kernel
     // fill the register file of a CU, so the hardware time-slices them instead of co-scheduling.
@@ -1909,24 +1795,13 @@ void Engine::reencrypt_sum_merged(const u64 *cts, const u64 *evks, u64 *out, uin
                 TailOnceArgs ta{convsum, til, ct0, out + (size_t)b0 * ct_words, pinv, pinv + nl,
                                 (size_t)cnt * 2 * n_intq * n, ct_cstride, ct_words, gc, nl, 2 * cnt, intq_mask, n_intq,
                                 g0 != 0 ? 1u : 0u, wt ? wt + (size_t)g0 * D * WT_WORDS : nullptr, D};
-                const uint32_t tiles = (1u << tabs_.log_r1) / (wide_rows ? RowT<3>::ROWS : RowT<2>::ROWS);
-                const dim3 grid(tiles * n_intq * 2 * cnt);
-                if (wt) {  // weighted: M_c * c0 per client
-                    if (wide_rows) with_int_arith(tabs_, [&](auto ar) {
-                        k_row3_tail_once<3, decltype(ar)::value, true>
+                with_rows_and_weight([&](auto lc, auto w) {  // weighted: M_c * c0 per client
+                    constexpr int LOGC = decltype(lc)::value;
+                    const dim3 grid(((1u << tabs_.log_r1) / RowT<LOGC>::ROWS) * n_intq * 2 * cnt);
+                    with_int_arith(tabs_, [&](auto ar) {
+                        k_row3_tail_once<LOGC, decltype(ar)::value, decltype(w)::value>
                             <<<grid, NTT_THREADS, 0, main>>>(ta, tabs_);
                     });
-                    else with_int_arith(tabs_, [&](auto ar) {
-                        k_row3_tail_once<2, decltype(ar)::value, true>
-                            <<<grid, NTT_THREADS, 0, main>>>(ta, tabs_);
-                    });
-                } else if (wide_rows) with_int_arith(tabs_, [&](auto ar) {
-                    k_row3_tail_once<3, decltype(ar)::value>
-                        <<<grid, NTT_THREADS, 0, main>>>(ta, tabs_);
-                });
-                else with_int_arith(tabs_, [&](auto ar) {
-                    k_row3_tail_once<2, decltype(ar)::value>
-                        <<<grid, NTT_THREADS, 0, main>>>(ta, tabs_);
                 });
             }
             QSumArgs qa{dig, convsum, ct0, evk0, out + (size_t)b0 * ct_words, pq, ct_cstride, ct_words, evk_words, ct_words,
@@ -1935,11 +1810,9 @@ void Engine::reencrypt_sum_merged(const u64 *cts, const u64 *evks, u64 *out, uin
             // 256-point rows: 2 workgroups per CU -- at N = 2^16, L = 12 the kernel's 5 632 workgroups then fill the 512 resident
             // slots exactly 11 times (7.33 times 768 at 3 per CU: a last round a third full) and nothing is parked in scratch;
             // +0.45 % on the step after the eval-key bursts (it was +-0 before them)
-            if (wt) {
-                if (wide_rows) launch_qsum3_fp<3, 3, true>(qa, tabs_, nparts, main);
-                else launch_qsum3_fp<2, 2, true>(qa, tabs_, nparts, main);
-            } else if (wide_rows) launch_qsum3_fp<3, 3>(qa, tabs_, nparts, main);
-            else launch_qsum3_fp<2, 2>(qa, tabs_, nparts, main);
+            with_rows_and_weight([&](auto lc, auto w) {  // MINW = LOGC: the two pairs the kernel exists for
+                launch_qsum3_fp<decltype(lc)::value, decltype(lc)::value, decltype(w)::value>(qa, tabs_, nparts, main);
+            });
             MK_HIP(hipGetLastError());
         }
     }
@@ -2111,15 +1984,10 @@ static void launch_fan3(const FanArgs &a0, const NttTables &T, uint32_t L, unsig
 template <int LOGC>
 static void launch_fan3_n(const FanArgs &a, const NttTables &T, uint32_t nparts, uint32_t L, unsigned long long fp_mask,
                           unsigned long long intq_mask, unsigned long long p_mask, hipStream_t s) {
-    switch (nparts) {
-        case 1: launch_fan3<1, LOGC>(a, T, L, fp_mask, intq_mask, p_mask, s); break;
-        case 2: launch_fan3<2, LOGC>(a, T, L, fp_mask, intq_mask, p_mask, s); break;
-        case 3: launch_fan3<3, LOGC>(a, T, L, fp_mask, intq_mask, p_mask, s); break;
-        case 4: launch_fan3<4, LOGC>(a, T, L, fp_mask, intq_mask, p_mask, s); break;
-        case 5: launch_fan3<5, LOGC>(a, T, L, fp_mask, intq_mask, p_mask, s); break;
-        case 6: launch_fan3<6, LOGC>(a, T, L, fp_mask, intq_mask, p_mask, s); break;
-        default: throw std::invalid_argument("more than 6 key-switch digits unsupported");
-    }
+    if (!dispatch<1, 2, 3, 4, 5, 6>(nparts, [&](auto np) {
+            launch_fan3<decltype(np)::value, LOGC>(a, T, L, fp_mask, intq_mask, p_mask, s);
+        }))
+        throw std::invalid_argument("more than 6 key-switch digits unsupported");
 }
 
 // the fused fan-out kernels need what keyswitch_digits needs for its fully fused form: radix column kernels, 256- or
@@ -2328,36 +2196,30 @@ void Engine::decrypt(const u64 *ct, const u64 *sk, u64 *m, uint32_t n_ct, uint32
 
 // ---- re-randomisation before a key switch (PREBase::ReEncrypt(ct, evalKey, publicKey) -> EncryptZeroCore) ----------
 
-template <int COL_H, int ROW_H>
+// The fused endpoints (re-randomisation, partial decryption, collective key switch) run one column and one row kernel
+// per arithmetic class of the first nl limbs: f(col_h, row_h, ar, mask, nsel) with the radices of the two passes (2, 3 or
+// 4 each: two-round rows only) and the class as integral constants.  A ring size without such a pair is the caller's
+// to keep away (the `fused` conditions of the three endpoints): it throws here instead of launching nothing.
+template <typename F>
+static void for_each_radix_class(const NttTables &T, uint32_t nl, F &&f) {
+    bool found = false;
+    dispatch<2, 3, 4>(fast_log_h(T.log_r1, 1u << T.log_r2), [&](auto col_h) {
+        found = dispatch<2, 3, 4>(fast_row(T.log_r2, 1u << T.log_r1), [&](auto row_h) {
+            for_each_class(T, limb_classes(nl, T),
+                           [&](auto ar, unsigned long long mask, uint32_t nsel) { f(col_h, row_h, ar, mask, nsel); });
+        });
+    });
+    if (!found) throw std::logic_error("fused endpoint needs a radix column pass and a two-round radix row pass");
+}
+
 static void launch_rerand(LiftIo li, RerandArgs ra, const NttTables &T, uint32_t cnt, hipStream_t s) {
-    const uint32_t r1 = 1u << T.log_r1, r2 = 1u << T.log_r2;
-    NttIo sel{};
-    sel.nslots = sel.nl = ra.nl;
-    for (int fp = 0; fp < 2; ++fp) {
-        const unsigned long long mask = class_mask(sel, T.h_fp_of, T.L, fp != 0);
-        const uint32_t nsel = (uint32_t)__builtin_popcountll(mask);
-        if (!nsel) continue;
+    for_each_radix_class(T, ra.nl, [&](auto col_h, auto row_h, auto ar, unsigned long long mask, uint32_t nsel) {
+        constexpr int COL_H = decltype(col_h)::value, ROW_H = decltype(row_h)::value, AR = decltype(ar)::value;
         li.slot_mask = ra.slot_mask = mask;
         li.nsel = ra.nsel = nsel;
-        const dim3 cgrid(r2 / (256u >> COL_H), 3 * nsel, cnt), rgrid((r1 / (256u >> ROW_H)) * nsel * cnt);
-        if (fp) {
-            k_lift_col<COL_H, AR_FP><<<cgrid, NTT_THREADS, 0, s>>>(li, T);
-            k_rerand_row<ROW_H, AR_FP><<<rgrid, NTT_THREADS, 0, s>>>(ra, T);
-        } else {
-            with_int_arith(T, [&](auto ar) {
-                k_lift_col<COL_H, decltype(ar)::value><<<cgrid, NTT_THREADS, 0, s>>>(li, T);
-                k_rerand_row<ROW_H, decltype(ar)::value><<<rgrid, NTT_THREADS, 0, s>>>(ra, T);
-            });
-        }
-    }
-}
-template <int COL_H>
-static void launch_rerand_c(const LiftIo &li, const RerandArgs &ra, const NttTables &T, uint32_t cnt, int row_h, hipStream_t s) {
-    switch (row_h) {
-        case 4: launch_rerand<COL_H, 4>(li, ra, T, cnt, s); break;
-        case 3: launch_rerand<COL_H, 3>(li, ra, T, cnt, s); break;
-        default: launch_rerand<COL_H, 2>(li, ra, T, cnt, s);
-    }
+        k_lift_col<COL_H, AR><<<dim3(col_tiles<COL_H>(T), 3 * nsel, cnt), NTT_THREADS, 0, s>>>(li, T);
+        k_rerand_row<ROW_H, AR><<<dim3(row_tiles<ROW_H>(T) * nsel * cnt), NTT_THREADS, 0, s>>>(ra, T);
+    });
 }
 
 void Engine::rerandomize(const u64 *ct, const u64 *pk, const int8_t *v, const int64_t *e0, const int64_t *e1, u64 *out,
@@ -2383,11 +2245,7 @@ void Engine::rerandomize(const u64 *ct, const u64 *pk, const int8_t *v, const in
         if (fused) {
             const LiftIo li{vb, e0b, e1b, ws, nl, 0, 0};
             const RerandArgs ra{ws, cin, pk, cout, nl_in, nl, D, 0, 0};
-            switch (col_h) {
-                case 4: launch_rerand_c<4>(li, ra, tabs_, cnt, row_h, stream_); break;
-                case 3: launch_rerand_c<3>(li, ra, tabs_, cnt, row_h, stream_); break;
-                default: launch_rerand_c<2>(li, ra, tabs_, cnt, row_h, stream_);
-            }
+            launch_rerand(li, ra, tabs_, cnt, stream_);
             MK_HIP(hipGetLastError());
         } else {  // the composition of Engine::encrypt with the ciphertext's components in the plaintext's place
             u64 *ve = ws, *e0e = ve + poly * cnt, *e1e = e0e + poly * cnt;
@@ -2429,36 +2287,14 @@ void Engine::keygen_join(const u64 *pk_prev, const int8_t *s, const int32_t *e, 
                               stream_));
 }
 
-template <int COL_H, int ROW_H>
 static void launch_pdec(PdecArgs pa, const NttTables &T, uint32_t cnt, hipStream_t s) {
-    const uint32_t r1 = 1u << T.log_r1, r2 = 1u << T.log_r2;
-    NttIo sel{};
-    sel.nslots = sel.nl = pa.nl;
-    for (int fp = 0; fp < 2; ++fp) {
-        const unsigned long long mask = class_mask(sel, T.h_fp_of, T.L, fp != 0);
-        const uint32_t nsel = (uint32_t)__builtin_popcountll(mask);
-        if (!nsel) continue;
+    for_each_radix_class(T, pa.nl, [&](auto col_h, auto row_h, auto ar, unsigned long long mask, uint32_t nsel) {
+        constexpr int COL_H = decltype(col_h)::value, ROW_H = decltype(row_h)::value, AR = decltype(ar)::value;
         pa.slot_mask = mask;
         pa.nsel = nsel;
-        const dim3 rgrid((r1 / (256u >> ROW_H)) * nsel * cnt), cgrid(r2 / (256u >> COL_H), nsel, cnt);
-        if (fp) {
-            k_pdec_row<ROW_H, AR_FP><<<rgrid, NTT_THREADS, 0, s>>>(pa, T);
-            k_pdec_col<COL_H, AR_FP><<<cgrid, NTT_THREADS, 0, s>>>(pa, T);
-        } else {
-            with_int_arith(T, [&](auto ar) {
-                k_pdec_row<ROW_H, decltype(ar)::value><<<rgrid, NTT_THREADS, 0, s>>>(pa, T);
-                k_pdec_col<COL_H, decltype(ar)::value><<<cgrid, NTT_THREADS, 0, s>>>(pa, T);
-            });
-        }
-    }
-}
-template <int COL_H>
-static void launch_pdec_c(const PdecArgs &pa, const NttTables &T, uint32_t cnt, int row_h, hipStream_t s) {
-    switch (row_h) {
-        case 4: launch_pdec<COL_H, 4>(pa, T, cnt, s); break;
-        case 3: launch_pdec<COL_H, 3>(pa, T, cnt, s); break;
-        default: launch_pdec<COL_H, 2>(pa, T, cnt, s);
-    }
+        k_pdec_row<ROW_H, AR><<<dim3(row_tiles<ROW_H>(T) * nsel * cnt), NTT_THREADS, 0, s>>>(pa, T);
+        k_pdec_col<COL_H, AR><<<dim3(col_tiles<COL_H>(T), nsel, cnt), NTT_THREADS, 0, s>>>(pa, T);
+    });
 }
 
 void Engine::partial_decrypt(const u64 *ct, const u64 *sk, const int64_t *e, u64 *share, uint32_t n_ct, uint32_t nl_in,
@@ -2485,11 +2321,7 @@ void Engine::partial_decrypt(const u64 *ct, const u64 *sk, const int64_t *e, u64
         u64 *out = share + (size_t)b0 * poly;
         if (fused) {
             const PdecArgs pa{cin, sk, eb, out, nl_in, nl, lead ? 1u : 0u, 0, 0};
-            switch (col_h) {
-                case 4: launch_pdec_c<4>(pa, tabs_, cnt, row_h, stream_); break;
-                case 3: launch_pdec_c<3>(pa, tabs_, cnt, row_h, stream_); break;
-                default: launch_pdec_c<2>(pa, tabs_, cnt, row_h, stream_);
-            }
+            launch_pdec(pa, tabs_, cnt, stream_);
             MK_HIP(hipGetLastError());
         } else {  // Engine::decrypt on the prefix, then the lifted error added
             EwGeom g{n, nl, ps_.L};
@@ -2507,36 +2339,14 @@ void Engine::partial_decrypt(const u64 *ct, const u64 *sk, const int64_t *e, u64
 
 // ---- collective public-key switch: one party's share (Mouchet et al., PCKS) -----------------------------------------
 
-template <int COL_H, int ROW_H>
 static void launch_kswitch(LiftIo li, KswitchArgs ka, const NttTables &T, uint32_t cnt, hipStream_t s) {
-    const uint32_t r1 = 1u << T.log_r1, r2 = 1u << T.log_r2;
-    NttIo sel{};
-    sel.nslots = sel.nl = ka.nl;
-    for (int fp = 0; fp < 2; ++fp) {
-        const unsigned long long mask = class_mask(sel, T.h_fp_of, T.L, fp != 0);
-        const uint32_t nsel = (uint32_t)__builtin_popcountll(mask);
-        if (!nsel) continue;
+    for_each_radix_class(T, ka.nl, [&](auto col_h, auto row_h, auto ar, unsigned long long mask, uint32_t nsel) {
+        constexpr int COL_H = decltype(col_h)::value, ROW_H = decltype(row_h)::value, AR = decltype(ar)::value;
         li.slot_mask = ka.slot_mask = mask;
         li.nsel = ka.nsel = nsel;
-        const dim3 cgrid(r2 / (256u >> COL_H), 3 * nsel, cnt), rgrid((r1 / (256u >> ROW_H)) * nsel * cnt);
-        if (fp) {
-            k_lift_col<COL_H, AR_FP><<<cgrid, NTT_THREADS, 0, s>>>(li, T);
-            k_kswitch_row<ROW_H, AR_FP><<<rgrid, NTT_THREADS, 0, s>>>(ka, T);
-        } else {
-            with_int_arith(T, [&](auto ar) {
-                k_lift_col<COL_H, decltype(ar)::value><<<cgrid, NTT_THREADS, 0, s>>>(li, T);
-                k_kswitch_row<ROW_H, decltype(ar)::value><<<rgrid, NTT_THREADS, 0, s>>>(ka, T);
-            });
-        }
-    }
-}
-template <int COL_H>
-static void launch_kswitch_c(const LiftIo &li, const KswitchArgs &ka, const NttTables &T, uint32_t cnt, int row_h, hipStream_t s) {
-    switch (row_h) {
-        case 4: launch_kswitch<COL_H, 4>(li, ka, T, cnt, s); break;
-        case 3: launch_kswitch<COL_H, 3>(li, ka, T, cnt, s); break;
-        default: launch_kswitch<COL_H, 2>(li, ka, T, cnt, s);
-    }
+        k_lift_col<COL_H, AR><<<dim3(col_tiles<COL_H>(T), 3 * nsel, cnt), NTT_THREADS, 0, s>>>(li, T);
+        k_kswitch_row<ROW_H, AR><<<dim3(row_tiles<ROW_H>(T) * nsel * cnt), NTT_THREADS, 0, s>>>(ka, T);
+    });
 }
 
 void Engine::switch_share(const u64 *ct, const u64 *sk, const u64 *pk, const int8_t *v, const int64_t *e0, const int64_t *e1,
@@ -2564,11 +2374,7 @@ void Engine::switch_share(const u64 *ct, const u64 *sk, const u64 *pk, const int
         if (fused) {
             const LiftIo li{vb, e0b, e1b, ws, nl, 0, 0};
             const KswitchArgs ka{ws, cin, sk, pk, cout, nl_in, nl, D, lead ? 1u : 0u, 0, 0};
-            switch (col_h) {
-                case 4: launch_kswitch_c<4>(li, ka, tabs_, cnt, row_h, stream_); break;
-                case 3: launch_kswitch_c<3>(li, ka, tabs_, cnt, row_h, stream_); break;
-                default: launch_kswitch_c<2>(li, ka, tabs_, cnt, row_h, stream_);
-            }
+            launch_kswitch(li, ka, tabs_, cnt, stream_);
             MK_HIP(hipGetLastError());
         } else {  // Engine::rerandomize's composition on the ciphertext (c1 * s (+ c0), 0): x from one k_fma into the workspace
             u64 *ve = ws, *e0e = ve + poly * cnt, *e1e = e0e + poly * cnt, *x = ws + 3 * poly * cmax;

@@ -51,11 +51,6 @@ struct DevConv {
     const double *hatq_d;  // device, [n_in][n_out]: [S/s_i]_t / t
 };
 
-// the stream a pass is launched on
-struct Lanes {
-    hipStream_t main = nullptr;
-};
-
 // Switches of the library (environment variables MKCKKS_*), read once when a context is created.  Defaults are the
 // measured best; every non-default value has a parity test (tests/test_gpu_parity.py).
 struct Knobs {
@@ -210,7 +205,6 @@ public:
 
 private:
     void need_device() const;
-    Lanes lanes() const;
     void check_nl(uint32_t nl) const;
     u64 *workspace(size_t words);  // grow-only scratch arena (stream-ordered reuse)
     const DevConv &modup_conv(uint32_t nl, uint32_t part);

@@ -72,7 +72,8 @@ def test_ntt_roundtrip_and_parity(ctxs, name):
         assert np.array_equal(inv[0, j], o.ntt_inv(l, x[0, j]))
 
 
-@pytest.mark.parametrize("log_n,generic", [(9, False), (11, False), (13, False), (17, False), (12, True), (16, True)])
+@pytest.mark.parametrize("log_n,generic", [(9, False), (11, False), (13, False), (15, False), (17, False), (12, True),
+                                            (16, True)])
 def test_ntt_other_sizes_and_generic_kernels(log_n, generic, monkeypatch):
     # odd log N and N = 2^17 take the generic LDS-stage kernels for one or both passes; MKCKKS_GENERIC_NTT=1
     # forces them everywhere.  Both schedules must give the same bits as the oracle.
