@@ -18,7 +18,7 @@ CONFIGS = {
     "c3": (16, 10, 50, 60, 3),        # BASELINE configs[1..2]: N=2^16, L=12, dnum=3
     "c5s": (12, 18, 50, 60, 3),       # BASELINE configs[4] limb structure (L=20, alpha=7, K=7) at a small ring
     "n17": (17, 2, 50, 60, 2),        # BASELINE configs[4] ring dimension (radix column pass + generic row pass)
-    "n11": (11, 2, 40, 60, 2),        # odd log N: generic kernels for both passes, integer arithmetic only
+    "n11": (11, 2, 40, 60, 2),        # odd log N: generic column pass (32 points), radix-8 row pass (64-point rows: k_ntt_row_r<3>); integer arithmetic only
 }
 
 
