@@ -169,6 +169,12 @@ int mkckks_reencrypt_accumulate_batch(mkckks_ctx *c, const uint64_t *d_ct, const
  * adding them in any order; the last ModDown pass of all clients and the sum are one kernel. */
 int mkckks_reencrypt_sum_batch(mkckks_ctx *c, const uint64_t *d_cts, const uint64_t *d_evks, uint64_t *d_out,
                                uint32_t n_clients, uint32_t n_ct, uint32_t nl);
+/* The form the integer-class Q limbs (q_0) take inside mkckks_reencrypt_sum_batch / mkckks_reencrypt_wsum_batch for a
+ * chunk of n_idx ciphertext indices on a ring with row_tiles row tiles and n_int_q such limbs: 1 = one kernel whose
+ * workgroup walks the clients, 0 = two kernels through a compact workspace.  mode is the switch MKCKKS_Q0_WALK: 0 and 1
+ * force a form, any other value chooses by grid size.  A pure function (no context, no device); both forms give the same
+ * bits. */
+int mkckks_q0_walk_choice(uint32_t row_tiles, uint32_t n_int_q, uint32_t n_idx, int mode);
 /* ---- weighted aggregation: sum_c w_c * x_c in place of the plain mean -----------------------------------------------
  * The weighted form of the server loop (ReEncrypt x n, then per client cc->EvalMult(ct, w_c) as at
  * aggregateEncryptedWeights.cpp:82-83, then the EvalAdd chain), with the weights folded into what the merged n-client

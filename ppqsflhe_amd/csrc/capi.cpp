@@ -315,6 +315,9 @@ int mkckks_reencrypt_sum_batch(mkckks_ctx *c, const uint64_t *cts, const uint64_
         c->eng->reencrypt_sum(cts, evks, out, n_clients, n_ct, nl);
     });
 }
+int mkckks_q0_walk_choice(uint32_t row_tiles, uint32_t n_int_q, uint32_t n_idx, int mode) {
+    return mk::q0_walk_fused(row_tiles, n_int_q, n_idx, mode) ? 1 : 0;
+}
 int mkckks_scale_evk_batch(mkckks_ctx *c, const uint64_t *d_evk_in, uint64_t *d_evk_out, uint32_t n_keys,
                            const double *h_weights, uint32_t sf_level) {
     return guarded([&] {

@@ -592,6 +592,10 @@ Knobs Knobs::from_env() {
     k.generic_ntt = env_flag("MKCKKS_GENERIC_NTT", k.generic_ntt);
     k.no_pm = env_flag("MKCKKS_NO_PM", k.no_pm);
     k.no_fp64 = env_flag("MKCKKS_NO_FP64", k.no_fp64);
+    if (const char *e = std::getenv("MKCKKS_Q0_WALK")) {
+        if (!std::strcmp(e, "0")) k.q0_walk = 0;
+        else if (!std::strcmp(e, "1")) k.q0_walk = 1;
+    }
     return k;
 }
 
@@ -1681,6 +1685,20 @@ static void launch_qsum3_fp(const QSumArgs &a, const NttTables &T, uint32_t npar
         throw std::invalid_argument("more than 6 key-switch digits unsupported");
 }
 
+// the integer-class Q limbs (a.slot_mask) in the same shape; two digits at least (a single-digit context keeps the
+// two-kernel form, whose q_0 instance runs 3 waves per SIMD)
+template <int LOGC, bool W>
+static void launch_qsum3_int(const QSumArgs &a, const NttTables &T, uint32_t nparts, hipStream_t s) {
+    const uint32_t tiles = (1u << T.log_r1) / RowT<LOGC>::ROWS;
+    const dim3 grid(tiles * a.nsel * a.cnt);
+    if (!dispatch<2, 3, 4, 5, 6>(nparts, [&](auto np) {
+            with_int_arith(T, [&](auto ar) {
+                k_qsum3_int<decltype(np)::value, LOGC, decltype(ar)::value, W><<<grid, NTT_THREADS, 0, s>>>(a, T);
+            });
+        }))
+        throw std::invalid_argument("k_qsum3_int: 2 to 6 key-switch digits");
+}
+
 // per Q limb: P mod q, (P mod q)/q, P^-1 mod q, (P^-1 mod q)/q as doubles (fp64-class limbs; zeros elsewhere)
 const u64 *Engine::p_doubles() {
     auto it = vec_cache_.find("p_doubles");
@@ -1713,7 +1731,9 @@ bool Engine::qsum_ok(uint32_t nl) const {
 //   ModUp of c1 -> converted digits (column-passed)                          modup_core
 //   P limbs: row pass + eval-key inner product + inverse row pass            k_row3_inner_int<.., true>
 //   ApproxModDown's conversion P -> Q_l (column-passed)                      moddown_convert
-//   integer-class Q limbs (q_0): inner product, then row pass + tail + sum   k_row3_inner_int<.., false>, k_row3_tail_once
+//   integer-class Q limbs (q_0): everything that is left, summed over clients  k_qsum3_int
+//     calls whose grid cannot fill the chip (q0_walk_fused) and single-digit contexts: inner product through a compact
+//     til, then row pass + tail + sum                                        k_row3_inner_int<.., false>, k_row3_tail_once
 //   fp64-class Q limbs: everything that is left, summed over clients        k_qsum3_fp
 void Engine::reencrypt_sum_merged(const u64 *cts, const u64 *evks, u64 *out, uint32_t n_clients, uint32_t n_ct,
                                   uint32_t nl, const u64 *wt) {
@@ -1742,7 +1762,15 @@ void Engine::reencrypt_sum_merged(const u64 *cts, const u64 *evks, u64 *out, uin
     const uint32_t max_items = group * std::min(knobs_.chunk, n_ct);
     const size_t w_coef = (size_t)max_items * nl * n, w_dig = (size_t)max_items * nparts * ext * n;
     const size_t w_pc = (size_t)max_items * 2 * K * n;
-    const size_t w_til = (size_t)max_items * 2 * n_intq * n;
+    // q_0 in one kernel or in two, per chunk (the last chunk of a call may be shorter and take the other form)
+    const uint32_t q0_tiles = (1u << tabs_.log_r1) / (wide_rows ? RowT<3>::ROWS : RowT<2>::ROWS);
+    auto q0_fused = [&](uint32_t cnt) {
+        return n_intq != 0 && nparts >= 2 && q0_walk_fused(q0_tiles, n_intq, cnt, knobs_.q0_walk);
+    };
+    const uint32_t cnt_full = std::min(knobs_.chunk, n_ct), cnt_last = n_ct % knobs_.chunk ? n_ct % knobs_.chunk : cnt_full;
+    // the compact til exists only for the two-kernel form
+    const bool any_til = n_intq != 0 && (!q0_fused(cnt_full) || !q0_fused(cnt_last));
+    const size_t w_til = any_til ? (size_t)max_items * 2 * n_intq * n : 0;
     const size_t w_csum = (size_t)std::min(knobs_.chunk, n_ct) * 2 * nl * n;  // conversions summed over a group's clients
     const size_t w_psum = (size_t)std::min(knobs_.chunk, n_ct) * 2 * K * n;   // P-limb coefficients summed over a group's clients
     u64 *ws = workspace(w_coef + w_dig + w_pc + w_til + w_csum + w_psum);
@@ -1782,7 +1810,8 @@ void Engine::reencrypt_sum_merged(const u64 *cts, const u64 *evks, u64 *out, uin
                 ConvIo cs{psum, convsum, (size_t)K * n, (size_t)nl * n, 2 * cnt, 0, 0};
                 launch_conv_col_psum(cs, tabs_, moddown_conv(nl), main);
             }
-            if (n_intq) {  // integer-class Q limbs: accumulators through a compact til
+            const bool fused_q0 = q0_fused(cnt);
+            if (n_intq && !fused_q0) {  // integer-class Q limbs: accumulators through a compact til
                 InnerArgs aq = ia;
                 aq.slot_mask = intq_mask;
                 aq.nsel = n_intq;
@@ -1791,7 +1820,14 @@ void Engine::reencrypt_sum_merged(const u64 *cts, const u64 *evks, u64 *out, uin
                 else launch_row3_inner_int_k<2, false>(aq, tabs_, nparts, ps_.L, nullptr, K, main);
             }
             MK_HIP(hipGetLastError());
-            if (n_intq) {  // q_0: row pass of the summed conversion, tail, sum over the group's clients
+            if (fused_q0) {  // q_0: inner products, sum over the group's clients, summed conversion and tail in one kernel
+                QSumArgs qi{dig, convsum, ct0, evk0, out + (size_t)b0 * ct_words, pq, ct_cstride, ct_words, evk_words, ct_words,
+                            gc, cnt, nl, ext, D, ps_.alpha, intq_mask, n_intq, g0 != 0 ? 1u : 0u,
+                            wt ? wt + (size_t)g0 * D * WT_WORDS : nullptr, pinv, pinv + nl};
+                with_rows_and_weight([&](auto lc, auto w) {
+                    launch_qsum3_int<decltype(lc)::value, decltype(w)::value>(qi, tabs_, nparts, main);
+                });
+            } else if (n_intq) {  // q_0: row pass of the summed conversion, tail, sum over the group's clients
                 TailOnceArgs ta{convsum, til, ct0, out + (size_t)b0 * ct_words, pinv, pinv + nl,
                                 (size_t)cnt * 2 * n_intq * n, ct_cstride, ct_words, gc, nl, 2 * cnt, intq_mask, n_intq,
                                 g0 != 0 ? 1u : 0u, wt ? wt + (size_t)g0 * D * WT_WORDS : nullptr, D};

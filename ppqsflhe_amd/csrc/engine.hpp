@@ -64,8 +64,21 @@ struct Knobs {
     bool generic_ntt = false;    // MKCKKS_GENERIC_NTT=1: LDS-stage kernels for both passes
     bool no_pm = false;          // MKCKKS_NO_PM=1: Shoup butterflies on the integer limbs instead of the pseudo-Mersenne ones
     bool no_fp64 = false;        // MKCKKS_NO_FP64=1: integer arithmetic on every limb
+    int q0_walk = 2;             // MKCKKS_Q0_WALK=0/1/auto: the integer-class Q limbs of the merged n-client flow as two kernels
+                                 // (k_row3_inner_int + k_row3_tail_once), as one (k_qsum3_int), or chosen per call by grid size
     static Knobs from_env();
 };
+
+// The form the integer-class Q limbs (q_0) of the merged n-client flow take in a call with `tiles` row tiles, `nsel` such
+// limbs and `cnt` ciphertext indices: true = one launch of k_qsum3_int, whose workgroup walks the clients of a group;
+// false = k_row3_inner_int<.., false> + k_row3_tail_once.  mode 0 / 1 force a form, anything else chooses: the walk is
+// serial over the clients, so it pays only where its tiles * nsel * cnt workgroups fill the resident slots of the chip
+// (2 per CU x 256 CUs); profiles/q0_walk_ab.txt has the measured sweep.
+constexpr uint32_t Q0_WALK_MIN_GRID = 512;
+inline bool q0_walk_fused(uint32_t tiles, uint32_t nsel, uint32_t cnt, int mode) {
+    if (mode == 0 || mode == 1) return mode == 1;
+    return (uint64_t)tiles * nsel * cnt >= Q0_WALK_MIN_GRID;
+}
 
 class Engine {
 public:

@@ -263,6 +263,19 @@ MK_HD u64 pm_reduce128(u64 hi, u64 lo, const PmK &P, u64 q) {
 #endif
 }
 
+// ANY X = hi:lo < 2^128 -> X mod q in [0, q) (sums of more products than pm_reduce128 takes: up to 31 of a lazy word and a
+// residue).  The high word is folded whole with 2^64 = c64 (mod q) first: X' = hi c64 + lo < 2^94 + 2^64 (c64 <= 2^30), which
+// is inside pm_reduce128's range 2^(2k+6) for every k >= 45.
+MK_HD u64 pm_reduce128_wide(u64 hi, u64 lo, const PmK &P, u64 q) {
+    const u64 f0 = (u64)(uint32_t)hi * P.c64, f1 = (u64)(uint32_t)(hi >> 32) * P.c64;  // each < 2^62; f1 weighs 2^32
+    u64 nlo = lo + f0;
+    u64 nhi = (nlo < f0 ? 1u : 0u) + (f1 >> 32);
+    const u64 t = f1 << 32;
+    nlo += t;
+    nhi += nlo < t ? 1u : 0u;
+    return pm_reduce128(nhi, nlo, P, q);
+}
+
 // Barrett reduction of a 128-bit x = hi:lo with x < 2^(k+62) (k = bitlen q) to [0,q).
 // qhat = mulhi64(x >> (k-2), mu), mu = floor(2^(62+k)/q): qhat in {Q-2,Q-1,Q}.
 // (X/q - qhat's real value = (f1 m + a f2 - f1 f2) / 2^64 with a = x / 2^(k-2) < 2^64, m = 2^(62+k)/q <= 2^63 and the two

@@ -20,7 +20,7 @@
 // k_conv_col_psum (ApproxModDown's conversion for a whole group of clients), k_switch_col (rescale), k_row_inner_fp /
 // k_row3_inner_fp (forward row pass of the converted digits + eval-key inner product, fp64 limbs; single re-encryptions),
 // k_row3_inner_int (the same for the integer limbs, continuing into the inverse row pass on the P limbs),
-// k_row3_tail_once and, in qsum_kernels.hpp, k_qsum3_fp (the Q-limb half of the n-client step).  In every row kernel a
+// k_row3_tail_once and, in qsum_kernels.hpp, k_qsum3_fp / k_qsum3_int (the Q-limb half of the n-client step).  In every row kernel a
 // wavefront owns complete rows, so LDS hand-offs are wave-level (wave_lds_sync) and the kernels contain no workgroup
 // barrier after the twiddle staging.
 #pragma once

@@ -161,6 +161,25 @@ void check_prime(const mk::LimbConst &lc_in, Counts &n, u64 &rng) {
         ++n.red128;
     }
 
+    // ---- pm_reduce128_wide: any 128-bit value; k_qsum3_int's runs of 31 maximal products on top of a carried residue ------------
+    {
+        u128 X = q - 1;  // the canonical value carried over from the previous run
+        u64 hi = 0, lo = q - 1;
+        for (int t = 0; t < 31; ++t) {
+            X += (u128)amax * (q - 1);
+            mk::mac128(hi, lo, amax, q - 1);
+            if (hi != (u64)(X >> 64) || lo != (u64)X) fail("mac128: wrong sum in a run of 31", q);
+            if (mk::pm_reduce128_wide(hi, lo, P, q) != (u64)(X % q)) fail("pm_reduce128_wide: wrong residue in a run of 31", q);
+        }
+        for (u64 h : {(u64)0, (u64)1, (u64)0xffffffffull, (u64)0x100000000ull, ~(u64)0 - 1, ~(u64)0})
+            for (u64 l : {(u64)0, q - 1, q, (u64)0xffffffffull, (u64)(~(u64)0 - 0xffffffffull), ~(u64)0})
+                if (mk::pm_reduce128_wide(h, l, P, q) != (u64)((((u128)h << 64) | l) % q)) fail("pm_reduce128_wide: boundary words", q);
+        for (int it = 0; it < 500000; ++it) {
+            const u64 h = next(), l = it % 3 == 0 ? ~(u64)0 - (next() & 0xffffffffull) : next();
+            if (mk::pm_reduce128_wide(h, l, P, q) != (u64)((((u128)h << 64) | l) % q)) fail("pm_reduce128_wide: wrong residue", q);
+        }
+    }
+
     // ---- pm_reduce_cols: column sums of up to 4 products of 60-bit numbers split in 30-bit halves --------------------------
     for (int it = 0; it < 1000000 / 2; ++it) {
         mk::Cols cs{0, 0, 0};

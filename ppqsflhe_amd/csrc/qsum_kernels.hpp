@@ -1,4 +1,5 @@
-// qsum_kernels.hpp -- the Q-limb half of the n-client server step in ONE kernel (gfx950, fp64-class limbs).
+// qsum_kernels.hpp -- the Q-limb half of the n-client server step in ONE kernel per arithmetic class (gfx950): k_qsum3_fp
+// for the fp64-class limbs, described here, and k_qsum3_int below for the integer-class ones (q_0).
 //
 // For a (ciphertext index b, Q limb t, row tile) the workgroup walks ALL clients c and, per client,
 //   * finishes the forward transform (row pass) of every converted ModUp digit d_j[t] and accumulates the eval-key
@@ -40,6 +41,8 @@ struct QSumArgs {
     // weighted instance (W): client c, limb t at wt + (c * D + t) * 4: M_c mod q_t, its Shoup companion, and on fp64-class
     // Q limbs the doubles P * M_c mod q_t and that / q_t (Engine::weight_table)
     const u64 *wt;
+    // integer-class Q limbs (k_qsum3_int): P^-1 mod q_t and its Shoup companion per limb; slot_mask / nsel then select those limbs
+    const u64 *pinv = nullptr, *pinv_sh = nullptr;
 };
 
 // Three-round row geometry (RowT<LOGC>: 8 words per thread, 256-point rows as 8 x 8 x 4, 512-point rows as 8 x 8 x 8): the
@@ -242,6 +245,207 @@ __global__ __launch_bounds__(NTT_THREADS, MINW) void k_qsum3_fp(QSumArgs a, NttT
     t_mark = stm.add<3>(t_mark);
     stm.add<4>(t_begin);
     stm.flush<2>(T.stamps, false);
+}
+
+// The same shape for the INTEGER-class Q limbs (q_0): a workgroup owns (ciphertext index b, integer Q limb, row tile),
+// walks the clients of the group and keeps ONE pair of 128-bit accumulator sets over digits and clients, where
+// k_row3_inner_int<.., false> reduced them once per client and wrote them to a til that k_row3_tail_once read back and
+// summed.  The epilogue is k_row3_tail_once's, on its operands: forward row pass of the two summed ModDown conversions,
+//   out = ( sum_c ctilde_c - conv_sum ) * P^-1 + sum_c c0_c   (component 0; without the c0 term on component 1).
+// Ring arithmetic mod q throughout, and the stored words are canonical: they are those of the two-kernel form, bit for bit.
+//
+// Deferred reduction.  A product is (lazy transform output or canonical c1 word) x (eval-key residue):
+//   AR_PM:  the lazy words go in as they are, < 8U = 2^(k+3) <= 2^63; a residue is < 2^60: a product is < 2^123, and 31 of
+//           them plus the canonical value carried over from the previous run (< 2^60) stay below 32 * 2^123 = 2^128.
+//           pm_reduce128 itself stops at 2^(2k+6), i.e. 8 such products: the runs end in pm_reduce128_wide.
+//   AR_INT: the words are made canonical before the product (as in k_row3_inner_int), a product is < q^2 <= 2^120, and
+//           reduce_wide takes X < 2^124: 15 products plus the carried value (15 * 2^120 + 2^60 < 2^124).
+// A client adds NPARTS products to every accumulator, so a run is floor(31 / NPARTS) or floor(15 / NPARTS) clients; the
+// reduced value becomes the first addend of the next run.  The flagship's 8 clients x 3 digits are one run of 24.
+// c0 is summed as 64-bit integers of canonical residues, reduced every 8 terms (< 9 * 2^60), as in k_row3_tail_once.
+template <int AR>
+MK_HD constexpr int qsum_int_products() { return AR == AR_PM ? 31 : 15; }
+// The round-C twiddles are parked in LDS as in k_qsum3_fp (MK_QSUM_INT_PARK_C): held in registers across the client loop
+// they put 13-24 registers of the pseudo-Mersenne instances into scratch.
+#ifndef MK_QSUM_INT_PARK_C
+#define MK_QSUM_INT_PARK_C 1
+#endif
+template <int NPARTS, int LOGC, int AR, bool W = false>
+__global__ __launch_bounds__(NTT_THREADS, 2) void k_qsum3_int(QSumArgs a, NttTables T) {
+    using TL = RowT<LOGC>;
+    constexpr int R = TL::R, S = TL::ROWS, TPR = TL::TPR, PAIRS = 4;
+    static_assert(NPARTS >= 2 && NPARTS <= qsum_int_products<AR>(), "a client's products must fit one run");
+    constexpr uint32_t RUN = qsum_int_products<AR>() / NPARTS;  // clients between two reductions
+    constexpr bool PARK = MK_QSUM_INT_PARK_C != 0;
+    constexpr int NC = PARK ? (LOGC == 3 ? 7 : 6) : 0;
+    __shared__ u64 lds[TL::WORDS + 2 * (TL::TWA + TL::TWB)];
+    __shared__ ulong2 ldsc[NC ? NC * NTT_THREADS : 1];
+    Row3Ctx c;
+    c.lds = lds;
+    c.twa = lds + TL::WORDS;
+    c.twa_sh = c.twa + TL::TWA;
+    c.twb = c.twa_sh + TL::TWA;
+    c.twb_sh = c.twb + TL::TWB;
+    c.twc = ldsc;
+    const uint32_t n = 1u << T.log_n, r1 = 1u << T.log_r1;
+    const uint32_t tiles = r1 / S, groups = tiles * a.nsel;
+    uint32_t grp, b;
+    group_member(blockIdx.x, groups, a.cnt, T.cu_affine, grp, b);
+    const uint32_t sl = nth_set_bit(a.slot_mask, grp / tiles);  // Q limb: slot == limb id
+    const LimbConst lc = T.limb[sl];
+    const int own = (int)(sl / a.alpha), j0 = own == 0 ? 1 : 0;
+    const uint32_t row0 = (grp % tiles) * S;
+    c.g = threadIdx.x / TPR;
+    c.t = threadIdx.x % TPR;
+    const u64 *tw = T.tw + (size_t)sl * n, *tw_sh = T.tw_sh + (size_t)sl * n;
+    row3_stage_twiddles<LOGC>(c, tw, tw_sh, r1 + row0);
+    u64 wc[7], wpc[7];
+    row3_load_c_twiddles<LOGC>(tw, tw_sh, r1 + row0 + c.g, c.t, wc, wpc);
+    if (PARK) {
+        row3_park_c_twiddles<LOGC>(c, wc, wpc);
+#pragma unroll
+        for (int i = 0; i < 7; ++i) wc[i] = wpc[i] = 0;
+    }
+    const size_t tile_off = (size_t)row0 * R;
+    const uint32_t th = (uint32_t)c.g * R + c.t;
+    const size_t dig_limb = (size_t)a.ext * n, dig_item = NPARTS * dig_limb;
+    // wave-uniform bases: digit j of client cl at digs + cl * cnt * dig_item + j * dig_limb, conversion u at convs + u * nl * n
+    const u64 *digs = a.dig + (size_t)b * dig_item + (size_t)sl * n + tile_off;
+    const u64 *convs = a.conv + ((size_t)b * 2 * a.nl + sl) * n + tile_off;
+    u64 h0[2 * PAIRS], l0[2 * PAIRS], h1[2 * PAIRS], l1[2 * PAIRS], z[2 * PAIRS];
+#pragma unroll
+    for (int i = 0; i < 2 * PAIRS; ++i) h0[i] = l0[i] = h1[i] = l1[i] = z[i] = 0;
+    auto reduce = [&](u64 hi, u64 lo) -> u64 {
+        if (AR == AR_PM) return pm_reduce128_wide(hi, lo, pm_consts(lc), lc.q);
+        return reduce_wide(hi, lo, lc);
+    };
+    u64 x[8];
+    {
+        const u64 *src = digs + j0 * dig_limb;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) x[k] = ld_stream(src + th + TPR * k);
+    }
+    __syncthreads();  // twiddles staged
+    uint32_t in_run = 0, cl = 0;
+    // a group has at least one client and a context of this kernel at least one converted digit: both loops test at the
+    // bottom, so no value of the limb (the pseudo-Mersenne constants live in scalar registers) meets a skipped-loop path
+#pragma unroll 1
+    do {
+        const u64 *ct = a.cts + (size_t)cl * a.ct_cstride + (size_t)b * a.ct_stride + (size_t)sl * n + tile_off;
+        const u64 *ek = a.evk + (size_t)cl * a.evk_cstride + (size_t)sl * n + tile_off;
+        {   // the digit that owns this limb: c1 itself; c0 joins its sum
+            const u64 *y1 = ct + (size_t)a.nl * n;
+            const u64 *e0 = ek + ((size_t)own * 2 + 0) * a.D * n, *e1 = ek + ((size_t)own * 2 + 1) * a.D * n;
+            const u64 *w = W ? a.wt + ((size_t)cl * a.D + sl) * 4 : nullptr;
+            const u64 w0 = W ? w[0] : 0, w1 = W ? w[1] : 0;
+#pragma unroll
+            for (int i = 0; i < PAIRS; ++i) {
+                const int e = row3_pair<LOGC>(c.g, c.t, i);
+                const ulong2 yy = ld_stream2(reinterpret_cast<const ulong2 *>(y1) + e);
+                const ulong2 zz = ld_stream2(reinterpret_cast<const ulong2 *>(ct) + e);
+                const ulong2 bb = reinterpret_cast<const ulong2 *>(e0)[e];
+                const ulong2 cc = reinterpret_cast<const ulong2 *>(e1)[e];
+                mac128(h0[2 * i], l0[2 * i], yy.x, bb.x);
+                mac128(h0[2 * i + 1], l0[2 * i + 1], yy.y, bb.y);
+                mac128(h1[2 * i], l1[2 * i], yy.x, cc.x);
+                mac128(h1[2 * i + 1], l1[2 * i + 1], yy.y, cc.y);
+                z[2 * i] += W ? shoup_mul(zz.x, w0, w1, lc.q) : zz.x;
+                z[2 * i + 1] += W ? shoup_mul(zz.y, w0, w1, lc.q) : zz.y;
+            }
+            if ((cl & 7) == 7) {
+#pragma unroll
+                for (int i = 0; i < 2 * PAIRS; ++i) z[i] = reduce_word(z[i], lc);
+            }
+        }
+        int jn = j0, np = NPARTS;
+        if (NPARTS == 2) asm volatile("" : "+s"(np));  // two digits: keep this a loop, as in k_qsum3_fp
+        int dj = jn;
+#pragma unroll 1
+        do {
+            jn = dj + 1 == own ? dj + 2 : dj + 1;
+            wave_lds_sync();  // previous transform's consumers finished reading this wave's row
+            row3_forward<AR, LOGC, PARK>(x, c, wc, wpc, lc);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) lds[TL::at(c.g, 8 * c.t + k)] = AR == AR_PM ? x[k] : canon8(x[k], lc.q, lc.q2);
+            {   // the next digit, the next client's first digit, or the first summed conversion
+                const u64 *src = jn < NPARTS ? digs + jn * dig_limb
+                                             : (cl + 1 < a.n_clients ? digs + (size_t)a.cnt * dig_item + j0 * dig_limb : convs);
+#pragma unroll
+                for (int k = 0; k < 8; ++k) x[k] = ld_stream(src + th + TPR * k);
+            }
+            wave_lds_sync();
+            const u64 *e0 = ek + ((size_t)dj * 2 + 0) * a.D * n, *e1 = ek + ((size_t)dj * 2 + 1) * a.D * n;
+            ulong2 eb[PAIRS], ec[PAIRS];  // the digit's eval-key tiles in one burst (see k_qsum3_fp)
+#pragma unroll
+            for (int i = 0; i < PAIRS; ++i) {
+                const int e = row3_pair<LOGC>(c.g, c.t, i);
+                eb[i] = reinterpret_cast<const ulong2 *>(e0)[e];
+                ec[i] = reinterpret_cast<const ulong2 *>(e1)[e];
+            }
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int i = 0; i < PAIRS; ++i) {
+                const int xx = (2 * row3_pair<LOGC>(c.g, c.t, i)) % R;
+                const u64 yx = lds[TL::at(c.g, xx)], yz = lds[TL::at(c.g, xx + 1)];
+                mac128(h0[2 * i], l0[2 * i], yx, eb[i].x);
+                mac128(h0[2 * i + 1], l0[2 * i + 1], yz, eb[i].y);
+                mac128(h1[2 * i], l1[2 * i], yx, ec[i].x);
+                mac128(h1[2 * i + 1], l1[2 * i + 1], yz, ec[i].y);
+            }
+            dj = jn;
+        } while (dj < np);
+        if (++in_run == RUN) {  // the run is full: its canonical value opens the next one
+            in_run = 0;
+#pragma unroll
+            for (int i = 0; i < 2 * PAIRS; ++i) {
+                l0[i] = reduce(h0[i], l0[i]);
+                l1[i] = reduce(h1[i], l1[i]);
+                h0[i] = h1[i] = 0;
+            }
+        }
+        digs += (size_t)a.cnt * dig_item;
+    } while (++cl < a.n_clients);
+#pragma unroll
+    for (int i = 0; i < 2 * PAIRS; ++i) {  // the last run (a value already canonical stays what it is)
+        l0[i] = reduce(h0[i], l0[i]);
+        l1[i] = reduce(h1[i], l1[i]);
+        z[i] = reduce_word(z[i], lc);
+    }
+    const u64 pi = a.pinv[sl], pi_sh = a.pinv_sh[sl];
+    u64 *o0 = a.out + (size_t)b * a.out_stride + (size_t)sl * n + tile_off;
+#pragma unroll 1
+    for (int comp = 0; comp < 2; ++comp) {  // the summed ModDown conversions, tail and store
+        wave_lds_sync();
+        row3_forward<AR, LOGC, PARK>(x, c, wc, wpc, lc);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) lds[TL::at(c.g, 8 * c.t + k)] = canon8(x[k], lc.q, lc.q2);
+        if (comp == 0) {
+            const u64 *src = convs + (size_t)a.nl * n;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) x[k] = ld_stream(src + th + TPR * k);
+        }
+        wave_lds_sync();
+        u64 *dst = o0 + (size_t)comp * a.nl * n;
+#pragma unroll
+        for (int i = 0; i < PAIRS; ++i) {
+            const int e = row3_pair<LOGC>(c.g, c.t, i);
+            const int xx = (2 * e) % R;
+            const u64 tx = comp ? l1[2 * i] : l0[2 * i], ty = comp ? l1[2 * i + 1] : l0[2 * i + 1];
+            ulong2 v;
+            v.x = shoup_mul(sub_mod(tx, lds[TL::at(c.g, xx)], lc.q), pi, pi_sh, lc.q);
+            v.y = shoup_mul(sub_mod(ty, lds[TL::at(c.g, xx + 1)], lc.q), pi, pi_sh, lc.q);
+            if (comp == 0) {
+                v.x = add_mod(v.x, z[2 * i], lc.q);
+                v.y = add_mod(v.y, z[2 * i + 1], lc.q);
+            }
+            if (a.init_from_out) {
+                const ulong2 o = reinterpret_cast<const ulong2 *>(dst)[e];
+                v.x = add_mod(v.x, o.x, lc.q);
+                v.y = add_mod(v.y, o.y, lc.q);
+            }
+            reinterpret_cast<ulong2 *>(dst)[e] = v;
+        }
+    }
 }
 
 }  // namespace mk

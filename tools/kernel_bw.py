@@ -54,6 +54,8 @@ def alg_limbs(name):
         return 2 * K * items, (nfp if fp else 1) * polys2
     if k == "k_row3_tail_once":
         return polys2 + 2 * items + items, polys2
+    if k == "k_qsum3_int":                                          # q_0 in one kernel: digits, c1, c0, eval keys, conversions
+        return (BETA - 1) * items + 2 * items + BETA * 2 * C + polys2, polys2
     if k == "k_qsum3_fp" or k == "k_qsum_fp":
         return nfp * ((BETA - 1) * items + 2 * items + BETA * 2 * C + polys2), nfp * polys2
     return None
