@@ -150,6 +150,34 @@ int mkckks_rescale_mult_const_batch(mkckks_ctx *c, const uint64_t *d_in, uint64_
 int mkckks_rescale_batch(mkckks_ctx *c, const uint64_t *d_in, uint64_t *d_out, uint32_t n_ct, uint32_t nl);
 int mkckks_mult_const_batch(mkckks_ctx *c, uint64_t *d_ct, uint32_t n_ct, uint32_t nl, double operand);
 
+/* ---- cc->EvalMult(ct, plaintext): per-slot aggregation weights ------------------------------------------------------
+ * The reference scales its aggregate by one constant (aggregateEncryptedWeights.cpp:82-83: EvalMult(ct_sum, 0.5)); the
+ * same call with an encoded plaintext in place of the constant scales every slot by a factor of its own (the divisor
+ * 1 / count_j of a round in which clients cover different coordinates, a per-layer rate, a 0/1 mask).
+ * d_pt is u64[n_pt][nl][N]: EVALUATION format, canonical residues, as mkckks_encode_batch writes them.  n_pt is n_ct
+ * (plaintext b for ciphertext b) or 1 (one plaintext for all); anything else is MKCKKS_E_INVALID, as are null pointers
+ * and nl outside [1, L] ([2, L] for the rescaling call).  A zero n_ct is a no-op; host-only context -> MKCKKS_E_NODEVICE.
+ * Order: multiply first, ONE rescale last, as in the weighted aggregation below -- the rescale's rounding error is not
+ * multiplied by the 2^p-sized plaintext as it is in OpenFHE's rescale-then-EvalMult.
+ * Scale: for a noiseScaleDeg-2 input at level = L - nl encode the factors at sf(level + 1) and call
+ * mkckks_mult_plain_rescale_batch -- the result has the limbs, level, scale (S_in / q_{nl-1} * sf(level + 1)) and
+ * noiseScaleDeg (2) of mkckks_rescale_mult_const_batch(ct, .); for a noiseScaleDeg-1 input encode at sf(level) and call
+ * mkckks_mult_plain_batch alone (the bookkeeping of mkckks_mult_const_batch).
+ * Headroom: before the rescale the encrypted coefficients are about S_in * sf * max|factor| * |values|, so
+ * log2(S_in * sf * max|factor|) must stay below log2(q_0 ... q_{nl-1}) - 1.  The library cannot check it.
+ *
+ * (aggregateEncryptedWeights.cpp:82-83) EvalMult(ct, pt) core, in place, no rescale:
+ * d_ct[b][k][i][.] = d_ct[b][k][i][.] * d_pt[b % n_pt][i][.] mod q_i   (k = 0, 1; i < nl). */
+int mkckks_mult_plain_batch(mkckks_ctx *c, uint64_t *d_ct, const uint64_t *d_pt, uint32_t n_ct, uint32_t n_pt, uint32_t nl);
+/* (aggregateEncryptedWeights.cpp:82-83) Rescale of that product: d_in u64[n_ct][2][nl][N] -> d_out u64[n_ct][2][nl-1][N].
+ * DEFINED bit for bit as the pointwise product of the canonical residues mod q_i on both components followed by
+ * mkckks_rescale_batch (DropLastElementAndScale); where the rescale runs on the fused kernels the product is formed
+ * inside its two row passes and never reaches memory (MKCKKS_PLAIN_FUSED=0 forces the composition, =1 the fused form
+ * wherever it exists).  d_in is not modified.  As with mkckks_rescale_batch the output's polynomials are nl-1 limbs
+ * apart and the input's nl, so the two cannot share memory: d_out overlapping d_in is MKCKKS_E_INVALID here. */
+int mkckks_mult_plain_rescale_batch(mkckks_ctx *c, const uint64_t *d_in, const uint64_t *d_pt, uint64_t *d_out, uint32_t n_ct,
+                                    uint32_t n_pt, uint32_t nl);
+
 /* ---- cc->ReEncrypt(ct, reKey)  (changeCipherDomain.cpp:74,89,105) --------
  * INDCPA proxy re-encryption (the HRA-secure form: mkckks_rerandomize_batch first) = hybrid key switch of c1 with the
  * eval key:

@@ -70,6 +70,8 @@ SYMBOLS = {
     "mkckks_rescale_mult_const_batch": (_int, [_vp, _vp, _vp, _u32, _u32, _dbl]),
     "mkckks_rescale_batch": (_int, [_vp, _vp, _vp, _u32, _u32]),
     "mkckks_mult_const_batch": (_int, [_vp, _vp, _u32, _u32, _dbl]),
+    "mkckks_mult_plain_batch": (_int, [_vp, _vp, _vp, _u32, _u32, _u32]),
+    "mkckks_mult_plain_rescale_batch": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u32]),
     "mkckks_reencrypt_batch": (_int, [_vp, _vp, _vp, _vp, _u32, _u32]),
     "mkckks_reencrypt_accumulate_batch": (_int, [_vp, _vp, _vp, _vp, _u32, _u32]),
     "mkckks_reencrypt_sum_batch": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u32]),
@@ -398,6 +400,14 @@ class Context:
 
     def mult_const(self, ct, n_ct, nl, operand):
         self._check(self._L.mkckks_mult_const_batch(self._h, _ptr(ct), n_ct, nl, float(operand)))
+
+    def mult_plain(self, ct, pt, n_ct, n_pt, nl):
+        """EvalMult(ct, plaintext) core in place: ct[b] *= pt[b % n_pt]; pt as encode() writes it, n_pt is n_ct or 1."""
+        self._check(self._L.mkckks_mult_plain_batch(self._h, _ptr(ct), _ptr(pt), n_ct, n_pt, nl))
+
+    def mult_plain_rescale(self, inp, pt, out, n_ct, n_pt, nl):
+        """out[n_ct][2][nl-1][N] = Rescale(inp * pt); inp is not modified and must not overlap out."""
+        self._check(self._L.mkckks_mult_plain_rescale_batch(self._h, _ptr(inp), _ptr(pt), _ptr(out), n_ct, n_pt, nl))
 
     def reduce_mod(self, ct, n_ct, nl, n_terms):
         self._check(self._L.mkckks_reduce_mod_batch(self._h, _ptr(ct), n_ct, nl, n_terms))

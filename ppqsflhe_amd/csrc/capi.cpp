@@ -293,6 +293,23 @@ int mkckks_mult_const_batch(mkckks_ctx *c, uint64_t *ct, uint32_t n_ct, uint32_t
         c->eng->mult_const(ct, n_ct, nl, ps.const_factors(nl, ps.L - nl, operand));
     });
 }
+int mkckks_mult_plain_batch(mkckks_ctx *c, uint64_t *ct, const uint64_t *pt, uint32_t n_ct, uint32_t n_pt, uint32_t nl) {
+    return guarded([&] {
+        need(c && ct && pt, "null argument");
+        need(nl >= 1 && nl <= c->eng->params().L, "nl out of range");
+        need(n_pt == 1 || n_pt == n_ct, "n_pt must be 1 or n_ct");
+        c->eng->mult_plain(ct, pt, n_ct, n_pt, nl);
+    });
+}
+int mkckks_mult_plain_rescale_batch(mkckks_ctx *c, const uint64_t *in, const uint64_t *pt, uint64_t *out, uint32_t n_ct,
+                                    uint32_t n_pt, uint32_t nl) {
+    return guarded([&] {
+        need(c && in && pt && out, "null argument");
+        need(nl >= 2 && nl <= c->eng->params().L, "nl out of range");
+        need(n_pt == 1 || n_pt == n_ct, "n_pt must be 1 or n_ct");
+        c->eng->mult_plain_rescale(in, pt, out, n_ct, n_pt, nl);
+    });
+}
 
 int mkckks_reencrypt_batch(mkckks_ctx *c, const uint64_t *ct, const uint64_t *evk, uint64_t *out, uint32_t n_ct,
                            uint32_t nl) {

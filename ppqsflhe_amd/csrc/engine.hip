@@ -5,6 +5,7 @@
 //   changeCipherDomain.cpp:74,89,105        cc->ReEncrypt       -> Engine::reencrypt
 //   aggregateEncryptedWeights.cpp:82,91,106 cc->EvalAdd         -> Engine::eval_add / eval_sum
 //   aggregateEncryptedWeights.cpp:83,92,107 cc->EvalMult(.,0.5) -> Engine::rescale (+ factors)
+//   aggregateEncryptedWeights.cpp:82-83     cc->EvalMult(.,pt)  -> Engine::mult_plain / mult_plain_rescale (per-slot weights)
 //   encryptModelWeights.cpp:83,91,110       cc->Encrypt         -> Engine::encrypt (+ lift_ntt)
 //   decryptModelWeights.cpp:81,90,108       cc->Decrypt         -> Engine::decrypt
 //   keyGen.cpp:33 / REkeyGen.cpp:52         KeyGen / ReKeyGen   -> Engine::keygen / rekeygen
@@ -283,6 +284,21 @@ __global__ void k_mul_const(u64 *ct, EwGeom g, const LimbConst *limb, uint32_t s
     v.x = shoup_mul(v.x, f[l], f_sh[l], q);
     v.y = shoup_mul(v.y, f[l], f_sh[l], q);
     st2(ct + off, v);
+}
+
+// out[item][k][l] = in[item][k][l] * pt[item % n_pt][l]   (EvalMult(ct, plaintext) core: the pointwise product of
+// canonical residues, mul_mod in every arithmetic class; out may be in)
+__global__ void k_mul_plain(const u64 *in, const u64 *pt, u64 *out, EwGeom g, const LimbConst *limb, uint32_t slots,
+                            uint32_t n_pt) {
+    EW_PROLOGUE(slots)
+    const uint32_t l = slot % g.nl;
+    const LimbConst lc = limb[limb_id_of(l, g.nl, g.L)];
+    const size_t off = ((size_t)item * slots + slot) * g.n + idx;
+    const ulong2 m = ld2(pt + ((size_t)(item % n_pt) * g.nl + l) * g.n + idx);
+    ulong2 v = ld2(in + off);
+    v.x = mul_mod(v.x, m.x, lc);
+    v.y = mul_mod(v.y, m.y, lc);
+    st2(out + off, v);
 }
 
 // NativeVectorT::SwitchModulus of the dropped limb (COEFFICIENT format) into limb `slot`:
@@ -595,6 +611,10 @@ Knobs Knobs::from_env() {
     if (const char *e = std::getenv("MKCKKS_Q0_WALK")) {
         if (!std::strcmp(e, "0")) k.q0_walk = 0;
         else if (!std::strcmp(e, "1")) k.q0_walk = 1;
+    }
+    if (const char *e = std::getenv("MKCKKS_PLAIN_FUSED")) {
+        if (!std::strcmp(e, "0")) k.plain_fused = 0;
+        else if (!std::strcmp(e, "1")) k.plain_fused = 1;
     }
     return k;
 }
@@ -1343,6 +1363,102 @@ void Engine::compress(const u64 *in, u64 *out, uint32_t n_ct, uint32_t nl_in, ui
     const size_t w_last = (size_t)items * n, w_tmp = (size_t)items * nl_out * n;
     u64 *ws = workspace(w_last + w_tmp);
     rescale_core(in, nl_in, out, items, nl, d_c, ws, ws + w_last, 0, 0);
+}
+
+// ---- EvalMult(ct, plaintext): per-slot aggregation weights ------------------------------
+
+static void check_plain_counts(uint32_t n_ct, uint32_t n_pt) {
+    if (n_pt != 1 && n_pt != n_ct) throw std::invalid_argument("n_pt must be 1 or n_ct");
+}
+
+void Engine::mult_plain(u64 *ct, const u64 *pt, uint32_t n_ct, uint32_t n_pt, uint32_t nl) {
+    need_device();
+    check_nl(nl);
+    check_plain_counts(n_ct, n_pt);
+    if (!n_ct) return;
+    EwGeom g{ps_.n, nl, ps_.L};
+    k_mul_plain<<<ew_grid(ps_.n, 2 * nl, n_ct), EW_THREADS, 0, stream_>>>(ct, pt, ct, g, d_limb_, 2 * nl, n_pt);
+    MK_HIP(hipGetLastError());
+}
+
+// the two row kernels of the fused form, in the arithmetic class of their limbs
+static void launch_ptmul_irow(const PtmulArgs &a, const NttTables &T, uint32_t polys, hipStream_t s) {
+    const uint32_t r1 = 1u << T.log_r1;
+    ClassMasks m;  // the dropped limb alone
+    (T.h_fp_of[a.nl - 1] ? m.fp : m.integer) = 1ull;
+    if (!dispatch<2, 3, 4, 9>(fast_row(T.log_r2, r1), [&](auto row_h) {
+            constexpr int ROW_H = decltype(row_h)::value;
+            for_each_class(T, m, [&](auto ar, unsigned long long, uint32_t) {
+                if constexpr (ROW_H == 9)
+                    k_ptmul_irow3<decltype(ar)::value><<<dim3((r1 / 4) * polys), NTT_THREADS, 0, s>>>(a, T);
+                else
+                    k_ptmul_irow<ROW_H, decltype(ar)::value><<<dim3(row_tiles<ROW_H>(T) * polys), NTT_THREADS, 0, s>>>(a, T);
+            });
+        }))
+        throw std::logic_error("fused plaintext product: no row kernel for this row length");
+}
+static void launch_ptresc_row(const PtmulArgs &a0, const NttTables &T, uint32_t polys, hipStream_t s) {
+    const uint32_t r1 = 1u << T.log_r1;
+    if (!dispatch<2, 3, 4, 9>(fast_row(T.log_r2, r1), [&](auto row_h) {
+            constexpr int ROW_H = decltype(row_h)::value;
+            for_each_class(T, limb_classes(a0.nl - 1, T), [&](auto ar, unsigned long long mask, uint32_t nsel) {
+                PtmulArgs a = a0;
+                a.slot_mask = mask;
+                a.nsel = nsel;
+                if constexpr (ROW_H == 9)
+                    k_ptresc_row3<decltype(ar)::value><<<dim3((r1 / 4) * polys * nsel), NTT_THREADS, 0, s>>>(a, T);
+                else
+                    k_ptresc_row<ROW_H, decltype(ar)::value>
+                        <<<dim3(row_tiles<ROW_H>(T) * polys * nsel), NTT_THREADS, 0, s>>>(a, T);
+            });
+        }))
+        throw std::logic_error("fused plaintext product: no row kernel for this row length");
+}
+
+// DropLastElementAndScale(in * pt).  Fused (the ring sizes whose plain rescale is fused): the product of the dropped limb
+// inside its inverse row pass, the products of the remaining limbs inside the forward row pass of the switched limb;
+// otherwise, and under MKCKKS_PLAIN_FUSED=0, the composition k_mul_plain into a workspace + rescale_core, chunk by chunk.
+void Engine::mult_plain_rescale(const u64 *in, const u64 *pt, u64 *out, uint32_t n_ct, uint32_t n_pt, uint32_t nl) {
+    need_device();
+    check_nl(nl);
+    if (nl < 2) throw std::invalid_argument("rescale needs at least 2 limbs");
+    check_plain_counts(n_ct, n_pt);
+    if (!n_ct) return;
+    const uint32_t n = ps_.n, last = nl - 1;
+    if (ranges_overlap(in, (size_t)n_ct * 2 * nl * n * sizeof(u64), out, (size_t)n_ct * 2 * last * n * sizeof(u64)))
+        throw std::invalid_argument("mult_plain_rescale cannot write over its input");
+    const u64 *d_c = rescale_consts(nl, nullptr);
+    const int col_h = fast_log_h(tabs_.log_r1, 1u << tabs_.log_r2);
+    const bool fused = col_h >= 2 && row_tail_supported(tabs_) && knobs_.plain_fused != 0;
+    if (fused) {
+        const uint32_t items = 2 * n_ct;
+        const size_t w_last = (size_t)items * n;
+        u64 *d_last = workspace(w_last + (size_t)items * last * n), *d_tmp = d_last + w_last;
+        PtmulArgs a{in, pt, d_tmp, d_last, d_c, d_c + last, nl, n_pt == 1 ? 1u : 0u, 0, 0};
+        launch_ptmul_irow(a, tabs_, items, stream_);
+        NttIo col{d_last, d_last, (size_t)n, (size_t)n, 0, 0, last, 1, nl};
+        launch_col<true>(col, tabs_, items, nullptr, nullptr, stream_);
+        if (!dispatch<2, 3, 4>(col_h, [&](auto log_h) {
+                launch_switch_col<decltype(log_h)::value>(d_last, d_tmp, tabs_, last, items, ps_.moduli[last], stream_);
+            }))
+            throw std::logic_error("fused rescale: no switch kernel for this column radix");
+        a.out = out;
+        launch_ptresc_row(a, tabs_, items, stream_);
+        MK_HIP(hipGetLastError());
+        return;
+    }
+    const uint32_t chunk = n_ct < knobs_.chunk ? n_ct : knobs_.chunk;
+    const size_t w_prod = (size_t)chunk * 2 * nl * n, w_last = (size_t)chunk * 2 * n;
+    u64 *prod = workspace(w_prod + w_last + (size_t)chunk * 2 * last * n);
+    EwGeom g{n, nl, ps_.L};
+    for (uint32_t b0 = 0; b0 < n_ct; b0 += chunk) {
+        const uint32_t cnt = n_ct - b0 < chunk ? n_ct - b0 : chunk;
+        const u64 *ptb = n_pt == 1 ? pt : pt + (size_t)b0 * nl * n;
+        k_mul_plain<<<ew_grid(n, 2 * nl, cnt), EW_THREADS, 0, stream_>>>(in + (size_t)b0 * 2 * nl * n, ptb, prod, g, d_limb_, 2 * nl,
+                                                                        n_pt == 1 ? 1u : cnt);
+        MK_HIP(hipGetLastError());
+        rescale_core(prod, nl, out + (size_t)b0 * 2 * last * n, 2 * cnt, nl, d_c, prod + w_prod, prod + w_prod + w_last, 0, 0);
+    }
 }
 
 // ---- hybrid key switching -----------------------------------------------------------

@@ -66,6 +66,9 @@ struct Knobs {
     bool no_fp64 = false;        // MKCKKS_NO_FP64=1: integer arithmetic on every limb
     int q0_walk = 2;             // MKCKKS_Q0_WALK=0/1/auto: the integer-class Q limbs of the merged n-client flow as two kernels
                                  // (k_row3_inner_int + k_row3_tail_once), as one (k_qsum3_int), or chosen per call by grid size
+    int plain_fused = 2;         // MKCKKS_PLAIN_FUSED=0/1: mult_plain_rescale as the composition (k_mul_plain + rescale) or fused
+                                 // into the rescale's two row passes; default: fused wherever the plain rescale is
+                                 // (profiles/slot_weights_ab.txt)
     static Knobs from_env();
 };
 
@@ -119,6 +122,11 @@ public:
     void eval_sum(const u64 *in, u64 *out, uint32_t n_clients, uint32_t n_ct, uint32_t nl);
     void rescale(const u64 *in, u64 *out, uint32_t n_ct, uint32_t nl, const std::vector<u64> *factors);
     void mult_const(u64 *ct, uint32_t n_ct, uint32_t nl, const std::vector<u64> &factors);
+    // EvalMult(ct, plaintext): pt u64[n_pt][nl][N] EVALUATION, canonical (encode's output); n_pt == n_ct or 1 (shared)
+    //   mult_plain:         ct[b][k][i] *= pt[b % n_pt][i] in place
+    //   mult_plain_rescale: out u64[n_ct][2][nl-1][N] = Rescale(in * pt); in is not modified, out must not overlap it
+    void mult_plain(u64 *ct, const u64 *pt, uint32_t n_ct, uint32_t n_pt, uint32_t nl);
+    void mult_plain_rescale(const u64 *in, const u64 *pt, u64 *out, uint32_t n_ct, uint32_t n_pt, uint32_t nl);
     void reduce_mod(u64 *ct, uint32_t n_ct, uint32_t nl, uint32_t n_terms);
     // RCCL exchange of the per-GPU partial sums: shard[b] = (sum over ranks of partial_r[rank * n_ct_shard + b]) mod q,
     // partial u64[n_ranks * n_ct_shard][2][nl][N] on every rank, shard u64[n_ct_shard][2][nl][N] (comm: ncclComm_t)

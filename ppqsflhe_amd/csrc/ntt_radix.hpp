@@ -2636,4 +2636,279 @@ __global__ __launch_bounds__(NTT_THREADS, 4) void k_pdec_col(PdecArgs a, NttTabl
     }
 }
 
+// =====================================================================================
+// Per-slot aggregation weights (mkckks_mult_plain_rescale_batch; Engine::mult_plain_rescale):
+//   out = DropLastElementAndScale(ct * pt)   with pt an encoded plaintext, EVALUATION format, canonical residues.
+// The product of the dropped limb is formed in the copy-in of its inverse row pass (as k_pdec_row forms c1 * s); the
+// products of the remaining limbs are formed in the copy-out of the switched limb's forward row pass, in front of the
+// subtraction of the rescale's tail.  The inverse column pass and k_switch_col run between the two as they do in a plain
+// rescale: the product ciphertext never exists in HBM.
+// =====================================================================================
+
+struct PtmulArgs {
+    const u64 *in;        // [polys][nl][N]: polynomial p = 2 b + k is component k of ciphertext b; read-only
+    const u64 *pt;        // [n_pt][nl][N]
+    const u64 *tmp;       // k_ptresc_row: [polys][nl-1][N] switched limb, column-passed (doubles on an fp limb)
+    u64 *out;             // k_ptmul_irow: [polys][N] (lazy, doubles on an fp limb); k_ptresc_row: [polys][nl-1][N]
+    const u64 *c, *c_sh;  // k_ptresc_row: [nl-1] q_last^-1 mod q_i and its Shoup companion
+    uint32_t nl;
+    uint32_t pt_shared;   // 1: one plaintext for every ciphertext (n_pt == 1), 0: plaintext b for ciphertext b
+    unsigned long long slot_mask;  // k_ptresc_row: remaining Q limbs (slot == limb id) of this instance's arithmetic class
+    uint32_t nsel;
+};
+MK_D size_t ptmul_pt_offset(const PtmulArgs &a, uint32_t poly, uint32_t n) {
+    return a.pt_shared ? 0 : (size_t)(poly >> 1) * a.nl * n;
+}
+
+// Inverse row pass of the dropped limb nl-1 (the INV branch of k_ntt_row_r) whose copy-in computes ct * pt: products as
+// k_pdec_row (mul_mod on canonical words, every arithmetic class).  Grid order of k_ntt_row_r: the polynomials of one
+// tile are neighbours in one XCD's queue, so the two components of a ciphertext (with one shared plaintext: all
+// ciphertexts) fetch the plaintext tile and the twiddle tile once and then hit in L2.
+template <int LOG_H, int AR>
+__global__ __launch_bounds__(NTT_THREADS) void k_ptmul_irow(PtmulArgs a, NttTables T) {
+    using TL = RowTile<LOG_H>;
+    using TA = RowTwA<LOG_H>;
+    constexpr int H = TL::H, S = TL::S, R = TL::R, PAIRS = S * R / 2 / NTT_THREADS;
+    __shared__ u64 lds[TL::WORDS + 2 * TA::WORDS];
+    u64 *twa = lds + TL::WORDS, *twa_sh = twa + TA::WORDS;
+    const uint32_t n = 1u << T.log_n, r1 = 1u << T.log_r1;
+    const uint32_t tiles = r1 / S, polys = gridDim.x / tiles;
+    uint32_t grp, poly;
+    group_member(blockIdx.x, tiles, polys, T.cu_affine, grp, poly);
+    const uint32_t sl = a.nl - 1;  // Q limb: slot == limb id
+    const LimbConst lc = T.limb[sl];
+    if ((lc.fp != 0) != (AR == AR_FP)) return;  // never: the host launches the instance of this limb's class
+    const uint32_t row0 = grp * S;
+    const int g = threadIdx.x / H, j = threadIdx.x % H;
+    const size_t tile = (size_t)sl * n + (size_t)row0 * R;
+    const ulong2 *ci = reinterpret_cast<const ulong2 *>(a.in + (size_t)poly * a.nl * n + tile);
+    const ulong2 *pt = reinterpret_cast<const ulong2 *>(a.pt + ptmul_pt_offset(a, poly, n) + tile);
+    u64 *dst = a.out + (size_t)poly * n + (size_t)row0 * R;
+    u64 x[H], w[H - 1], wp[H - 1];
+    load_rowb_twiddles<LOG_H>(T.itwb + (size_t)sl * 2 * n, row0 + g, j, w, wp);  // first: in flight while the tile is staged
+    for (int i = 0; i < PAIRS; ++i) {
+        const int e = wave_pair<LOG_H>(i);
+        const int gg = (2 * e) / R, xx = (2 * e) % R;
+        const ulong2 c = ld_pass2(ci + e), m = pt[e];
+        lds[TL::at(gg, xx)] = mul_mod(c.x, m.x, lc);
+        lds[TL::at(gg, xx + 1)] = mul_mod(c.y, m.y, lc);
+    }
+    stage_twiddles_wave<LOG_H>(twa, twa_sh, T.itw + (size_t)sl * n, T.itw_sh + (size_t)sl * n, r1 + row0);
+    wave_lds_sync();
+#pragma unroll
+    for (int k = 0; k < H; ++k) x[k] = lds[TL::at(g, H * j + k)];
+    if (AR == AR_FP) {  // canonical input -> doubles
+#pragma unroll
+        for (int k = 0; k < H; ++k) x[k] = dbits((double)x[k]);
+    }
+    radix_inverse_any<LOG_H, AR>(x, w, wp, lc);
+#pragma unroll
+    for (int k = 0; k < H; ++k) lds[TL::at(g, H * j + k)] = x[k];
+    wave_lds_sync();
+#pragma unroll
+    for (int k = 0; k < H; ++k) x[k] = lds[TL::at(g, j + H * k)];
+    TA::fetch(twa, twa_sh, g, w, wp);
+    radix_inverse_any<LOG_H, AR>(x, w, wp, lc);
+#pragma unroll
+    for (int k = 0; k < H; ++k) st_pass(dst + (size_t)g * R + j + H * k, x[k]);  // lazy (doubles on an fp limb): the column pass scales
+}
+
+// Forward row pass of the switched limb (the forward branch of k_ntt_row_r with its tail) whose copy-out loads the tiles
+// of ct and pt and writes (ct * pt - tmp) * q_last^-1.  Grid order of k_ntt_row_r, for the plaintext tile's sake.
+template <int LOG_H, int AR>
+__global__ __launch_bounds__(NTT_THREADS) void k_ptresc_row(PtmulArgs a, NttTables T) {
+    using TL = RowTile<LOG_H>;
+    using TA = RowTwA<LOG_H>;
+    constexpr int H = TL::H, S = TL::S, R = TL::R, PAIRS = S * R / 2 / NTT_THREADS;
+    __shared__ u64 lds[TL::WORDS + 2 * TA::WORDS];
+    u64 *twa = lds + TL::WORDS, *twa_sh = twa + TA::WORDS;
+    const uint32_t n = 1u << T.log_n, r1 = 1u << T.log_r1, last = a.nl - 1;
+    const uint32_t tiles = r1 / S, groups = tiles * a.nsel, polys = gridDim.x / groups;
+    uint32_t grp, poly;
+    group_member(blockIdx.x, groups, polys, T.cu_affine, grp, poly);
+    const uint32_t sl = nth_set_bit(a.slot_mask, grp / tiles);  // remaining Q limb: slot == limb id
+    const LimbConst lc = T.limb[sl];
+    if ((lc.fp != 0) != (AR == AR_FP)) return;  // block-uniform
+    const uint32_t row0 = (grp % tiles) * S;
+    const int g = threadIdx.x / H, j = threadIdx.x % H;
+    const size_t tile = (size_t)sl * n + (size_t)row0 * R;
+    const u64 *src = a.tmp + (size_t)poly * last * n + tile;
+    const u64 *tw = T.tw + (size_t)sl * n, *tw_sh = T.tw_sh + (size_t)sl * n;
+    u64 x[H], w[H - 1], wp[H - 1];
+#pragma unroll
+    for (int k = 0; k < H; ++k) x[k] = ld_pass(src + (size_t)g * R + j + H * k);
+    stage_twiddles_wave<LOG_H>(twa, twa_sh, tw, tw_sh, r1 + row0);
+    wave_lds_sync();
+    TA::fetch(twa, twa_sh, g, w, wp);
+    radix_forward_any<LOG_H, AR>(x, w, wp, lc);
+    u64 w2[H - 1], wp2[H - 1];  // round-B twiddles: requested before the exchange, used after it
+    load_rowb_twiddles<LOG_H>(T.twb + (size_t)sl * 2 * n, row0 + g, j, w2, wp2);
+#pragma unroll
+    for (int k = 0; k < H; ++k) lds[TL::at(g, j + H * k)] = x[k];
+    wave_lds_sync();
+#pragma unroll
+    for (int k = 0; k < H; ++k) x[k] = lds[TL::at(g, H * j + k)];
+    radix_forward_any<LOG_H, AR>(x, w2, wp2, lc);
+#pragma unroll
+    for (int k = 0; k < H; ++k)  // canonical u64, own words only
+        lds[TL::at(g, H * j + k)] = (AR == AR_FP) ? fp_to_canonical(bitsd(x[k]), lc.qd, lc.qinv) : canon8(x[k], lc.q, lc.q2);
+    wave_lds_sync();
+    const u64 ci = a.c[sl], ci_sh = a.c_sh[sl];
+    const ulong2 *cq = reinterpret_cast<const ulong2 *>(a.in + (size_t)poly * a.nl * n + tile);
+    const ulong2 *pt = reinterpret_cast<const ulong2 *>(a.pt + ptmul_pt_offset(a, poly, n) + tile);
+    ulong2 *dst = reinterpret_cast<ulong2 *>(a.out + (size_t)poly * last * n + tile);
+    for (int i = 0; i < PAIRS; ++i) {
+        const int e = wave_pair<LOG_H>(i);
+        const int gg = (2 * e) / R, xx = (2 * e) % R;
+        const ulong2 t = ld_pass2(cq + e), m = pt[e];
+        ulong2 v;
+        v.x = shoup_mul(sub_mod(mul_mod(t.x, m.x, lc), lds[TL::at(gg, xx)], lc.q), ci, ci_sh, lc.q);
+        v.y = shoup_mul(sub_mod(mul_mod(t.y, m.y, lc), lds[TL::at(gg, xx + 1)], lc.q), ci, ci_sh, lc.q);
+        st_pass2(dst + e, v);
+    }
+}
+
+// The same two kernels on 512-point rows (the INV branch and the forward branch + tail of k_ntt_row3).
+template <int AR>
+__global__ __launch_bounds__(NTT_THREADS) void k_ptmul_irow3(PtmulArgs a, NttTables T) {
+    using TL = Row3;
+    constexpr int H = 8, LOG_H = 3, R = TL::R, S = TL::ROWS;
+    __shared__ u64 lds[TL::WORDS + 2 * (TL::TWA + TL::TWB)];
+    u64 *twa = lds + TL::WORDS, *twa_sh = twa + TL::TWA, *twb = twa_sh + TL::TWA, *twb_sh = twb + TL::TWB;
+    const uint32_t n = 1u << T.log_n, r1 = 1u << T.log_r1;
+    const uint32_t tiles = r1 / S, polys = gridDim.x / tiles;
+    uint32_t grp, poly;
+    group_member(blockIdx.x, tiles, polys, T.cu_affine, grp, poly);
+    const uint32_t sl = a.nl - 1;
+    const LimbConst lc = T.limb[sl];
+    if ((lc.fp != 0) != (AR == AR_FP)) return;
+    const uint32_t row0 = grp * S;
+    const int g = threadIdx.x / 64, t = threadIdx.x % 64, p = t / 8, r = t % 8;
+    const size_t tile = (size_t)sl * n + (size_t)row0 * R;
+    const ulong2 *ci = reinterpret_cast<const ulong2 *>(a.in + (size_t)poly * a.nl * n + tile);
+    const ulong2 *pt = reinterpret_cast<const ulong2 *>(a.pt + ptmul_pt_offset(a, poly, n) + tile);
+    u64 *dst = a.out + (size_t)poly * n + (size_t)row0 * R;
+    const u64 *tw = T.itw + (size_t)sl * n, *tw_sh = T.itw_sh + (size_t)sl * n;
+    const uint32_t base = r1 + row0 + g;
+    row3_stage_twiddles<3>(Row3Ctx{lds, twa, twa_sh, twb, twb_sh, g, t}, tw, tw_sh, r1 + row0);
+    u64 x[H], w[H - 1], wp[H - 1];
+    for (int e = threadIdx.x; e < S * R / 2; e += NTT_THREADS) {
+        const int gg = (2 * e) / R, xx = (2 * e) % R;
+        const ulong2 c = ci[e], m = pt[e];
+        lds[TL::at(gg, xx)] = mul_mod(c.x, m.x, lc);
+        lds[TL::at(gg, xx + 1)] = mul_mod(c.y, m.y, lc);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < H; ++k) x[k] = lds[TL::at(g, 64 * p + 8 * r + k)];
+    if (AR == AR_FP) {
+#pragma unroll
+        for (int k = 0; k < H; ++k) x[k] = dbits((double)x[k]);
+    }
+    load_round_twiddles<LOG_H>(tw, tw_sh, base * 64 + 8 * p + r, w, wp);
+    radix_inverse_any<LOG_H, AR>(x, w, wp, lc);
+#pragma unroll
+    for (int k = 0; k < H; ++k) lds[TL::at(g, 64 * p + 8 * r + k)] = x[k];
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < H; ++k) x[k] = lds[TL::at(g, 64 * p + 8 * k + r)];
+#pragma unroll
+    for (int s = 0; s < LOG_H; ++s)
+#pragma unroll
+        for (int gg = 0; gg < (1 << s); ++gg) {
+            const int e = S * 8 * ((1 << s) - 1) + ((g * 8 + p) << s) + gg;
+            w[(1 << s) - 1 + gg] = twb[e];
+            wp[(1 << s) - 1 + gg] = twb_sh[e];
+        }
+    radix_inverse_any<LOG_H, AR>(x, w, wp, lc);
+#pragma unroll
+    for (int k = 0; k < H; ++k) lds[TL::at(g, 64 * p + 8 * k + r)] = x[k];
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < H; ++k) x[k] = lds[TL::at(g, t + 64 * k)];
+#pragma unroll
+    for (int s = 0; s < LOG_H; ++s)
+#pragma unroll
+        for (int gg = 0; gg < (1 << s); ++gg) {
+            const int e = S * ((1 << s) - 1) + (g << s) + gg;
+            w[(1 << s) - 1 + gg] = twa[e];
+            wp[(1 << s) - 1 + gg] = twa_sh[e];
+        }
+    radix_inverse_any<LOG_H, AR>(x, w, wp, lc);
+#pragma unroll
+    for (int k = 0; k < H; ++k) dst[(size_t)g * R + t + 64 * k] = x[k];  // lazy [0,2q) / doubles: the column pass scales
+}
+
+template <int AR>
+__global__ __launch_bounds__(NTT_THREADS) void k_ptresc_row3(PtmulArgs a, NttTables T) {
+    using TL = Row3;
+    constexpr int H = 8, LOG_H = 3, R = TL::R, S = TL::ROWS;
+    __shared__ u64 lds[TL::WORDS + 2 * (TL::TWA + TL::TWB)];
+    u64 *twa = lds + TL::WORDS, *twa_sh = twa + TL::TWA, *twb = twa_sh + TL::TWA, *twb_sh = twb + TL::TWB;
+    const uint32_t n = 1u << T.log_n, r1 = 1u << T.log_r1, last = a.nl - 1;
+    const uint32_t tiles = r1 / S, groups = tiles * a.nsel, polys = gridDim.x / groups;
+    uint32_t grp, poly;
+    group_member(blockIdx.x, groups, polys, T.cu_affine, grp, poly);
+    const uint32_t sl = nth_set_bit(a.slot_mask, grp / tiles);
+    const LimbConst lc = T.limb[sl];
+    if ((lc.fp != 0) != (AR == AR_FP)) return;
+    const uint32_t row0 = (grp % tiles) * S;
+    const int g = threadIdx.x / 64, t = threadIdx.x % 64, p = t / 8, r = t % 8;
+    const size_t tile = (size_t)sl * n + (size_t)row0 * R;
+    const u64 *src = a.tmp + (size_t)poly * last * n + tile;
+    const u64 *tw = T.tw + (size_t)sl * n, *tw_sh = T.tw_sh + (size_t)sl * n;
+    const uint32_t base = r1 + row0 + g;
+    row3_stage_twiddles<3>(Row3Ctx{lds, twa, twa_sh, twb, twb_sh, g, t}, tw, tw_sh, r1 + row0);
+    u64 x[H], w[H - 1], wp[H - 1];
+#pragma unroll
+    for (int k = 0; k < H; ++k) x[k] = src[(size_t)g * R + t + 64 * k];  // doubles from the column pass on an fp limb
+    __syncthreads();
+#pragma unroll
+    for (int s = 0; s < LOG_H; ++s)
+#pragma unroll
+        for (int gg = 0; gg < (1 << s); ++gg) {
+            const int e = S * ((1 << s) - 1) + (g << s) + gg;
+            w[(1 << s) - 1 + gg] = twa[e];
+            wp[(1 << s) - 1 + gg] = twa_sh[e];
+        }
+    radix_forward_any<LOG_H, AR>(x, w, wp, lc);
+#pragma unroll
+    for (int k = 0; k < H; ++k) lds[TL::at(g, t + 64 * k)] = x[k];
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < H; ++k) x[k] = lds[TL::at(g, 64 * p + 8 * k + r)];
+#pragma unroll
+    for (int s = 0; s < LOG_H; ++s)
+#pragma unroll
+        for (int gg = 0; gg < (1 << s); ++gg) {
+            const int e = S * 8 * ((1 << s) - 1) + ((g * 8 + p) << s) + gg;
+            w[(1 << s) - 1 + gg] = twb[e];
+            wp[(1 << s) - 1 + gg] = twb_sh[e];
+        }
+    radix_forward_any<LOG_H, AR>(x, w, wp, lc);
+#pragma unroll
+    for (int k = 0; k < H; ++k) lds[TL::at(g, 64 * p + 8 * k + r)] = x[k];  // own words
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < H; ++k) x[k] = lds[TL::at(g, 64 * p + 8 * r + k)];
+    load_round_twiddles<LOG_H>(tw, tw_sh, base * 64 + 8 * p + r, w, wp);
+    radix_forward_any<LOG_H, AR>(x, w, wp, lc);
+#pragma unroll
+    for (int k = 0; k < H; ++k)
+        lds[TL::at(g, 64 * p + 8 * r + k)] = (AR == AR_FP) ? fp_to_canonical(bitsd(x[k]), lc.qd, lc.qinv) : canon8(x[k], lc.q, lc.q2);
+    __syncthreads();
+    const u64 ci = a.c[sl], ci_sh = a.c_sh[sl];
+    const ulong2 *cq = reinterpret_cast<const ulong2 *>(a.in + (size_t)poly * a.nl * n + tile);
+    const ulong2 *pt = reinterpret_cast<const ulong2 *>(a.pt + ptmul_pt_offset(a, poly, n) + tile);
+    ulong2 *dst = reinterpret_cast<ulong2 *>(a.out + (size_t)poly * last * n + tile);
+    for (int e = threadIdx.x; e < S * R / 2; e += NTT_THREADS) {
+        const int gg = (2 * e) / R, xx = (2 * e) % R;
+        const ulong2 tt = cq[e], m = pt[e];
+        ulong2 v;
+        v.x = shoup_mul(sub_mod(mul_mod(tt.x, m.x, lc), lds[TL::at(gg, xx)], lc.q), ci, ci_sh, lc.q);
+        v.y = shoup_mul(sub_mod(mul_mod(tt.y, m.y, lc), lds[TL::at(gg, xx + 1)], lc.q), ci, ci_sh, lc.q);
+        dst[e] = v;
+    }
+}
+
 }  // namespace mk

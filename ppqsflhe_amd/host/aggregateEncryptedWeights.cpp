@@ -10,6 +10,12 @@
 // one, one non-negative number per input file in argument order (sample counts as they are).  One
 // mkckks_eval_wsum_batch (EvalMult(ct, w_c) per file + the EvalAdd chain) and one rescale; the same bytes as serverRound
 // --weights with every client marked "-".
+// --slot-weights <file> (anywhere after <cc_path>): every coordinate of the aggregate scaled by a factor of its own, read
+// from a plaintext weights_summary JSON in the schema encryptModelWeights reads (slotweights.hpp) -- the divisor
+// 1 / count_j of a round whose clients cover different coordinates, a per-layer rate, a 0/1 mask.  The file holds the
+// whole factor (nothing multiplies by 1/n as well): one mkckks_eval_sum_batch, then EvalMult(ct, plaintext) with one
+// rescale last (mkckks_mult_plain_rescale_batch); the same bytes as serverRound --slot-weights with every client marked
+// "-".  Not together with --weights (that needs a second rescale and a second level).
 #include "hostlib.hpp"
 using namespace mkh;
 
@@ -28,6 +34,28 @@ int main(int argc, char *argv[]) {
             av.erase(av.begin() + i, av.begin() + i + 2);
             break;
         }
+    SlotWeights sw;
+    for (size_t i = 1; i < av.size(); ++i)
+        if (std::string(av[i]) == "--slot-weights") {
+            if (i + 1 >= av.size() || !*av[i + 1]) {
+                std::cerr << "[agg] ERROR: --slot-weights needs a file" << std::endl;
+                return 1;
+            }
+            if (have_weights) {
+                std::cerr << "[agg] ERROR: --slot-weights cannot be combined with --weights" << std::endl;
+                return 1;
+            }
+            sw.path = av[i + 1];
+            av.erase(av.begin() + i, av.begin() + i + 2);
+            break;
+        }
+    if (sw.on()) {
+        const std::string err = load_slot_weights(sw.path, sw.file);
+        if (!err.empty()) {
+            std::cerr << "[agg] ERROR: " << err << std::endl;
+            return 1;
+        }
+    }
     argc = (int)av.size();
     argv = av.data();
     if (argc < 5) {
@@ -77,6 +105,19 @@ int main(int argc, char *argv[]) {
             uint64_t *d_in = s.to_device(flat.data(), flat.size());
             seeds.expand(s, d_in, first.nl, 0, n_files * B);
             uint64_t *d_sum = s.alloc<uint64_t>(B * words);
+            const uint64_t *d_slot_pt = nullptr;
+            if (sw.on()) {
+                std::vector<double> vals;
+                std::string err = slot_weights_headroom_error(s, first, sw);
+                if (err.empty()) err = slot_weight_values(s, items, outputJson, sw, vals);
+                if (!err.empty()) {
+                    std::cerr << "[agg] ERROR: " << err << std::endl;
+                    return 1;
+                }
+                uint64_t *d_pt = s.alloc<uint64_t>(B * (size_t)first.nl * N);
+                encode_slot_weights(s, vals, B, first, d_pt);
+                d_slot_pt = d_pt;
+            }
             if (rw.on()) {
                 const std::string err = weights_headroom_error(s, first);
                 if (!err.empty()) {
@@ -88,7 +129,7 @@ int main(int argc, char *argv[]) {
             } else {
                 Session::check(mkckks_eval_sum_batch(s.ctx(), d_in, d_sum, (uint32_t)n_files, (uint32_t)B, first.nl));
             }
-            finish_aggregate(s, items, d_sum, first, n_files, outputJson, rw.on());
+            finish_aggregate(s, items, d_sum, first, n_files, outputJson, rw.on(), d_slot_pt);
         }
         write_envelope(outputJson, output_file, binary);
     } catch (const std::exception &e) {

@@ -25,6 +25,7 @@
 #include "base64.hpp"
 #include "json.hpp"
 #include "sampler.hpp"
+#include "slotweights.hpp"
 #include "weights.hpp"
 
 namespace mkh {
@@ -796,10 +797,61 @@ struct RoundWeights {
     bool on() const { return !w.empty(); }
 };
 
+// --slot-weights: per-coordinate factors of the aggregate (slotweights.hpp), multiplied in as an encoded plaintext by the
+// closing EvalMult in place of its constant 1/n: cc->EvalMult(ct, plaintext) where the reference has
+// cc->EvalMult(ct, 0.5) (aggregateEncryptedWeights.cpp:82-83).  The plaintexts are encoded like the constants of
+// --weights: at the ciphertexts' limbs and sf(weights_sf_level(first)).
+struct SlotWeights {
+    std::string path;  // empty: off
+    SlotWeightsFile file;
+    bool on() const { return !path.empty(); }
+};
+inline std::string slot_weights_headroom_error(const Session &s, const Ciphertext &first, const SlotWeights &sw) {
+    double log_q = 0;
+    for (uint32_t i = 0; i < first.nl; ++i) log_q += std::log2((double)s.moduli()[i]);
+    return slot_headroom_error(std::log2(first.scale), std::log2(s.sf(weights_sf_level(first), false)), sw.file.max_abs, log_q,
+                               first.nl);
+}
+// the slot vectors of the round's aggregated ciphertexts, vals [B][slots] in item order; the error text, empty on success
+inline std::string slot_weight_values(const Session &s, const std::vector<AggItem> &items, const Json &outputJson,
+                                      const SlotWeights &sw, std::vector<double> &vals) {
+    const size_t slots = s.slots();
+    vals.assign(items.size() * slots, 0.0);
+    for (size_t b = 0; b < items.size(); ++b) {
+        const Json &lay = outputJson.at("weights_summary").at(items[b].out_layer);
+        const std::string err = slot_vector(sw.file, lay.at("layer").as_string(), lay.at("shape"), items[b].field, items[b].idx,
+                                            lay.at("values").size(), s.batch(), &vals[b * slots], slots);
+        if (!err.empty()) return err;
+    }
+    return "";
+}
+// what decides the encoded planes of a round: the file (by name, as the keys are), the items and the encoding
+inline std::string slot_weights_tag(const std::vector<AggItem> &items, const Json &outputJson, const SlotWeights &sw,
+                                    const Ciphertext &first) {
+    std::string tag = sw.path + "|" + std::to_string(first.nl) + "|" + std::to_string(weights_sf_level(first));
+    for (const AggItem &it : items)
+        tag += "|" + outputJson.at("weights_summary").at(it.out_layer).at("layer").as_string() + "/" + std::to_string(it.field) +
+               "/" + std::to_string(it.idx);
+    return tag;
+}
+// d_pt u64[B][first.nl][N] = the encoded slot vectors (one mkckks_encode_batch)
+inline void encode_slot_weights(Session &s, const std::vector<double> &vals, size_t B, const Ciphertext &first, uint64_t *d_pt) {
+    void *d_vals = nullptr;
+    Session::check(mkckks_dev_alloc(s.ctx(), vals.size() * sizeof(double), &d_vals));
+    int rc = mkckks_upload(s.ctx(), d_vals, vals.data(), vals.size() * sizeof(double));
+    if (rc == MKCKKS_OK)
+        rc = mkckks_encode_batch(s.ctx(), static_cast<const double *>(d_vals), d_pt, (uint32_t)B, first.nl,
+                                 s.sf(weights_sf_level(first), false));
+    if (rc == MKCKKS_OK) rc = mkckks_sync(s.ctx());
+    mkckks_dev_free(s.ctx(), d_vals);
+    Session::check(rc);
+}
+
 // weighted (--weights): d_sum already is sum_c M_c * x_c (mkckks_reencrypt_wsum_batch / mkckks_eval_wsum_batch), so what
 // is left of EvalMult is its rescale -- the result's header is the same
+// d_slot_pt (--slot-weights): the encoded per-slot factors u64[B][nl][N]; EvalMult(ct, plaintext) with ONE rescale last
 inline AggResult scale_aggregate(Session &s, size_t B, uint64_t *d_sum, const Ciphertext &first, size_t n_clients,
-                                 bool weighted = false) {
+                                 bool weighted = false, const uint64_t *d_slot_pt = nullptr) {
     const uint32_t N = s.N(), nl = first.nl;
     AggResult r;
     Ciphertext &res = r.meta;
@@ -809,6 +861,9 @@ inline AggResult scale_aggregate(Session &s, size_t B, uint64_t *d_sum, const Ci
         // EvalMult(ct, double): rescale first (ModReduceInternalInPlace), then the integer constant
         if (nl < 2) throw std::runtime_error("ciphertext has no limb left to rescale");
         r.d_out = s.alloc<uint64_t>(B * (size_t)2 * (nl - 1) * N);
+        if (d_slot_pt)
+            Session::check(mkckks_mult_plain_rescale_batch(s.ctx(), d_sum, d_slot_pt, r.d_out, (uint32_t)B, (uint32_t)B, nl));
+        else
         if (weighted) Session::check(mkckks_rescale_batch(s.ctx(), d_sum, r.d_out, (uint32_t)B, nl));
         else Session::check(mkckks_rescale_mult_const_batch(s.ctx(), d_sum, r.d_out, (uint32_t)B, nl, operand));
         res.nl = nl - 1;
@@ -816,6 +871,8 @@ inline AggResult scale_aggregate(Session &s, size_t B, uint64_t *d_sum, const Ci
         res.scale = first.scale / (double)s.moduli()[nl - 1] * s.sf(res.level, false);
         res.noise_deg = 2;
     } else {
+        if (d_slot_pt) Session::check(mkckks_mult_plain_batch(s.ctx(), d_sum, d_slot_pt, (uint32_t)B, (uint32_t)B, nl));
+        else
         if (!weighted) Session::check(mkckks_mult_const_batch(s.ctx(), d_sum, (uint32_t)B, nl, operand));
         res.nl = nl;
         res.level = first.level;
@@ -844,8 +901,8 @@ inline void store_agg_items(Session &s, const std::vector<AggItem> &items, const
 }
 
 inline AggResult finish_aggregate(Session &s, const std::vector<AggItem> &items, uint64_t *d_sum, const Ciphertext &first,
-                                  size_t n_clients, Json &outputJson, bool weighted = false) {
-    AggResult r = scale_aggregate(s, items.size(), d_sum, first, n_clients, weighted);
+                                  size_t n_clients, Json &outputJson, bool weighted = false, const uint64_t *d_slot_pt = nullptr) {
+    AggResult r = scale_aggregate(s, items.size(), d_sum, first, n_clients, weighted, d_slot_pt);
     store_agg_items(s, items, r.d_out, r.meta, outputJson);
     return r;
 }

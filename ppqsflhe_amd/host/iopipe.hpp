@@ -303,6 +303,7 @@ struct RoundPlan {
     size_t evk_words = 0;
     unsigned threads = 4;
     RoundWeights weights;                     // --weights (device order); off: the plain mean
+    const uint64_t *slot_pt = nullptr;        // --slot-weights: encoded per-slot factors, device u64[B][nl][N]; off: null
 };
 
 inline unsigned round_chunk(size_t B) {
@@ -318,7 +319,7 @@ class RoundCache {
 public:
     explicit RoundCache(Session &s) : s_(s) {}
     ~RoundCache() {
-        for (Slot *b : {&all, &sum, &out, &evk, &evk_scaled, &back, &back_evk, &hra, &hra_rand, &hra_pk})
+        for (Slot *b : {&all, &sum, &out, &evk, &evk_scaled, &slot_pt, &back, &back_evk, &hra, &hra_rand, &hra_pk})
             if (b->p) mkckks_dev_free(s_.ctx(), b->p);
     }
     RoundCache(const RoundCache &) = delete;
@@ -356,6 +357,9 @@ public:
     // gives every client a wrong aggregate without any error); it is remade otherwise.
     Slot evk_scaled;
     std::string scaled_tag;
+    // --slot-weights: the encoded per-slot factors and what they were encoded from (hostlib.hpp: slot_weights_tag)
+    Slot slot_pt;
+    std::string slot_tag;
     std::unique_ptr<PinnedRing> ring, out_pin;
     std::string warm_shape;              // "<nl>/<chunk>/<n_pre>/<n_plain>/<rescale>" the kernels were launched with
 
@@ -442,9 +446,13 @@ inline AggResult run_round_pipeline(Session &s, const RoundPlan &plan, Json doc,
             Session::check(mkckks_eval_wsum_batch(s.ctx(), terms, out, n_terms, (uint32_t)cnt, nl_, w_terms, rw.sf_level, n_pre ? 1 : 0));
         else Session::check(mkckks_eval_sum_batch(s.ctx(), terms, out, n_terms, (uint32_t)cnt, nl_));
     };
-    auto scale_sum = [&](uint64_t *sum, uint64_t *outp, size_t cnt, uint32_t nl_, bool rescale_) {
+    auto scale_sum = [&](uint64_t *sum, uint64_t *outp, size_t b0, size_t cnt, uint32_t nl_, bool rescale_) {
         const double operand = 1.0 / (double)n_clients;
-        if (rescale_) {
+        if (plan.slot_pt) {  // EvalMult(ct, plaintext): the per-slot factors of indices b0 .. b0 + cnt, ONE rescale last
+            const uint64_t *pt = plan.slot_pt + b0 * (size_t)nl_ * N;
+            if (rescale_) Session::check(mkckks_mult_plain_rescale_batch(s.ctx(), sum, pt, outp, (uint32_t)cnt, (uint32_t)cnt, nl_));
+            else Session::check(mkckks_mult_plain_batch(s.ctx(), sum, pt, (uint32_t)cnt, (uint32_t)cnt, nl_));
+        } else if (rescale_) {
             if (weighted) Session::check(mkckks_rescale_batch(s.ctx(), sum, outp, (uint32_t)cnt, nl_));
             else Session::check(mkckks_rescale_mult_const_batch(s.ctx(), sum, outp, (uint32_t)cnt, nl_, operand));
         } else if (!weighted) {
@@ -484,7 +492,8 @@ inline AggResult run_round_pipeline(Session &s, const RoundPlan &plan, Json doc,
     const uint64_t blobs0 = head.size(), blob_size = sizeof(BlobHeader) + out_bytes;
     const BlobHeader out_hdr = header_of(res, N);
     const std::string shape = std::to_string(nl) + "/" + std::to_string(Bc) + "/" + std::to_string(n_pre) + "/" +
-                              std::to_string(n_plain) + "/" + std::to_string((int)rescale) + (weighted ? "/w" : "");
+                              std::to_string(n_plain) + "/" + std::to_string((int)rescale) + (weighted ? "/w" : "") +
+                              (plan.slot_pt ? "/s" : "");
     if (cache.warm_shape != shape) {   // process warm-up, the last part of the setup: copy streams, the workspace of one chunk and the first launch of every
         // kernel of the round (the HIP runtime resolves a kernel when it is first launched: ~30 ms for this path), on
         // whatever the fresh buffers hold -- none of the kernels addresses memory by data, and chunk 0 is overwritten below
@@ -498,7 +507,7 @@ inline AggResult run_round_pipeline(Session &s, const RoundPlan &plan, Json doc,
         uint64_t *slot = d_all + n_pre * cnt * words;
         if (n_pre) sum_pre(d_all, n_plain ? slot : d_sum, cnt, nl);
         if (n_plain) sum_plain(n_pre ? slot : slot + cnt * words, d_sum, cnt, nl);
-        scale_sum(d_sum, d_out, cnt, nl, rescale);
+        scale_sum(d_sum, d_out, 0, cnt, nl, rescale);
         Session::check(mkckks_fence_compute(s.ctx()));
         Session::check(mkckks_download_async(s.ctx(), out_pin.slot(0), rescale ? d_out : d_sum, out_bytes, &ticket));
         Session::check(mkckks_copy_wait(s.ctx(), ticket));
@@ -750,7 +759,7 @@ inline AggResult run_round_pipeline(Session &s, const RoundPlan &plan, Json doc,
                 if (n_plain) sum_plain(n_pre ? slot : slot + cnt * words, sum, cnt, nl);
                 lap(1);
                 uint64_t *outp = rescale ? d_out + b0 * owords : sum;
-                scale_sum(sum, outp, cnt, nl, rescale);
+                scale_sum(sum, outp, b0, cnt, nl, rescale);
                 lap(2);
                 Session::check(mkckks_fence_compute(s.ctx()));
                 lap(3);

@@ -36,6 +36,12 @@
 // noiseScaleDeg-1 inputs: nothing).  The output has the header of the plain mean's; --back, --back-limbs and --hra-back
 // work on it as they are.  Refused: a count of weights that is not the count of clients, a negative weight or one that is
 // no number, inputs without headroom for the weighted sum (include/mkckks.h).  Without --weights nothing changes.
+// --slot-weights <file> (anywhere after <output_aggfile>): every coordinate of the aggregate scaled by a factor of its own
+// in place of 1/n -- a plaintext weights_summary JSON in the schema encryptModelWeights reads, split and padded as that
+// program splits its input (slotweights.hpp), encoded once and multiplied in by the closing EvalMult with ONE rescale last
+// (mkckks_mult_plain_rescale_batch).  Under --rounds the encoded planes stay resident in HBM like the keys (by file name).
+// Refused: together with --weights, a missing or unreadable file, a layer of the round the file lacks, another shape or
+// value count, a factor that is not finite, inputs without headroom for the largest factor.
 // Binary (MKWS) envelopes take the I/O pipeline of iopipe.hpp: files are indexed, not loaded; reader threads fill pinned
 // slots, uploads run beside the reads, residues are range-checked on the device, results are written by pwrite() from
 // pinned slots.  MKCKKS_SYNC_IO=1 forces the synchronous path (every ciphertext through read_envelope / decode_ct /
@@ -63,6 +69,8 @@ struct RoundArgs {
     bool hra_bits_ok = true;  // false: --hra-sigma-bits was no integer in [6, 56] (reported by run_round)
     bool have_weights = false;  // --weights given
     std::string weights_text;   // its value (judged by run_round, which knows the clients)
+    SlotWeights slot;           // --slot-weights: its file, loaded by main before the context
+    std::string slot_error;     // --slot-weights without a value or together with --weights (reported by main)
 };
 // tokens: <output_aggfile> <rekey_1|-> <encfile_1> ... [--back <rekey_back_1> <output_encfile_1> ...]
 static bool parse_round(std::vector<std::string> t, RoundArgs &a) {
@@ -88,6 +96,16 @@ static bool parse_round(std::vector<std::string> t, RoundArgs &a) {
             t.erase(t.begin() + i, t.begin() + i + 2);
             break;
         }
+    std::string slot_path, slot_error;
+    for (size_t i = 1; i < t.size(); ++i)
+        if (t[i] == "--slot-weights") {  // one value, taken out the same way; its errors have a line of their own
+            const bool has_value = i + 1 < t.size() && !t[i + 1].empty();
+            if (has_value) slot_path = t[i + 1];
+            else slot_error = "--slot-weights needs a file";
+            t.erase(t.begin() + i, t.begin() + i + (i + 1 < t.size() ? 2 : 1));
+            break;
+        }
+    if (!slot_path.empty() && have_weights) slot_error = "--slot-weights cannot be combined with --weights";
     std::string hra_pk;
     uint32_t hra_bits = HRA_SIGMA_BITS_DEFAULT;
     bool hra_bits_ok = true, have_bits = false;
@@ -125,6 +143,8 @@ static bool parse_round(std::vector<std::string> t, RoundArgs &a) {
     a.back_limbs = back_limbs;
     a.have_weights = have_weights;
     a.weights_text = weights_text;
+    a.slot.path = slot_path;
+    a.slot_error = slot_error;
     a.output_file = t[0];
     for (size_t i = 1; i + 1 < n_args; i += 2) {
         a.rekey_paths.push_back(t[i]);
@@ -276,6 +296,29 @@ static int run_round(Session &s, ServerState &st, const RoundArgs &a) {
         }
         rw.sf_level = weights_sf_level(first);
     }
+    const uint64_t *d_slot_pt = nullptr;  // --slot-weights: the encoded factors [B][nl][N], resident from round to round
+    if (a.slot.on() && !items.empty()) {
+        const Ciphertext first = meta_of(first_header(), s);
+        std::vector<double> vals;
+        std::string err = slot_weights_headroom_error(s, first, a.slot);
+        if (err.empty()) err = slot_weight_values(s, items, outputJson, a.slot, vals);
+        if (!err.empty()) {
+            std::cerr << "[round] ERROR: " << err << std::endl;
+            return 1;
+        }
+        const size_t pt_words = items.size() * (size_t)first.nl * N;
+        const std::string tag = slot_weights_tag(items, outputJson, a.slot, first);
+        if (pt_words > st.cache.slot_pt.words) st.cache.slot_tag.clear();  // the array moves: nothing is kept
+        uint64_t *d_pt = st.cache.grow(st.cache.slot_pt, pt_words);
+        const bool resident = st.cache.slot_tag == tag;
+        if (!resident) {
+            st.cache.slot_tag.clear();
+            encode_slot_weights(s, vals, items.size(), first, d_pt);
+            st.cache.slot_tag = tag;
+        }
+        std::cout << "[round] --slot-weights: " << items.size() << " plaintext(s) " << (resident ? "resident" : "encoded") << "\n";
+        d_slot_pt = d_pt;
+    }
     if (a.compact) {
         if (a.back_limbs < 1) {
             std::cerr << "[round] ERROR: --back-limbs must be at least 1" << std::endl;
@@ -307,6 +350,7 @@ static int run_round(Session &s, ServerState &st, const RoundArgs &a) {
         plan.evk_words = evk_words;
         plan.threads = threads;
         plan.weights = rw;
+        plan.slot_pt = d_slot_pt;
         RoundTimes tm;
         agg = run_round_pipeline(s, plan, outputJson, a.output_file, st.cache, tm);
         pinned_out = true;
@@ -359,7 +403,7 @@ static int run_round(Session &s, ServerState &st, const RoundArgs &a) {
             else
                 Session::check(mkckks_eval_sum_batch(s.ctx(), d_terms, d_sum, (uint32_t)(n_plain + (n_pre ? 1 : 0)), (uint32_t)B, nl));
         }
-        agg = finish_aggregate(s, items, d_sum, first, n_clients, outputJson, rw.on());
+        agg = finish_aggregate(s, items, d_sum, first, n_clients, outputJson, rw.on(), d_slot_pt);
     }
     if (!pinned_out) write_envelope(outputJson, a.output_file, binary);
     if (int rc = run_back_leg(s, st, a, items, agg, outputJson, binary, pinned_out, threads)) return rc;
@@ -512,7 +556,7 @@ static int run_back_leg(Session &s, ServerState &st, const RoundArgs &a, const s
 int main(int argc, char *argv[]) {
     auto usage = [&] {
         std::cerr << "Usage: " << argv[0] << " <cc_path> <output_aggfile> <rekey_1|-> <encfile_1> [<rekey_2|-> <encfile_2> ...]"
-                  << " [--weights <w_1,...,w_n>] [--back <rekey_back_1|-> <output_encfile_1> ... [--back-limbs <k>] [--hra-back <target_domain_pubkey> [--hra-sigma-bits <s>]]]\n       " << argv[0]
+                  << " [--weights <w_1,...,w_n> | --slot-weights <factors.json>] [--back <rekey_back_1|-> <output_encfile_1> ... [--back-limbs <k>] [--hra-back <target_domain_pubkey> [--hra-sigma-bits <s>]]]\n       " << argv[0]
                   << " <cc_path> --rounds <file with one such argument list (after <cc_path>) per line>" << std::endl;
         return 1;
     };
@@ -544,6 +588,14 @@ int main(int argc, char *argv[]) {
         RoundArgs a;
         if (!parse_round(std::vector<std::string>(argv + 2, argv + argc), a)) return usage();
         rounds.push_back(std::move(a));
+    }
+    for (RoundArgs &a : rounds) {  // the --slot-weights refusals that need no context come before anything is loaded
+        std::string err = a.slot_error;
+        if (err.empty() && a.slot.on()) err = load_slot_weights(a.slot.path, a.slot.file);
+        if (!err.empty()) {
+            std::cerr << "[round] ERROR: " << err << std::endl;
+            return 1;
+        }
     }
     const double t_start = now_ms();
     CcFile cc;
