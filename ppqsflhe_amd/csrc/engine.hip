@@ -911,28 +911,17 @@ static DevConv to_dev(const BaseConvTable &t, const u64 *d_hat, const u64 *d_hat
     c.hat = d_hat;
     c.hat_d = reinterpret_cast<const double *>(d_hat_fp);
     c.hatq_d = c.hat_d + t.hat.size();
+    c.hat30_d = c.hatq_d + t.hat.size();
     return c;
 }
 
-// [S/s_i]_t and [S/s_i]_t / t as doubles (bit patterns), [n_in][n_out] each: the fp64 form of the conversion matrix
-static std::vector<u64> hat_as_doubles(const BaseConvTable &t, const std::vector<u64> &moduli) {
-    const size_t cnt = t.hat.size(), n_out = t.dst.size();
-    std::vector<u64> v(2 * cnt);
-    for (size_t e = 0; e < cnt; ++e) {
-        const long double q = (long double)moduli[t.dst[e % n_out]];
-        const double h = (double)t.hat[e], hq = (double)((long double)t.hat[e] / q);
-        std::memcpy(&v[e], &h, 8);
-        std::memcpy(&v[cnt + e], &hq, 8);
-    }
-    return v;
-}
-
-const DevConv &Engine::modup_conv(uint32_t nl, uint32_t part) {
+const DevConv &Engine::modup_conv(uint32_t nl, uint32_t part, bool p_scaled) {
     auto key = std::make_pair(nl, part);
-    auto it = modup_cache_.find(key);
-    if (it != modup_cache_.end()) return it->second;
-    BaseConvTable t = ps_.modup_table(nl, part);
-    const std::string tag = std::to_string(nl) + "_" + std::to_string(part);
+    auto &cache = p_scaled ? modup_ps_cache_ : modup_cache_;
+    auto it = cache.find(key);
+    if (it != cache.end()) return it->second;
+    BaseConvTable t = p_scaled ? ps_.modup_table_pscaled(nl, part) : ps_.modup_table(nl, part);
+    const std::string tag = std::to_string(nl) + "_" + std::to_string(part) + (p_scaled ? "_ps" : "");
     const u64 *d_hat = limb_vector("modup_hat_" + tag, t.hat);
     DevConv c = to_dev(t, d_hat, limb_vector("modup_hatd_" + tag, hat_as_doubles(t, ps_.moduli)));
     const uint32_t lo = part * ps_.alpha;
@@ -941,7 +930,7 @@ const DevConv &Engine::modup_conv(uint32_t nl, uint32_t part) {
     uint32_t w = 0;
     for (uint32_t s = 0; s < nl + ps_.K; ++s)
         if (s < lo || s >= lo + c.n_in) c.dst_slot[w++] = s;
-    return modup_cache_.emplace(key, c).first->second;
+    return cache.emplace(key, c).first->second;
 }
 
 const DevConv &Engine::moddown_conv(uint32_t nl) {
@@ -1187,13 +1176,13 @@ static void launch_conv_col_psum(const ConvIo &io, const NttTables &T, const Dev
     MK_HIP(hipGetLastError());
 }
 // inverse column pass of the P limbs of every client of a group, summed over the clients as integers (k_icol_sum)
-static void launch_icol_sum(const u64 *pc, u64 *psum, const NttTables &T, const u64 *scale, const u64 *scale_sh, uint32_t K,
-                            uint32_t n_polys, uint32_t n_clients, size_t in_cstride, hipStream_t s) {
+static void launch_icol_sum(const u64 *pc, u64 *psum, const NttTables &T, uint32_t K, uint32_t n_polys, uint32_t n_clients,
+                            size_t in_cstride, hipStream_t s) {
     if (!dispatch<3, 4>(fast_log_h(T.log_r1, 1u << T.log_r2), [&](auto log_h) {
             constexpr int LOG_H = decltype(log_h)::value;
             with_int_arith(T, [&](auto ar) {
                 k_icol_sum<LOG_H, decltype(ar)::value><<<dim3(col_tiles<LOG_H>(T), n_polys * K), NTT_THREADS, 0, s>>>(
-                    pc, psum, T, scale, scale_sh, K, n_clients, in_cstride);
+                    pc, psum, T, K, n_clients, in_cstride);
             });
         }))
         throw std::logic_error("summed conversion needs 64- or 256-point columns");
@@ -1506,8 +1495,10 @@ const u64 *Engine::p_inverse(uint32_t nl) {
 
 // EvalKeySwitchPrecomputeCore on `cnt` polynomials c1 (items ct_stride apart): fills the converted limbs of
 // dig[item][part][ext][N] in EVALUATION format; the digits' own limbs are NOT copied (readers take them from c1).
+// p_scaled (the merged n-client flow only): convert with the P-scaled tables, so the P limbs of the digits hold
+// N^-1 [(P/p_k)^-1]_{p_k} d_j and the flow's inverse transform of the P limbs does not scale (k_icol_sum).
 void Engine::modup_core(const u64 *c1, size_t c1_stride, u64 *coef, u64 *dig, uint32_t cnt, uint32_t nl,
-                        bool rows_int_only, uint32_t in_group, size_t in_gstride) {
+                        bool rows_int_only, uint32_t in_group, size_t in_gstride, bool p_scaled) {
     const uint32_t n = ps_.n, ext = nl + ps_.K, nparts = ps_.num_parts(nl), D = ps_.D;
     const u64 *fold = folded_scale(nl);
     // the fused conversion kernel exists when the column pass has a radix kernel; it reads packed 30-bit halves
@@ -1521,14 +1512,14 @@ void Engine::modup_core(const u64 *c1, size_t c1_stride, u64 *coef, u64 *dig, ui
     // "all fp64-class" or "q_0 first, then fp64-class" (k_conv_col's SRCMODE 1 / 2), else packed halves throughout
     bool doubles = fused && tabs_.has_fp && fast_log_h(tabs_.log_r1, 1u << tabs_.log_r2) >= 3;
     for (uint32_t part = 0; part < nparts && doubles; ++part) {
-        const DevConv &cv = modup_conv(nl, part);
+        const DevConv &cv = modup_conv(nl, part, p_scaled);
         if (conv_src_mode(cv) < 0 || (conv_src_mode(cv) != 0 && cv.n_in > 4)) doubles = false;
     }
     ntt_passes(s1, tabs_, cnt, true, fold, fold + D, stream_, fused ? (doubles ? 2 : 1) : 0);
     for (uint32_t part = 0; part < nparts && fused; ++part) {
         // S2+S3a: base conversion fused into the column pass of each complement limb
         ConvIo io{coef, dig + (size_t)part * ext * n, (size_t)nl * n, dstride, cnt, 0, 0};
-        const DevConv &cv = modup_conv(nl, part);
+        const DevConv &cv = modup_conv(nl, part, p_scaled);
         launch_conv_col(io, tabs_, cv, stream_, doubles ? conv_src_mode(cv) : 0);
     }
     if (fused) {
@@ -1539,7 +1530,7 @@ void Engine::modup_core(const u64 *c1, size_t c1_stride, u64 *coef, u64 *dig, ui
         MK_HIP(hipGetLastError());
         return;
     }
-    if (rows_int_only) throw std::logic_error("fused inner product needs the radix kernels");
+    if (rows_int_only || p_scaled) throw std::logic_error("fused inner product needs the radix kernels");
     for (uint32_t part = 0; part < nparts; ++part) {  // ring sizes without a radix column kernel
         const DevConv &cv = modup_conv(nl, part);
         const uint32_t lo = part * ps_.alpha, hi = lo + cv.n_in;
@@ -1906,7 +1897,8 @@ void Engine::reencrypt_sum_merged(const u64 *cts, const u64 *evks, u64 *out, uin
                     ~Reset() { flag = false; }
                 } reset{skip_rows_};
                 skip_rows_ = true;
-                modup_core(c1, ct_words, coef, dig, items, nl, true, cnt, ct_cstride);
+                // P-scaled tables: the converted P limbs hold sc_k d_j, so k_icol_sum's outputs need no scaling
+                modup_core(c1, ct_words, coef, dig, items, nl, true, cnt, ct_cstride, true);
             }
             InnerArgs ia{dig, c1, evk0, til, ct_words, nl, ext, D, ps_.alpha, items, 0, 0};
             ia.ipc = cnt;
@@ -1921,8 +1913,7 @@ void Engine::reencrypt_sum_merged(const u64 *cts, const u64 *evks, u64 *out, uin
             }
             {   // ApproxModDown: inverse column pass of every item's P limbs, summed over the group's clients as integers
                 // (k_icol_sum), then ONE conversion P -> Q_l and forward column pass per (index, component, target limb)
-                const u64 *fold = folded_scale(nl);
-                launch_icol_sum(pc, psum, tabs_, fold, fold + D, K, 2 * cnt, gc, (size_t)cnt * 2 * K * n, main);
+                launch_icol_sum(pc, psum, tabs_, K, 2 * cnt, gc, (size_t)cnt * 2 * K * n, main);
                 ConvIo cs{psum, convsum, (size_t)K * n, (size_t)nl * n, 2 * cnt, 0, 0};
                 launch_conv_col_psum(cs, tabs_, moddown_conv(nl), main);
             }

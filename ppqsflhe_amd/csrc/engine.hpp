@@ -49,6 +49,7 @@ struct DevConv {
     const u64 *hat;        // device, [n_in][n_out]: [S/s_i]_t
     const double *hat_d;   // device, [n_in][n_out]: the same as doubles (used for fp64-class targets)
     const double *hatq_d;  // device, [n_in][n_out]: [S/s_i]_t / t
+    const double *hat30_d;  // device, [2][n_out]: [S/s_0 * 2^30]_t and its quotient by t (packed source 0, fp64-class targets)
 };
 
 // Switches of the library (environment variables MKCKKS_*), read once when a context is created.  Defaults are the
@@ -228,7 +229,8 @@ private:
     void need_device() const;
     void check_nl(uint32_t nl) const;
     u64 *workspace(size_t words);  // grow-only scratch arena (stream-ordered reuse)
-    const DevConv &modup_conv(uint32_t nl, uint32_t part);
+    // p_scaled: the P targets' constants carry ModDown's scale (ParamSet::modup_table_pscaled; the merged n-client flow)
+    const DevConv &modup_conv(uint32_t nl, uint32_t part, bool p_scaled = false);
     const DevConv &moddown_conv(uint32_t nl);
     const u64 *limb_vector(const std::string &key, const std::vector<u64> &vals);  // cached small device arrays
     const u64 *garner_table(uint32_t nl);  // CRT interpolation constants of the first nl limbs (decode)
@@ -238,7 +240,7 @@ private:
     const u64 *folded_scale(uint32_t nl);
     const u64 *p_inverse(uint32_t nl);
     void modup_core(const u64 *c1, size_t c1_stride, u64 *coef, u64 *dig, uint32_t cnt, uint32_t nl,
-                    bool rows_int_only = false, uint32_t in_group = 0, size_t in_gstride = 0);
+                    bool rows_int_only = false, uint32_t in_group = 0, size_t in_gstride = 0, bool p_scaled = false);
     bool qsum_ok(uint32_t nl) const;
     // wt: weight table of the clients (weighted instance of the two Q-limb kernels), nullptr: the plain sum
     void reencrypt_sum_merged(const u64 *cts, const u64 *evks, u64 *out, uint32_t n_clients, uint32_t n_ct, uint32_t nl,
@@ -291,7 +293,7 @@ private:
     u64 *ws_ = nullptr;
     size_t ws_words_ = 0;
     Knobs knobs_;
-    std::map<std::pair<uint32_t, uint32_t>, DevConv> modup_cache_;
+    std::map<std::pair<uint32_t, uint32_t>, DevConv> modup_cache_, modup_ps_cache_;  // plain / P-scaled tables
     std::map<uint32_t, DevConv> moddown_cache_;
     std::map<std::string, u64 *> vec_cache_;
     std::map<std::string, u64 *> wt_cache_;  // weight_table

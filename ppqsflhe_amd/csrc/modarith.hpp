@@ -276,6 +276,15 @@ MK_HD u64 pm_reduce128_wide(u64 hi, u64 lo, const PmK &P, u64 q) {
     return pm_reduce128(nhi, nlo, P, q);
 }
 
+// An output word of an inverse butterfly round -> the canonical residue in [0, q) (0 stays 0).  Bound of the word, by
+// the round's last stage:
+//   Shoup (gs_butterfly):             x' = csub(x + y, 2q) < 2q,  y' = shoup_lazy(..) < 2q for any 64-bit input  -> v < 2q
+//   pseudo-Mersenne (gs_butterfly_pm): x' = pm_fold(x + y) < U + 2^30,  y' = pm_lazy(..) < 2.375U, U = 2^k        -> v < 2.375U
+// and 2.375U < 3q (q = U - c, c <= 2^(k-34)), 2.375U > 2q: two conditional subtractions there, one on the Shoup limb.
+MK_HD u64 canon_inverse_round(u64 v, const LimbConst &L, bool pm) {
+    return pm ? csub(csub(v, L.q2), L.q) : csub(v, L.q);
+}
+
 // Barrett reduction of a 128-bit x = hi:lo with x < 2^(k+62) (k = bitlen q) to [0,q).
 // qhat = mulhi64(x >> (k-2), mu), mu = floor(2^(62+k)/q): qhat in {Q-2,Q-1,Q}.
 // (X/q - qhat's real value = (f1 m + a f2 - f1 f2) / 2^64 with a = x / 2^(k-2) < 2^64, m = 2^(62+k)/q <= 2^63 and the two

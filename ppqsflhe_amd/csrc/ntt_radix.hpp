@@ -714,17 +714,31 @@ template <int N_IN>
 struct ConvConst {
     uint32_t h0[N_IN], h1[N_IN];  // [S/s_i]_t as 30-bit halves (integer path)
     double hd[N_IN], hq[N_IN];    // [S/s_i]_t and its quotient by t as doubles (fp64 path)
+    double hs, hsq;               // [S/s_0 2^30]_t and its quotient (fp64 path, SRCMODE 2: the high half of packed source 0)
 };
 template <int N_IN, int AR, int SRCMODE, typename CONV>
 MK_D void conv_consts(const CONV &cv, uint32_t jt, ConvConst<N_IN> &k) {
 #pragma unroll
     for (int i = 0; i < N_IN; ++i) {
-        if ((AR == AR_FP) && src_is_double<SRCMODE>(i)) {
+        if ((AR == AR_FP) && SRCMODE != 0) {  // SRCMODE 2, source 0: the constant of its low half
             k.hd[i] = cv.hat_d[i * cv.n_out + jt];
             k.hq[i] = cv.hatq_d[i * cv.n_out + jt];
         } else {
             split30(cv.hat[i * cv.n_out + jt], k.h0[i], k.h1[i]);
         }
+    }
+    if ((AR == AR_FP) && SRCMODE == 2) {
+        k.hs = cv.hat30_d[jt];
+        k.hsq = cv.hat30_d[cv.n_out + jt];
+    }
+}
+// the 30-bit halves of packed source 0 as doubles (fp64-class targets under SRCMODE 2): converted once per source word,
+// shared by every target computed from it
+template <int AR, int SRCMODE>
+MK_D void conv_halves_d(u64 p0, double &lo, double &hi) {
+    if ((AR == AR_FP) && SRCMODE == 2) {
+        lo = (double)(uint32_t)p0;
+        hi = (double)(uint32_t)(p0 >> 32);
     }
 }
 // 30-bit halves of the sources that enter the integer column accumulation (packed sources as they are, double sources
@@ -745,22 +759,19 @@ MK_D void conv_split_sources(const u64 (&p)[N_IN], uint32_t (&a0)[N_IN], uint32_
 // Packed sources and [S/s_i]_t are below 2^60: 30-bit column accumulation, pure v_mad_u64_u32 chains.  Sources that
 // arrive as doubles (fp64-class limbs, below 1.25 * 2^50): an fp64-class target takes their products mod t on the FMA unit
 // (6 operations instead of 4 mads + a share of the Barrett step); an integer-class target uses the split halves.
+// The packed 60-bit source of SRCMODE 2 (q_0 = lo + 2^30 hi, halves s_lo, s_hi as doubles) meets an fp64-class target
+// the same way, as lo [S/s_0]_t + hi [S/s_0 2^30]_t: two more products on the FMA unit, no integer reduction.
 template <int N_IN, int AR, int SRCMODE>
 MK_D u64 conv_output(const u64 (&p)[N_IN], const uint32_t (&a0)[N_IN], const uint32_t (&a1)[N_IN], const ConvConst<N_IN> &k,
-                     const LimbConst &lc) {
+                     const LimbConst &lc, double s_lo = 0.0, double s_hi = 0.0) {
     if ((AR == AR_FP) && SRCMODE != 0) {
         double acc = 0.0;
-        if (SRCMODE == 2) {  // the packed source(s): column accumulation, below 4q < 2^53
-            Cols ia{0, 0, 0};
-#pragma unroll
-            for (int i = 0; i < N_IN; ++i)
-                if (!src_is_double<SRCMODE>(i)) mac_cols(ia, (uint32_t)p[i], (uint32_t)(p[i] >> 32), k.h0[i], k.h1[i]);
-            acc = (double)reduce_cols_lazy(ia, lc);
-        }
+        if (SRCMODE == 2)  // halves below 2^30: each product mod t is within 0.51 q
+            acc = fp_mulmod(s_lo, k.hd[0], k.hq[0], lc.qd) + fp_mulmod(s_hi, k.hs, k.hsq, lc.qd);
 #pragma unroll
         for (int i = 0; i < N_IN; ++i)
             if (src_is_double<SRCMODE>(i)) acc += fp_mulmod(bitsd(p[i]), k.hd[i], k.hq[i], lc.qd);
-        // |acc| <= 4q + 4 * 0.8q < 2^53: exact; into the rounds' range
+        // |acc| <= 2 * 0.51q + 3 * 0.81q (SRCMODE 1: 4 * 0.81q) < 3.5q < 2^53: exact; into the rounds' range
         return dbits(fp_reduce(acc, lc.qd, lc.qinv));
     }
     Cols acc{0, 0, 0};
@@ -819,7 +830,9 @@ __global__ __launch_bounds__(NTT_THREADS, 4) void k_conv_col(ConvIo io, NttTable
             }
             uint32_t a0[N_IN], a1[N_IN];
             if (!((AR == AR_FP) && SRCMODE != 0)) conv_split_sources<N_IN, SRCMODE>(p, a0, a1);
-            x[k] = conv_output<N_IN, AR, SRCMODE>(p, a0, a1, kc, lc);
+            double s_lo = 0.0, s_hi = 0.0;
+            conv_halves_d<AR, SRCMODE>(p[0], s_lo, s_hi);
+            x[k] = conv_output<N_IN, AR, SRCMODE>(p, a0, a1, kc, lc, s_lo, s_hi);
             // the output is materialised here and the refills stay where they are: otherwise the arithmetic sinks to its first
             // use (the butterflies) while all 16 slices' loads stay at the top, and what does not fit is parked in scratch
             asm volatile("" : "+v"(x[k]));
@@ -928,8 +941,10 @@ __global__ __launch_bounds__(NTT_THREADS, 3) void k_conv_col2(ConvIo io, NttTabl
         }
         uint32_t a0[N_IN], a1[N_IN];
         if (!((AR == AR_FP) && SRCMODE != 0)) conv_split_sources<N_IN, SRCMODE>(p, a0, a1);  // once for both targets
-        xa[k] = conv_output<N_IN, AR, SRCMODE>(p, a0, a1, ka, la);
-        xb[k] = conv_output<N_IN, AR, SRCMODE>(p, a0, a1, kb, lb);
+        double s_lo = 0.0, s_hi = 0.0;
+        conv_halves_d<AR, SRCMODE>(p[0], s_lo, s_hi);  // once for both targets
+        xa[k] = conv_output<N_IN, AR, SRCMODE>(p, a0, a1, ka, la, s_lo, s_hi);
+        xb[k] = conv_output<N_IN, AR, SRCMODE>(p, a0, a1, kb, lb, s_lo, s_hi);
         // materialised here (see k_conv_col): this is what makes two targets fit -- 115-117 VGPRs and no scratch, 4 waves
         // per SIMD like the one-target kernel; without it the compiler parked 34-150 registers in scratch
         asm volatile("" : "+v"(xa[k]), "+v"(xb[k]));
@@ -961,14 +976,15 @@ __global__ __launch_bounds__(NTT_THREADS, 3) void k_conv_col2(ConvIo io, NttTabl
 // P-limb coefficients disappear, and the result is the same residue mod q_t, bit for bit.
 //
 // k_icol_sum: inverse COLUMN pass of the P limbs (second pass of ApproxModDown's SetFormat(COEFFICIENT)) of every client
-// of the group, scaled to canonical residues and summed over the clients as 64-bit integers.
+// of the group, brought to canonical residues and summed over the clients as 64-bit integers.  There is no scaling here:
+// the flow's ModUp converts into the P limbs with constants that already carry N^-1 [(P/p_k)^-1]_{p_k}
+// (ParamSet::modup_table_pscaled), and everything from there to this pass is linear mod p_k.
 //   pc:   [client][poly][K][N]  outputs of the inverse row pass (lazy), clients in_cstride words apart
 //   psum: [poly][K][N]          X_k = sum over clients, < n_clients * p_k < 2^64
 // grid (column tile, poly * K + k); the host caps the group so that the sum cannot wrap.
 template <int LOG_H, int AR>
-__global__ __launch_bounds__(NTT_THREADS, 3) void k_icol_sum(const u64 *pc, u64 *psum, NttTables T, const u64 *scale,
-                                                             const u64 *scale_sh, uint32_t K, uint32_t n_clients,
-                                                             size_t in_cstride) {
+__global__ __launch_bounds__(NTT_THREADS, 3) void k_icol_sum(const u64 *pc, u64 *psum, NttTables T, uint32_t K,
+                                                             uint32_t n_clients, size_t in_cstride) {
     using TL = ColTile<LOG_H>;
     constexpr int H = TL::H, S = TL::S;
     static_assert(AR != AR_FP, "P limbs are integer-class");
@@ -980,7 +996,6 @@ __global__ __launch_bounds__(NTT_THREADS, 3) void k_icol_sum(const u64 *pc, u64 
     const int c = threadIdx.x % S, j = threadIdx.x / S;
     const size_t off = ((size_t)poly * K + k) * n + blockIdx.x * S + c;
     const u64 *itw0 = T.itw + (size_t)id * n, *itw_sh0 = T.itw_sh + (size_t)id * n;
-    const u64 sc = scale[id], sc_sh = scale_sh[id];
     u64 acc[H];
 #pragma unroll
     for (int kk = 0; kk < H; ++kk) acc[kk] = 0;
@@ -1008,7 +1023,7 @@ __global__ __launch_bounds__(NTT_THREADS, 3) void k_icol_sum(const u64 *pc, u64 
         for (int kk = 0; kk < H; ++kk) x[kk] = lds[TL::at(kk, j, c)];
         radix_inverse_staged<LOG_H, AR>(x, [&](int i) { return ColTwB<LOG_H>::pair_a(strip, i); }, lc);
 #pragma unroll
-        for (int kk = 0; kk < H; ++kk) acc[kk] += shoup_mul(x[kk], sc, sc_sh, lc.q);  // canonical, as the per-client pass stores it
+        for (int kk = 0; kk < H; ++kk) acc[kk] += canon_inverse_round(x[kk], lc, AR == AR_PM);  // the per-client pass's stored word
     }
     u64 *dst = psum + off;
 #pragma unroll

@@ -297,6 +297,44 @@ BaseConvTable ParamSet::moddown_table(uint32_t nl) const {
     return make_table(moduli, src, dst);
 }
 
+std::vector<u64> hat_as_doubles(const BaseConvTable &t, const std::vector<u64> &moduli) {
+    const size_t cnt = t.hat.size(), n_out = t.dst.size();
+    std::vector<u64> v(2 * cnt + 2 * n_out);
+    auto put = [&](size_t at, u64 h, u64 q) {
+        const double hd = (double)h, hq = (double)((long double)h / (long double)q);
+        std::memcpy(&v[at], &hd, 8);
+        return hq;
+    };
+    for (size_t e = 0; e < cnt; ++e) {
+        const double hq = put(e, t.hat[e], moduli[t.dst[e % n_out]]);
+        std::memcpy(&v[cnt + e], &hq, 8);
+    }
+    for (size_t j = 0; j < n_out; ++j) {
+        const u64 q = moduli[t.dst[j]];
+        const double hq = put(2 * cnt + j, h_mulmod(t.hat[j], ((u64)1 << 30) % q, q), q);
+        std::memcpy(&v[2 * cnt + n_out + j], &hq, 8);
+    }
+    return v;
+}
+
+u64 ParamSet::moddown_scale(uint32_t k) const {
+    std::vector<uint32_t> src;
+    for (uint32_t i = 0; i < K; ++i) src.push_back(L + i);
+    const u64 p = moduli[L + k];
+    return h_mulmod(limb[L + k].ninv, h_invmod(product_mod(moduli, src, (int)k, p), p), p);
+}
+
+BaseConvTable ParamSet::modup_table_pscaled(uint32_t nl, uint32_t part) const {
+    BaseConvTable t = modup_table(nl, part);
+    const size_t ni = t.src.size(), no = t.dst.size();
+    for (size_t j = 0; j < no; ++j) {
+        if (t.dst[j] < L) continue;
+        const u64 p = moduli[t.dst[j]], sc = moddown_scale(t.dst[j] - L);
+        for (size_t i = 0; i < ni; ++i) t.hat[i * no + j] = h_mulmod(t.hat[i * no + j], sc, p);
+    }
+    return t;
+}
+
 u64 ParamSet::p_mod(uint32_t id) const {
     u64 q = moduli[id], acc = 1;
     for (uint32_t k = 0; k < K; ++k) acc = h_mulmod(acc, moduli[L + k] % q, q);

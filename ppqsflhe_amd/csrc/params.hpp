@@ -41,6 +41,11 @@ struct BaseConvTable {
     std::vector<u64> hat;        // [S/s_i]_{t_j}, row-major [i][j]
 };
 
+// The fp64 form of a conversion matrix, as bit patterns of doubles: [S/s_i]_t and [S/s_i]_t / t, [n_in][n_out] each, then
+// for source 0 alone [S/s_0 * 2^30]_t and its quotient by t, [n_out] each -- a packed 60-bit source x = lo + 2^30 hi
+// meets an fp64-class target as lo [S/s_0]_t + hi [S/s_0 2^30]_t, two exact FMA products of 30-bit factors.
+std::vector<u64> hat_as_doubles(const BaseConvTable &t, const std::vector<u64> &moduli);
+
 struct ParamSet {
     uint32_t log_n = 0, n = 0;
     uint32_t L = 0, K = 0, D = 0;  // #Q limbs, #P limbs, L+K
@@ -69,6 +74,12 @@ struct ParamSet {
     BaseConvTable modup_table(uint32_t nl, uint32_t part) const;
     // ModDown table: P -> first nl Q limbs
     BaseConvTable moddown_table(uint32_t nl) const;
+    // N^-1 [(P/p_k)^-1]_{p_k}: what the inverse transform ahead of ModDown's conversion scales P limb k by
+    u64 moddown_scale(uint32_t k) const;
+    // modup_table with the constants of the P targets multiplied by moddown_scale: [S/s_i * sc_k]_{p_k}.  Everything
+    // between ModUp's conversion into a P limb and ModDown's conversion out of it is linear mod p_k, so a flow that
+    // converts with this table needs no scaling in its inverse transform of the P limbs.  Q targets are unchanged.
+    BaseConvTable modup_table_pscaled(uint32_t nl, uint32_t part) const;
     // [P^-1]_{q_i} and [P]_{q_i}
     u64 p_inv_mod(uint32_t limb_id) const;
     u64 p_mod(uint32_t limb_id) const;
