@@ -203,6 +203,12 @@ int mkckks_reencrypt_sum_batch(mkckks_ctx *c, const uint64_t *d_cts, const uint6
  * force a form, any other value chooses by grid size.  A pure function (no context, no device); both forms give the same
  * bits. */
 int mkckks_q0_walk_choice(uint32_t row_tiles, uint32_t n_int_q, uint32_t n_idx, int mode);
+/* How many fp64-class ModUp targets of a digit whose sources are all fp64-class are converted inside the inverse column
+ * pass of those sources instead of by the conversion kernels: the digit has n_fp_targets of them, and the call's grid
+ * for that pass is grid = polynomials x such digits x column tiles.  mode is the switch MKCKKS_ICOL_CONV: 0..3 force
+ * that many (as far as the digit has them), any other value chooses.  A pure function (no context, no device); every
+ * choice gives the same bits. */
+uint32_t mkckks_icol_conv_targets(uint32_t n_fp_targets, uint64_t grid, int mode);
 /* ---- weighted aggregation: sum_c w_c * x_c in place of the plain mean -----------------------------------------------
  * The weighted form of the server loop (ReEncrypt x n, then per client cc->EvalMult(ct, w_c) as at
  * aggregateEncryptedWeights.cpp:82-83, then the EvalAdd chain), with the weights folded into what the merged n-client

@@ -93,6 +93,7 @@ SYMBOLS = {
     "mkckks_combine_key_shares": (_int, [_vp, _vp, _vp, _vp, _u32, _u32]),
     "mkckks_lagrange_at_zero": (_int, [_vp, _vp, _u32, _vp]),
     "mkckks_q0_walk_choice": (_int, [_u32, _u32, _u32, _int]),
+    "mkckks_icol_conv_targets": (_u32, [_u32, C.c_uint64, _int]),
     "mkckks_encrypt_batch": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32]),
     "mkckks_lift_ntt_batch": (_int, [_vp, _vp, _vp, _u32, _u32]),
     "mkckks_decrypt_batch": (_int, [_vp, _vp, _vp, _vp, _u32, _u32]),

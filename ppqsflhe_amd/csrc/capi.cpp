@@ -335,6 +335,9 @@ int mkckks_reencrypt_sum_batch(mkckks_ctx *c, const uint64_t *cts, const uint64_
 int mkckks_q0_walk_choice(uint32_t row_tiles, uint32_t n_int_q, uint32_t n_idx, int mode) {
     return mk::q0_walk_fused(row_tiles, n_int_q, n_idx, mode) ? 1 : 0;
 }
+uint32_t mkckks_icol_conv_targets(uint32_t n_fp_targets, uint64_t grid, int mode) {
+    return mk::icol_conv_targets(n_fp_targets, grid, mode);
+}
 int mkckks_scale_evk_batch(mkckks_ctx *c, const uint64_t *d_evk_in, uint64_t *d_evk_out, uint32_t n_keys,
                            const double *h_weights, uint32_t sf_level) {
     return guarded([&] {

@@ -24,6 +24,7 @@
 #include "arith_probe_kernels.hpp"
 #include "../../include/mkckks.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <type_traits>
@@ -616,6 +617,9 @@ Knobs Knobs::from_env() {
         if (!std::strcmp(e, "0")) k.plain_fused = 0;
         else if (!std::strcmp(e, "1")) k.plain_fused = 1;
     }
+    if (const char *e = std::getenv("MKCKKS_ICOL_CONV")) {
+        if (e[0] >= '0' && e[0] <= '3' && !e[1]) k.icol_conv = e[0] - '0';
+    }
     return k;
 }
 
@@ -1045,11 +1049,14 @@ static uint32_t row_tiles(const NttTables &T) { return (1u << T.log_r1) / (256u 
 
 template <bool INV>
 static void launch_col(const NttIo &io0, const NttTables &T, uint32_t n_polys, const u64 *scale, const u64 *scale_sh,
-                       hipStream_t s, int pack = 0) {
+                       hipStream_t s, int pack = 0, unsigned long long skip = 0) {  // skip: slots another kernel transforms
     const uint32_t r1 = 1u << T.log_r1, r2 = 1u << T.log_r2;
     const bool radix = dispatch<2, 3, 4>(fast_log_h(T.log_r1, r2), [&](auto log_h) {
         constexpr int LOG_H = decltype(log_h)::value;
-        for_each_class(T, slot_classes(io0, T), [&](auto ar, unsigned long long mask, uint32_t nsel) {
+        ClassMasks m = slot_classes(io0, T);
+        m.integer &= ~skip;
+        m.fp &= ~skip;
+        for_each_class(T, m, [&](auto ar, unsigned long long mask, uint32_t nsel) {
             NttIo io = io0;
             io.slot_mask = mask;
             io.nsel = nsel;
@@ -1058,7 +1065,7 @@ static void launch_col(const NttIo &io0, const NttTables &T, uint32_t n_polys, c
         });
     });
     if (radix) return;
-    if (pack) throw std::logic_error("packed output needs the radix column kernel");
+    if (pack || skip) throw std::logic_error("packed output needs the radix column kernel");
     k_ntt_col<INV><<<dim3(r2 / NTT_COLS, n_polys * io0.nslots), NTT_THREADS, (size_t)r1 * NTT_COLS * sizeof(u64), s>>>(
         io0, T, scale, scale_sh);
 }
@@ -1090,7 +1097,7 @@ static void launch_row(const NttIo &io0, const NttTables &T, uint32_t n_polys, c
 
 // two-pass launcher: reads `io.in`, leaves the result in `io.out` (may be the same buffer)
 static void ntt_passes(NttIo io, const NttTables &T, uint32_t n_polys, bool inverse, const u64 *scale,
-                       const u64 *scale_sh, hipStream_t s, int pack = 0) {
+                       const u64 *scale_sh, hipStream_t s, int pack = 0, unsigned long long icol_skip = 0) {
     if (n_polys == 0 || io.nslots == 0) return;
     NttIo second = io;  // second pass runs in place on the output
     second.in_group = 0;
@@ -1103,7 +1110,7 @@ static void ntt_passes(NttIo io, const NttTables &T, uint32_t n_polys, bool inve
         launch_row<false>(second, T, n_polys, none, s);
     } else {
         launch_row<true>(io, T, n_polys, none, s);
-        launch_col<true>(second, T, n_polys, scale, scale_sh, s, pack);
+        launch_col<true>(second, T, n_polys, scale, scale_sh, s, pack, icol_skip);
     }
     MK_HIP(hipGetLastError());
 }
@@ -1111,8 +1118,12 @@ static void ntt_passes(NttIo io, const NttTables &T, uint32_t n_polys, bool inve
 // base conversion fused into the forward column pass of every converted limb (k_conv_col); false when the
 // column pass of this ring size has no radix kernel (the caller then runs k_baseconv + a plain column pass)
 template <int LOG_H, int N_IN, int SRCMODE>
-static void launch_conv_col_n(const ConvIo &io0, const NttTables &T, const DevConv &cv, hipStream_t s, unsigned classes) {
-    for_each_class(T, target_classes(cv, T, classes), [&](auto ar, unsigned long long mask, uint32_t nsel) {
+static void launch_conv_col_n(const ConvIo &io0, const NttTables &T, const DevConv &cv, hipStream_t s, unsigned classes,
+                              unsigned long long done) {
+    ClassMasks m = target_classes(cv, T, classes);
+    m.integer &= ~done;
+    m.fp &= ~done;
+    for_each_class(T, m, [&](auto ar, unsigned long long mask, uint32_t nsel) {
         ConvIo io = io0;
         io.target_mask = mask;
         io.nsel = nsel;
@@ -1128,26 +1139,41 @@ static void launch_conv_col_n(const ConvIo &io0, const NttTables &T, const DevCo
 }
 template <int LOG_H, int N_IN>
 static void launch_conv_col_m(const ConvIo &io, const NttTables &T, const DevConv &cv, hipStream_t s, int srcmode,
-                              unsigned classes) {
+                              unsigned classes, unsigned long long done) {
     if constexpr (N_IN <= 4 && LOG_H >= 3) {
-        if (srcmode == 1) return launch_conv_col_n<LOG_H, N_IN, 1>(io, T, cv, s, classes);
-        if (srcmode == 2) return launch_conv_col_n<LOG_H, N_IN, (N_IN > 1 ? 2 : 0)>(io, T, cv, s, classes);
+        if (srcmode == 1) return launch_conv_col_n<LOG_H, N_IN, 1>(io, T, cv, s, classes, done);
+        if (srcmode == 2) return launch_conv_col_n<LOG_H, N_IN, (N_IN > 1 ? 2 : 0)>(io, T, cv, s, classes, done);
     }
     if (srcmode != 0) throw std::logic_error("double conversion sources: unsupported shape");
-    launch_conv_col_n<LOG_H, N_IN, 0>(io, T, cv, s, classes);
+    launch_conv_col_n<LOG_H, N_IN, 0>(io, T, cv, s, classes, done);
 }
 // srcmode: form of the sources in io.in (see src_is_double): 0 = packed 30-bit halves, 1 / 2 = doubles
-// classes: bit 0 integer-class targets, bit 1 fp64-class targets
+// classes: bit 0 integer-class targets, bit 1 fp64-class targets; done: targets (indices into cv.dst_*) already written
 static bool launch_conv_col(const ConvIo &io, const NttTables &T, const DevConv &cv, hipStream_t s, int srcmode = 0,
-                            unsigned classes = 3) {
+                            unsigned classes = 3, unsigned long long done = 0) {
     const bool radix = dispatch<2, 3, 4>(fast_log_h(T.log_r1, 1u << T.log_r2), [&](auto log_h) {
         if (!dispatch<1, 2, 3, 4, 5, 6, 7, 8>(cv.n_in, [&](auto n_in) {
-                launch_conv_col_m<decltype(log_h)::value, decltype(n_in)::value>(io, T, cv, s, srcmode, classes);
+                launch_conv_col_m<decltype(log_h)::value, decltype(n_in)::value>(io, T, cv, s, srcmode, classes, done);
             }))
             throw std::invalid_argument("base conversion fan-in unsupported");
     });
     if (radix) MK_HIP(hipGetLastError());
     return radix;
+}
+// the inverse column pass of every fp64-class limb of c1 in one launch, digit by digit, with up to `nt_max` fp64-class
+// targets of a digit converted on the way (k_icol_conv; io.job[])
+static void launch_icol_conv(const IcolConvIo &io, const NttTables &T, uint32_t nt_max, const u64 *scale, const u64 *scale_sh,
+                             hipStream_t s) {
+    if (!dispatch<3, 4>(fast_log_h(T.log_r1, 1u << T.log_r2), [&](auto log_h) {
+            constexpr int LOG_H = decltype(log_h)::value;
+            if (!dispatch<1, 2, 3>(nt_max, [&](auto nt_c) {
+                    k_icol_conv<LOG_H, decltype(nt_c)::value>
+                        <<<dim3(io.njobs * io.items * col_tiles<LOG_H>(T)), NTT_THREADS, 0, s>>>(io, T, scale, scale_sh);
+                }))
+                throw std::logic_error("k_icol_conv takes 1 to 3 targets");
+        }))
+        throw std::logic_error("k_icol_conv needs 64- or 256-point columns");
+    MK_HIP(hipGetLastError());
 }
 // the group's ONE ModDown conversion (k_conv_col_psum), one instance per arithmetic class of the targets
 template <int LOG_H, int N_IN>
@@ -1515,12 +1541,71 @@ void Engine::modup_core(const u64 *c1, size_t c1_stride, u64 *coef, u64 *dig, ui
         const DevConv &cv = modup_conv(nl, part, p_scaled);
         if (conv_src_mode(cv) < 0 || (conv_src_mode(cv) != 0 && cv.n_in > 4)) doubles = false;
     }
-    ntt_passes(s1, tabs_, cnt, true, fold, fold + D, stream_, fused ? (doubles ? 2 : 1) : 0);
+    // digits whose sources are all fp64-class: their inverse column pass converts some of their fp64-class targets on the
+    // way (how many: icol_conv_targets).  Where a digit takes part, ONE launch of k_icol_conv runs the inverse column pass
+    // of every fp64-class limb (a job per digit, the longest first) and the fp64 instance of the plain pass is not launched
+    std::vector<unsigned long long> icol_done(nparts, 0);  // per digit: the targets k_icol_conv writes
+    IcolConvIo icol{coef, dig, (size_t)nl * n, dstride, cnt, 0, {}};
+    uint32_t icol_nt_max = 0;
+    unsigned long long icol_slots = 0;
+    if (doubles && knobs_.icol_conv != 0 && nparts <= (uint32_t)ICOL_MAX_JOBS) {
+        std::vector<unsigned long long> fp_targets(nparts, 0);
+        uint32_t eligible = 0;
+        for (uint32_t part = 0; part < nparts; ++part) {
+            const DevConv &cv = modup_conv(nl, part, p_scaled);
+            if (conv_src_mode(cv) != 1) continue;
+            fp_targets[part] = target_classes(cv, tabs_, 2).fp;
+            eligible += fp_targets[part] != 0;
+        }
+        const uint64_t grid = (uint64_t)cnt * eligible * ((1u << tabs_.log_r2) / (256u >> (tabs_.log_r1 / 2)));
+        std::vector<IcolJob> jobs;
+        for (uint32_t part = 0; part < nparts; ++part) {
+            const DevConv &cv = modup_conv(nl, part, p_scaled);
+            IcolJob jb{};
+            uint32_t first_fp = 0;  // index in cv of the job's first source: its rows of the constant tables start there
+            for (uint32_t i = 0; i < cv.n_in; ++i)
+                if (fp_of_[cv.src_id[i]]) {
+                    if (!jb.n_in) first_fp = i;
+                    jb.src_id[jb.n_in] = cv.src_id[i];
+                    jb.src_slot[jb.n_in++] = cv.src_slot[i];
+                    icol_slots |= 1ull << cv.src_slot[i];
+                }
+            if (!jb.n_in) continue;
+            unsigned long long m = fp_targets[part];
+            uint32_t nt = icol_conv_targets((uint32_t)__builtin_popcountll(m), grid, knobs_.icol_conv);
+            for (; nt; --nt, m &= m - 1) icol_done[part] |= m & (~m + 1);  // the first nt of them
+            for (unsigned long long d = icol_done[part]; d; d &= d - 1) {
+                const uint32_t t = (uint32_t)__builtin_ctzll(d);
+                jb.dst_id[jb.nt] = cv.dst_id[t];
+                jb.dst_slot[jb.nt] = cv.dst_slot[t];
+                jb.hat_d[jb.nt] = cv.hat_d + t;
+                jb.hatq_d[jb.nt++] = cv.hatq_d + t;
+            }
+            for (uint32_t t = jb.nt; t < 3; ++t) {  // the kernel loads every target's constants: valid ones, sums dropped
+                jb.dst_id[t] = jb.src_id[0];
+                jb.hat_d[t] = cv.hat_d + (size_t)first_fp * cv.n_out;
+                jb.hatq_d[t] = cv.hatq_d + (size_t)first_fp * cv.n_out;
+            }
+            jb.hat_stride = cv.n_out;
+            jb.dig_off = (size_t)part * ext * n;
+            icol_nt_max = std::max(icol_nt_max, jb.nt);
+            jobs.push_back(jb);
+        }
+        if (icol_nt_max) {
+            std::stable_sort(jobs.begin(), jobs.end(),
+                             [](const IcolJob &a, const IcolJob &b) { return a.n_in + a.nt > b.n_in + b.nt; });
+            for (const IcolJob &jb : jobs) icol.job[icol.njobs++] = jb;
+        } else {
+            icol_slots = 0;
+        }
+    }
+    ntt_passes(s1, tabs_, cnt, true, fold, fold + D, stream_, fused ? (doubles ? 2 : 1) : 0, icol_slots);
+    if (icol_slots) launch_icol_conv(icol, tabs_, icol_nt_max, fold, fold + D, stream_);
     for (uint32_t part = 0; part < nparts && fused; ++part) {
         // S2+S3a: base conversion fused into the column pass of each complement limb
         ConvIo io{coef, dig + (size_t)part * ext * n, (size_t)nl * n, dstride, cnt, 0, 0};
         const DevConv &cv = modup_conv(nl, part, p_scaled);
-        launch_conv_col(io, tabs_, cv, stream_, doubles ? conv_src_mode(cv) : 0);
+        launch_conv_col(io, tabs_, cv, stream_, doubles ? conv_src_mode(cv) : 0, 3, icol_done[part]);
     }
     if (fused) {
         // S3b: one row pass over every converted limb of every digit (own limbs skipped)

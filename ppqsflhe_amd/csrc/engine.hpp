@@ -70,6 +70,9 @@ struct Knobs {
     int plain_fused = 2;         // MKCKKS_PLAIN_FUSED=0/1: mult_plain_rescale as the composition (k_mul_plain + rescale) or fused
                                  // into the rescale's two row passes; default: fused wherever the plain rescale is
                                  // (profiles/slot_weights_ab.txt)
+    int icol_conv = -1;          // MKCKKS_ICOL_CONV=0/1/2/3/auto: fp64-class ModUp targets of an all-fp64 digit converted inside the
+                                 // inverse column pass of its sources (k_icol_conv); 0: none, 1..3: that many wherever the digit
+                                 // has them, default: icol_conv_targets (profiles/icol_conv_ab.txt)
     static Knobs from_env();
 };
 
@@ -82,6 +85,21 @@ constexpr uint32_t Q0_WALK_MIN_GRID = 512;
 inline bool q0_walk_fused(uint32_t tiles, uint32_t nsel, uint32_t cnt, int mode) {
     if (mode == 0 || mode == 1) return mode == 1;
     return (uint64_t)tiles * nsel * cnt >= Q0_WALK_MIN_GRID;
+}
+
+// How many fp64-class targets of a digit with `n_fp` of them k_icol_conv converts inside the inverse column pass of the
+// digit's sources, in a call whose k_icol_conv grid (items x such digits x column tiles) is `grid`.  mode 0..3 forces
+// that many (as far as the digit has them); anything else chooses: the largest count up to ICOL_CONV_AUTO_MAX that leaves
+// k_conv_col2 an even number of targets (no half-empty last workgroup) -- with the shipped maximum of 1 that is the odd
+// target of a digit with an odd count -- and none where the grid would not fill the chip: a workgroup walks the digit's
+// sources one after the other, like the client walk of q0_walk_fused (profiles/icol_conv_ab.txt).
+constexpr uint32_t ICOL_CONV_MAX = 3, ICOL_CONV_AUTO_MAX = 1, ICOL_CONV_MIN_GRID = 2048;  // two and three targets measured no gain
+inline uint32_t icol_conv_targets(uint32_t n_fp, uint64_t grid, int mode) {
+    if (mode >= 0 && mode <= (int)ICOL_CONV_MAX) return (uint32_t)mode < n_fp ? (uint32_t)mode : n_fp;
+    if (grid < ICOL_CONV_MIN_GRID) return 0;
+    for (uint32_t nt = ICOL_CONV_AUTO_MAX < n_fp ? ICOL_CONV_AUTO_MAX : n_fp; nt >= 1; --nt)
+        if ((n_fp - nt) % 2 == 0) return nt;
+    return 0;
 }
 
 class Engine {

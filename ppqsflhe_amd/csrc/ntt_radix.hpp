@@ -963,6 +963,128 @@ __global__ __launch_bounds__(NTT_THREADS, 3) void k_conv_col2(ConvIo io, NttTabl
     col_forward_finish<LOG_H, AR>(xb, lds, twb, twb_sh, lb, j, c, dst, r2);
 }
 
+// ---- ModUp targets converted inside the inverse column pass of their sources -------------------------------------------
+// k_icol_conv: the inverse column pass of EVERY fp64-class limb of c1 in one launch.  A workgroup owns (digit, item,
+// column tile) and walks the fp64-class source limbs of its digit one after the other (at most 4).  After its second
+// round thread (j, c) holds rows j + H k of column c -- the layout k_conv_col2 loads and col_forward_finish takes -- so
+// every canonical double is stored to `coef` exactly as k_ntt_col_r<.., true, AR_FP> with pack == 2 stores it and, on a
+// digit whose sources are all fp64-class (SRCMODE 1), added times [S/s_i]_t mod t into the running sums of up to NT
+// fp64-class targets of the digit; only the sums (2 H registers per target) live across the source loop.  After the last
+// source each target goes through the tail of conv_output + k_conv_col2: fp_reduce, forward column pass, store into the
+// digit buffer.  Same helpers on the same operands in the same order: the words are the ones the two kernels write.
+// The digits are jobs of one grid, the longest first (sources + targets), so that the short ones fill the tail.
+// a workgroup-uniform double that was loaded through a pointer the compiler cannot prove uniform: into scalar registers
+MK_D double uniform_d(double v) {
+    const u64 b = dbits(v);
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)b), hi = __builtin_amdgcn_readfirstlane((uint32_t)(b >> 32));
+    return bitsd(((u64)hi << 32) | lo);
+}
+struct IcolJob {
+    uint32_t n_in, nt;                 // fp64-class sources of the digit; targets converted here (0: inverse pass only)
+    uint32_t src_id[4], src_slot[4];   // limb id and slot in `coef` of each source
+    uint32_t dst_id[3], dst_slot[3];   // limb id and slot in the digit's [ext][N] block of each target (t >= nt: any valid id)
+    const double *hat_d[3], *hatq_d[3];  // per target: [S/s_i]_t and its quotient by t, source i at [i * hat_stride]
+    uint32_t hat_stride;
+    size_t dig_off;                    // the digit's block inside an item of the digit buffer
+};
+constexpr int ICOL_MAX_JOBS = 6;
+struct IcolConvIo {
+    u64 *coef;  // [items][nl][N]: output of the inverse row pass, replaced in place by the coefficient-form limbs
+    u64 *dig;   // [items][nparts][ext][N]
+    size_t coef_stride, dig_stride;
+    uint32_t items, njobs;
+    IcolJob job[ICOL_MAX_JOBS];
+};
+#ifndef MK_ICOL_CONV_WAVES3
+#define MK_ICOL_CONV_WAVES3 2  // three targets hold 96 registers of sums: no scratch at 2 waves per SIMD only
+#endif
+template <int LOG_H, int NT>
+__global__ __launch_bounds__(NTT_THREADS, NT == 3 ? MK_ICOL_CONV_WAVES3 : (NT == 2 ? 3 : 4)) void k_icol_conv(IcolConvIo io, NttTables T,
+                                                                                                          const u64 *scale,
+                                                                                                          const u64 *scale_sh) {
+    using TL = ColTile<LOG_H>;
+    constexpr int H = TL::H, S = TL::S;
+    static_assert(NT >= 1 && NT <= 3, "1..3 targets");
+    __shared__ u64 lds[TL::WORDS + ColTwB<LOG_H>::WORDS];
+    const uint32_t n = 1u << T.log_n, r2 = 1u << T.log_r2, tiles = r2 / S;
+    const uint32_t groups = io.items * tiles;
+    const uint32_t jidx = blockIdx.x / groups;  // workgroup-uniform; < io.njobs by the grid
+    const IcolJob &jb = io.job[jidx];
+    uint32_t grp, mem, item, tile;
+    group_member(blockIdx.x % groups, groups, 1, T.cu_affine, grp, mem);  // the XCD that k_conv_col2 reads this source tile on
+    conv_item_tile(grp, groups, io.items, tiles, item, tile);
+    const u64 *strip = lds + TL::WORDS;
+    const uint32_t nt = jb.nt, n_in = jb.n_in;
+    double qt[NT], acc[NT][H];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+        qt[t] = T.limb[jb.dst_id[t]].qd;
+#pragma unroll
+        for (int k = 0; k < H; ++k) acc[t][k] = 0.0;
+    }
+#pragma unroll 1
+    for (uint32_t i = 0; i < n_in; ++i) {
+        // nothing but the sums is meant to live across the source loop (see k_icol_sum)
+        const uint32_t id = jb.src_id[i];
+        const LimbConst lc = T.limb[id];
+        uint32_t r2v = r2, tid = threadIdx.x;
+        asm volatile("" : "+s"(r2v));
+        asm volatile("" : "+v"(tid));  // the thread's tile coordinates and addresses are rebuilt per limb, not kept (4 registers)
+        const int c = tid % S, j = tid / S;
+        u64 *p = io.coef + (size_t)item * io.coef_stride + (size_t)jb.src_slot[i] * n + tile * S + c;
+        if (i) __syncthreads();  // the previous limb's exchange and twiddle strip are read out
+        ColTwB<LOG_H>::stage(lds + TL::WORDS, T.itw + (size_t)id * n, T.itw_sh + (size_t)id * n);
+        u64 x[H];
+#pragma unroll
+        for (int k = 0; k < H; ++k) x[k] = ld_pass(p + (uint32_t)(H * j + k) * r2v);  // from the row pass: doubles
+        wave_lds_sync();  // the strip is this wave's own
+        radix_inverse_staged<LOG_H, AR_FP>(x, [&](int e) { return ColTwB<LOG_H>::pair_b(strip, j, e); }, lc);
+#pragma unroll
+        for (int k = 0; k < H; ++k) lds[TL::at(j, k, c)] = x[k];
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < H; ++k) x[k] = lds[TL::at(k, j, c)];
+        radix_inverse_staged<LOG_H, AR_FP>(x, [&](int e) { return ColTwB<LOG_H>::pair_a(strip, e); }, lc);
+        const double sc = bitsd(scale[id]), sc_q = bitsd(scale_sh[id]);
+        double hd[NT], hq[NT];
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            hd[t] = uniform_d(jb.hat_d[t][i * jb.hat_stride]);  // unconditional (a guarded load costs 40 registers): the host points
+            hq[t] = uniform_d(jb.hatq_d[t][i * jb.hat_stride]);  // the unused targets of a job at valid constants, their sums are dropped
+        }
+#pragma unroll
+        for (int k = 0; k < H; ++k) {
+            double sd = fp_mulmod(bitsd(x[k]), sc, sc_q, lc.qd);  // k_ntt_col_r's pack == 2 word
+            sd = sd < 0.0 ? sd + lc.qd : sd;
+            st_pass(p + (uint32_t)(j + H * k) * r2v, dbits(sd));
+            // conv_output's addend i (a job with fewer targets adds exact zeros: no branch inside the pinned schedule)
+#pragma unroll
+            for (int t = 0; t < NT; ++t) acc[t][k] += fp_mulmod(sd, hd[t], hq[t], qt[t]);
+            // the sums are brought up to date here: otherwise the products sink to the targets' first butterflies and
+            // every limb's scaled words stay live
+#pragma unroll
+            for (int t = 0; t < NT; ++t) asm volatile("" : "+v"(acc[t][k]));
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+        if ((uint32_t)t >= nt) break;  // workgroup-uniform
+        const uint32_t idt = jb.dst_id[t];
+        const LimbConst lt = T.limb[idt];
+        const int c = threadIdx.x % S, j = threadIdx.x / S;
+        u64 x[H];
+#pragma unroll
+        for (int k = 0; k < H; ++k) x[k] = dbits(fp_reduce(acc[t][k], lt.qd, lt.qinv));  // conv_output's last step
+        __syncthreads();  // the LDS tile and the strips change hands
+        // a later target's twiddle loads must not be hoisted above the earlier passes: opaque table pointers (k_conv_col2)
+        const u64 *tw = T.tw + (size_t)idt * n, *tw_sh = T.tw_sh + (size_t)idt * n;
+        asm volatile("" : "+s"(tw), "+s"(tw_sh));
+        u64 *dst = io.dig + (size_t)item * io.dig_stride + jb.dig_off + (size_t)jb.dst_slot[t] * n + tile * S + c;
+        col_forward_finish<LOG_H, AR_FP>(x, lds, tw, tw_sh, lt, j, c, dst, r2);
+    }
+}
+
 // ---- ApproxModDown's conversion P -> Q_l for a whole group of clients at once ------------------------------------------
 // The reference converts every client's key-switch result on its own (ApproxModDown inside each ReEncrypt) and adds the
 // re-encryptions afterwards (EvalAdd).  With x_{c,k} the canonical residue mod p_k of client c's coefficient (the inverse
