@@ -328,6 +328,50 @@ int mkckks_keygen(mkckks_ctx *c, const int8_t *d_s, const uint64_t *d_a, const i
 int mkckks_rekeygen(mkckks_ctx *c, const int8_t *d_s_old, const uint64_t *d_pk_new, const int8_t *d_u,
                     const int32_t *d_e0, const int32_t *d_e1, uint64_t *d_evk);
 
+/* ==== slot rotations and slot sums: cc->EvalRotateKeyGen / cc->EvalRotate / cc->EvalSumKeyGen / cc->EvalSum ============
+ * Upstream CryptoContext calls the reference never makes: every operation of its mains leaves a slot where the client
+ * put it.  With them a ciphertext's slots can be moved, summed, and (mkckks_mult_plain_rescale_batch first) turned into
+ * an encrypted inner product with a public vector.
+ * Automorphism: for odd g < 2N, sigma_g(a)(X) = a(X^g).  In EVALUATION format (X[i] = a(psi^(2 brev(i) + 1))) it is a
+ * gather that is the same for every limb: sigma_g(X)[i] = X[src(i)] with 2 brev(src(i)) + 1 = (2 brev(i) + 1) g mod 2N.
+ * On a ternary secret in COEFFICIENT format coefficient k goes to position k g mod 2N; a position at or above N means
+ * position - N with the sign flipped.  Slot j sits at zeta^(5^j), so g = 5^r mod 2N rotates LEFT by r:
+ * out[j] = in[(j + r) mod N/2]; a negative r is the inverse element; g = MKCKKS_GALOIS_CONJ(N) = 2N - 1 conjugates.
+ * Refusals of all compute calls below: MKCKKS_E_INVALID for an even g or g >= 2N, null pointers, nl outside [1, L],
+ * an output that overlaps its input; a zero count is a no-op; a host-only context gives MKCKKS_E_NODEVICE.  The
+ * polynomial arrays must be 16-byte aligned (every allocation is; an odd word offset into one is not): MKCKKS_E_INVALID.
+ *
+ * (cc->EvalRotate's index -> element map, upstream FindAutomorphismIndex2nComplex) host only, works on a device = -1
+ * context: *g = 5^step mod 2N; step < 0 gives the inverse element, step 0 gives 1. */
+#define MKCKKS_GALOIS_CONJ(ring_dim) (2u * (ring_dim) - 1u)
+int mkckks_galois_element(const mkckks_ctx *c, int32_t step, uint32_t *g);
+/* (cc->EvalRotate, the automorphism half: upstream DCRTPoly::AutomorphismTransform) d_out[p] = sigma_g(d_in[p]) on
+ * u64[n_polys][nl][N], EVALUATION, out of place.  No arithmetic: canonical residues stay canonical. */
+int mkckks_automorphism_batch(mkckks_ctx *c, const uint64_t *d_in, uint64_t *d_out, uint32_t n_polys, uint32_t nl, uint32_t g);
+/* (cc->EvalRotateKeyGen, the secret's half) d_out int8[N] = sigma_g(d_s), COEFFICIENT, signed; out of place. */
+int mkckks_automorphism_secret(mkckks_ctx *c, const int8_t *d_s, int8_t *d_out, uint32_t g);
+/* (cc->EvalRotateKeyGen / cc->EvalSumKeyGen for one element) The Galois key for g is the re-encryption key from
+ * sigma_g(s) to s: bit for bit mkckks_rekeygen(sigma_g(d_s), d_pk, d_u, d_e0, d_e1), same layouts and randomness
+ * arguments; d_pk is the public key of s; d_evk out u64[beta][2][D][N].  Generated by the OWNER of s (for the server's
+ * slot sums: the owner of the common-domain key).  A Galois key for a JOINT key needs a collective protocol, which this
+ * library does not have. */
+int mkckks_galois_keygen(mkckks_ctx *c, const int8_t *d_s, const uint64_t *d_pk, const int8_t *d_u, const int32_t *d_e0,
+                         const int32_t *d_e1, uint32_t g, uint64_t *d_evk);
+/* (cc->EvalRotate) d_out[b] = ReEncrypt((sigma_g(c0), sigma_g(c1)), d_evk): word for word what mkckks_reencrypt_batch
+ * returns on the permuted ciphertext.  d_ct, d_out u64[n_ct][2][nl][N], nl <= L (a partial last digit included); d_evk
+ * from mkckks_galois_keygen with the SAME g (another key gives noise and no error).  Both components are permuted
+ * straight into d_out and the key switch runs there in place: one read and one write of the ciphertext more than
+ * mkckks_reencrypt_batch.  Noise: that of one re-encryption. */
+int mkckks_rotate_batch(mkckks_ctx *c, const uint64_t *d_ct, const uint64_t *d_evk, uint64_t *d_out, uint32_t n_ct, uint32_t nl,
+                        uint32_t g);
+/* (cc->EvalSum) d_out = d_ct, then for k = 0 .. log2(span) - 1 in that order: d_out = d_out + Rotate(d_out, 5^(2^k))
+ * with key k of d_evks u64[log2 span][beta][2][D][N] (key k for step 2^k; not read when span = 1, which copies the
+ * input).  Slot j then holds in[j] + ... + in[j + span - 1] (indices mod N/2); with span = N/2 every slot holds the sum
+ * of all slots.  span: a power of two in [1, N/2], else MKCKKS_E_INVALID.  Bit-identical to the loop of
+ * mkckks_rotate_batch and mkckks_eval_add_batch.  Noise: log2(span) re-encryptions, each doubled by the steps after it. */
+int mkckks_slot_sum_batch(mkckks_ctx *c, const uint64_t *d_ct, const uint64_t *d_evks, uint64_t *d_out, uint32_t n_ct,
+                          uint32_t nl, uint32_t span);
+
 /* ---- cc->Encrypt(pk, pt)  (client/src/encryptModelWeights.cpp:83,91,110) --
  * d_pt u64[n_ct][nl][N] encoded plaintexts (EVALUATION); v int8[n_ct][N];
  * e0,e1 int32[n_ct][N]; out u64[n_ct][2][nl][N]. */

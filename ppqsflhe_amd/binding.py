@@ -85,6 +85,12 @@ SYMBOLS = {
     "mkckks_moddown_batch": (_int, [_vp, _vp, _vp, _u32, _u32]),
     "mkckks_keygen": (_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "mkckks_rekeygen": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mkckks_galois_element": (_int, [_vp, C.c_int32, C.POINTER(_u32)]),
+    "mkckks_automorphism_batch": (_int, [_vp, _vp, _vp, _u32, _u32, _u32]),
+    "mkckks_automorphism_secret": (_int, [_vp, _vp, _vp, _u32]),
+    "mkckks_galois_keygen": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp]),
+    "mkckks_rotate_batch": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u32]),
+    "mkckks_slot_sum_batch": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u32]),
     "mkckks_keygen_join": (_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "mkckks_partial_decrypt_batch": (_int, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _int]),
     "mkckks_fuse_shares_batch": (_int, [_vp, _vp, _vp, _u32, _u32, _u32]),
@@ -546,6 +552,35 @@ class Context:
 
     def rekeygen(self, s_old, pk_new, u, e0, e1, evk):
         self._check(self._L.mkckks_rekeygen(self._h, _ptr(s_old), _ptr(pk_new), _ptr(u), _ptr(e0), _ptr(e1), _ptr(evk)))
+
+    # ---- slot rotations (include/mkckks.h: "slot rotations and slot sums")
+    def galois_element(self, step):
+        """5^step mod 2N: the element that rotates the slots left by `step` (negative: right).  Host only."""
+        g = C.c_uint32()
+        self._check(self._L.mkckks_galois_element(self._h, int(step), C.byref(g)))
+        return g.value
+
+    @property
+    def galois_conj(self):
+        """MKCKKS_GALOIS_CONJ: 2N - 1, the element of the complex conjugation."""
+        return 2 * self.N - 1
+
+    def automorphism(self, inp, out, n_polys, nl, g):
+        self._check(self._L.mkckks_automorphism_batch(self._h, _ptr(inp), _ptr(out), n_polys, nl, g))
+
+    def automorphism_secret(self, s, out, g):
+        self._check(self._L.mkckks_automorphism_secret(self._h, _ptr(s), _ptr(out), g))
+
+    def galois_keygen(self, s, pk, u, e0, e1, g, evk):
+        """The Galois key for g: rekeygen(sigma_g(s), pk, u, e0, e1)."""
+        self._check(self._L.mkckks_galois_keygen(self._h, _ptr(s), _ptr(pk), _ptr(u), _ptr(e0), _ptr(e1), g, _ptr(evk)))
+
+    def rotate(self, ct, evk, out, n_ct, nl, g):
+        self._check(self._L.mkckks_rotate_batch(self._h, _ptr(ct), _ptr(evk), _ptr(out), n_ct, nl, g))
+
+    def slot_sum(self, ct, evks, out, n_ct, nl, span):
+        """out = ct + its rotations by 1 .. span - 1; evks [log2 span][beta][2][D][N], key k for step 2^k."""
+        self._check(self._L.mkckks_slot_sum_batch(self._h, _ptr(ct), _ptr(evks), _ptr(out), n_ct, nl, span))
 
     def encrypt(self, pk, pt, v, e0, e1, ct, n_ct, nl):
         self._check(self._L.mkckks_encrypt_batch(self._h, _ptr(pk), _ptr(pt), _ptr(v), _ptr(e0), _ptr(e1), _ptr(ct),

@@ -7,6 +7,7 @@
 #include "../../include/mkckks.h"
 #include "comm.hpp"
 #include "engine.hpp"
+#include "galois.hpp"
 
 struct mkckks_ctx {
     mk::Engine *eng;
@@ -418,6 +419,71 @@ int mkckks_rekeygen(mkckks_ctx *c, const int8_t *s_old, const uint64_t *pk_new, 
     return guarded([&] {
         need(c && s_old && pk_new && u && e0 && e1 && evk, "null argument");
         c->eng->rekeygen(s_old, pk_new, u, e0, e1, evk);
+    });
+}
+// ---- slot rotations: every refusal is decided here, before a device is asked for
+static void need_galois(const mk::ParamSet &ps, uint32_t g) {
+    need(mk::galois_valid(g, ps.log_n), "Galois element must be odd and below 2N");
+}
+static void need_apart(const void *in, const void *out, size_t bytes) {
+    const uintptr_t i = (uintptr_t)in, o = (uintptr_t)out;
+    need(!(o < i + bytes && i < o + bytes), "output overlaps input");
+}
+int mkckks_galois_element(const mkckks_ctx *c, int32_t step, uint32_t *g) {
+    return guarded([&] {
+        need(c && g, "null argument");
+        *g = mk::galois_element(step, c->eng->params().log_n);
+    });
+}
+int mkckks_automorphism_batch(mkckks_ctx *c, const uint64_t *in, uint64_t *out, uint32_t n_polys, uint32_t nl, uint32_t g) {
+    return guarded([&] {
+        need(c && in && out, "null argument");
+        const mk::ParamSet &ps = c->eng->params();
+        need(nl >= 1 && nl <= ps.L, "nl out of range");
+        need_galois(ps, g);
+        need_apart(in, out, (size_t)n_polys * nl * ps.n * sizeof(uint64_t));
+        if (!n_polys) return;
+        c->eng->automorphism(in, out, n_polys, nl, g);
+    });
+}
+int mkckks_automorphism_secret(mkckks_ctx *c, const int8_t *s, int8_t *out, uint32_t g) {
+    return guarded([&] {
+        need(c && s && out, "null argument");
+        need_galois(c->eng->params(), g);
+        need_apart(s, out, c->eng->params().n);
+        c->eng->automorphism_secret(s, out, g);
+    });
+}
+int mkckks_galois_keygen(mkckks_ctx *c, const int8_t *s, const uint64_t *pk, const int8_t *u, const int32_t *e0,
+                         const int32_t *e1, uint32_t g, uint64_t *evk) {
+    return guarded([&] {
+        need(c && s && pk && u && e0 && e1 && evk, "null argument");
+        need_galois(c->eng->params(), g);
+        c->eng->galois_keygen(s, pk, u, e0, e1, g, evk);
+    });
+}
+int mkckks_rotate_batch(mkckks_ctx *c, const uint64_t *ct, const uint64_t *evk, uint64_t *out, uint32_t n_ct, uint32_t nl,
+                        uint32_t g) {
+    return guarded([&] {
+        need(c && ct && evk && out, "null argument");
+        const mk::ParamSet &ps = c->eng->params();
+        need(nl >= 1 && nl <= ps.L, "nl out of range");
+        need_galois(ps, g);
+        need_apart(ct, out, (size_t)n_ct * 2 * nl * ps.n * sizeof(uint64_t));
+        if (!n_ct) return;
+        c->eng->rotate(ct, evk, out, n_ct, nl, g);
+    });
+}
+int mkckks_slot_sum_batch(mkckks_ctx *c, const uint64_t *ct, const uint64_t *evks, uint64_t *out, uint32_t n_ct, uint32_t nl,
+                          uint32_t span) {
+    return guarded([&] {
+        need(c && ct && out && (evks || span == 1), "null argument");
+        const mk::ParamSet &ps = c->eng->params();
+        need(nl >= 1 && nl <= ps.L, "nl out of range");
+        need(span >= 1 && !(span & (span - 1)) && span <= ps.n / 2, "span must be a power of two in [1, N/2]");
+        need_apart(ct, out, (size_t)n_ct * 2 * nl * ps.n * sizeof(uint64_t));
+        if (!n_ct) return;
+        c->eng->slot_sum(ct, evks, out, n_ct, nl, span);
     });
 }
 int mkckks_encrypt_batch(mkckks_ctx *c, const uint64_t *pk, const uint64_t *pt, const int8_t *v, const int32_t *e0,

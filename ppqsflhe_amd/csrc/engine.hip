@@ -20,6 +20,7 @@
 #include "qsum_kernels.hpp"
 #include "fanout_kernels.hpp"
 #include "codec_kernels.hpp"
+#include "galois_kernels.hpp"
 #include "sampler_kernels.hpp"
 #include "arith_probe_kernels.hpp"
 #include "../../include/mkckks.h"
@@ -734,7 +735,7 @@ Engine::~Engine() {
     (void)hipDeviceSynchronize();
     for (void *p : {(void *)d_limb_, (void *)d_tw_, (void *)d_tw_sh_, (void *)d_itw_, (void *)d_itw_sh_, (void *)ws_,
                     (void *)d_twb_, (void *)d_itwb_, (void *)d_stamps_,
-                    (void *)d_rot_, (void *)d_ksi_})
+                    (void *)d_rot_, (void *)d_ksi_, (void *)d_gal_s_})
         if (p) (void)hipFree(p);
     for (void *p : owned_) (void)hipFree(p);
     for (auto &kv : wt_cache_) (void)hipFree(kv.second);
@@ -887,6 +888,18 @@ u64 *Engine::workspace(size_t words) {
         ws_words_ = words;
     }
     return ws_;
+}
+
+u64 *Engine::chunk_buffer(size_t words) {
+    if (words > wtmp_words_) {
+        MK_HIP(hipStreamSynchronize(stream_));
+        if (wtmp_) MK_HIP(hipFree(wtmp_));
+        wtmp_ = nullptr;
+        wtmp_words_ = 0;
+        MK_HIP(hipMalloc(&wtmp_, words * sizeof(u64)));
+        wtmp_words_ = words;
+    }
+    return wtmp_;
 }
 
 const u64 *Engine::limb_vector(const std::string &key, const std::vector<u64> &vals) {
@@ -2142,22 +2155,15 @@ void Engine::reencrypt_wsum(const u64 *cts, const u64 *evks_scaled, u64 *out, ui
     // other ring sizes / arithmetic classes: the composition, chunk by chunk -- c0 scaled into a buffer of its own (the
     // re-encryption owns the workspace), then the accumulating re-encryption with the scaled key
     const uint32_t chunk = std::min(knobs_.chunk, n_ct);
-    if ((size_t)chunk * ct_words > wtmp_words_) {
-        MK_HIP(hipStreamSynchronize(stream_));
-        if (wtmp_) MK_HIP(hipFree(wtmp_));
-        wtmp_ = nullptr;
-        wtmp_words_ = 0;
-        MK_HIP(hipMalloc(&wtmp_, (size_t)chunk * ct_words * sizeof(u64)));
-        wtmp_words_ = (size_t)chunk * ct_words;
-    }
+    u64 *scaled = chunk_buffer((size_t)chunk * ct_words);
     EwGeom g{ps_.n, nl, ps_.L};
     for (uint32_t c = 0; c < n_clients; ++c)
         for (uint32_t b0 = 0; b0 < n_ct; b0 += chunk) {
             const uint32_t cnt = std::min(chunk, n_ct - b0);
             k_scale_c0<<<ew_grid(ps_.n, 2 * nl, cnt), EW_THREADS, 0, stream_>>>(
-                cts + ((size_t)c * n_ct + b0) * ct_words, wtmp_, g, d_limb_, wt + (size_t)c * ps_.D * WT_WORDS);
+                cts + ((size_t)c * n_ct + b0) * ct_words, scaled, g, d_limb_, wt + (size_t)c * ps_.D * WT_WORDS);
             MK_HIP(hipGetLastError());
-            reencrypt_chunk(wtmp_, evks_scaled + (size_t)c * evk_words, out + (size_t)b0 * ct_words, cnt, nl, c != 0);
+            reencrypt_chunk(scaled, evks_scaled + (size_t)c * evk_words, out + (size_t)b0 * ct_words, cnt, nl, c != 0);
         }
 }
 
@@ -2371,6 +2377,76 @@ void Engine::rekeygen(const int8_t *s_old, const u64 *pk_new, const int8_t *u, c
                                                          0, 0, g, d_limb_, D);
         MK_HIP(hipGetLastError());
         MK_HIP(hipStreamSynchronize(stream_));  // d_gadget is rewritten next iteration
+    }
+}
+
+// ---- slot rotations ("rotations and slot sums"); overlaps and the span are refused in capi.cpp ---------------
+
+// rows = (polynomial, limb) pairs, N words apart in both buffers
+void Engine::launch_automorph(const u64 *in, u64 *out, size_t rows, uint32_t g) {
+    if (!galois_valid(g, ps_.log_n)) throw std::invalid_argument("Galois element must be odd and below 2N");
+    if (((uintptr_t)in | (uintptr_t)out) & 15) throw std::invalid_argument("polynomials must be 16-byte aligned");
+    const uint32_t log_t = std::min(ps_.log_n, AUTO_LOG_TILE);
+    const size_t blocks = rows << (ps_.log_n - log_t);
+    if (blocks > 0x7fffffffu) throw std::invalid_argument("batch too large for one launch");
+    if (!blocks) return;
+    k_automorph<<<dim3((unsigned)blocks), AUTO_THREADS, 0, stream_>>>(in, out, g, ps_.log_n, log_t);
+    MK_HIP(hipGetLastError());
+}
+
+void Engine::automorphism(const u64 *in, u64 *out, uint32_t n_polys, uint32_t nl, uint32_t g) {
+    need_device();
+    check_nl(nl);
+    launch_automorph(in, out, (size_t)n_polys * nl, g);
+}
+
+void Engine::automorphism_secret(const int8_t *s, int8_t *out, uint32_t g) {
+    need_device();
+    if (!galois_valid(g, ps_.log_n)) throw std::invalid_argument("Galois element must be odd and below 2N");
+    k_automorph_s8<<<(ps_.n + 255) / 256, 256, 0, stream_>>>(s, out, g, ps_.log_n);
+    MK_HIP(hipGetLastError());
+}
+
+// the re-encryption key from sigma_g(s) to s: a ciphertext permuted by sigma_g decrypts under sigma_g(s)
+void Engine::galois_keygen(const int8_t *s, const u64 *pk, const int8_t *u, const int32_t *e0, const int32_t *e1, uint32_t g,
+                           u64 *evk) {
+    need_device();
+    if (!d_gal_s_) MK_HIP(hipMalloc(&d_gal_s_, ps_.n));
+    automorphism_secret(s, d_gal_s_, g);
+    rekeygen(d_gal_s_, pk, u, e0, e1, evk);
+}
+
+// Both components are permuted straight into `out`, where the key switch then runs in place: sigma_g(c1) exists once in
+// HBM, as the source of the INTT and as the digits' own limbs, and sigma_g(c0) sits where the ModDown tail adds it.
+// One read and one write of the ciphertext on top of reencrypt.
+void Engine::rotate(const u64 *ct, const u64 *evk, u64 *out, uint32_t n_ct, uint32_t nl, uint32_t g) {
+    need_device();
+    check_nl(nl);
+    const size_t ct_words = (size_t)2 * nl * ps_.n;
+    for (uint32_t done = 0; done < n_ct; done += knobs_.chunk) {
+        const uint32_t cnt = std::min(knobs_.chunk, n_ct - done);
+        launch_automorph(ct + done * ct_words, out + done * ct_words, (size_t)cnt * 2 * nl, g);
+        reencrypt_chunk(out + done * ct_words, evk, out + done * ct_words, cnt, nl, false);
+    }
+}
+
+// out = ct; step k: out += ReEncrypt(sigma_g(out), evks[k]) with g = 5^(2^k): the permuted chunk goes to the chunk
+// buffer, the accumulating ModDown tail adds the rotation to the running sum
+void Engine::slot_sum(const u64 *ct, const u64 *evks, u64 *out, uint32_t n_ct, uint32_t nl, uint32_t span) {
+    need_device();
+    check_nl(nl);
+    const size_t ct_words = (size_t)2 * nl * ps_.n, evk_words = (size_t)ps_.beta * 2 * ps_.D * ps_.n;
+    if (!n_ct) return;
+    const uint32_t chunk = std::min(knobs_.chunk, n_ct);
+    u64 *perm = span > 1 ? chunk_buffer((size_t)chunk * ct_words) : nullptr;
+    for (uint32_t done = 0; done < n_ct; done += chunk) {
+        const uint32_t cnt = std::min(chunk, n_ct - done);
+        u64 *acc = out + done * ct_words;
+        MK_HIP(hipMemcpyAsync(acc, ct + done * ct_words, cnt * ct_words * sizeof(u64), hipMemcpyDeviceToDevice, stream_));
+        for (uint32_t k = 0; (1u << k) < span; ++k) {
+            launch_automorph(acc, perm, (size_t)cnt * 2 * nl, galois_element((int32_t)(1u << k), ps_.log_n));
+            reencrypt_chunk(perm, evks + k * evk_words, acc, cnt, nl, true);
+        }
     }
 }
 

@@ -208,6 +208,18 @@ public:
     void share_key(const u64 *sk, u64 *shares, uint32_t nl, uint32_t n_parties, uint32_t threshold, const uint8_t *key32,
                    uint32_t sid0);
     void combine_key_shares(const u64 *in, const u64 *w, u64 *out, uint32_t m, uint32_t nl);
+    // slot rotations ("rotations and slot sums"; index arithmetic: galois.hpp).  g: odd, below 2N.
+    //   automorphism:        out[p][i] = sigma_g(in[p][i]) on u64[n_polys][nl][N], EVALUATION; out never overlaps in
+    //   automorphism_secret: out int8[N] = sigma_g(s), COEFFICIENT, signed
+    //   galois_keygen:       evk = rekeygen(sigma_g(s), pk, u, e0, e1)
+    //   rotate:              out[b] = ReEncrypt(sigma_g(ct[b]), evk)
+    //   slot_sum:            out = ct, then out += Rotate(out, 5^(2^k)) with evks[k] for k = 0 .. log2(span) - 1
+    void automorphism(const u64 *in, u64 *out, uint32_t n_polys, uint32_t nl, uint32_t g);
+    void automorphism_secret(const int8_t *s, int8_t *out, uint32_t g);
+    void galois_keygen(const int8_t *s, const u64 *pk, const int8_t *u, const int32_t *e0, const int32_t *e1, uint32_t g,
+                       u64 *evk);
+    void rotate(const u64 *ct, const u64 *evk, u64 *out, uint32_t n_ct, uint32_t nl, uint32_t g);
+    void slot_sum(const u64 *ct, const u64 *evks, u64 *out, uint32_t n_ct, uint32_t nl, uint32_t span);
     void lift_ntt(const double *coef, u64 *out, uint32_t n, uint32_t nl);
     void decrypt(const u64 *ct, const u64 *sk, u64 *m, uint32_t n_ct, uint32_t nl);
     // counter-based samplers (ChaCha20 block function under a 256-bit key): element i of stream sid is a pure
@@ -247,6 +259,8 @@ private:
     void need_device() const;
     void check_nl(uint32_t nl) const;
     u64 *workspace(size_t words);  // grow-only scratch arena (stream-ordered reuse)
+    u64 *chunk_buffer(size_t words);  // a second grow-only buffer: a chunk of ciphertexts that feeds reencrypt_chunk
+    void launch_automorph(const u64 *in, u64 *out, size_t rows, uint32_t g);
     // p_scaled: the P targets' constants carry ModDown's scale (ParamSet::modup_table_pscaled; the merged n-client flow)
     const DevConv &modup_conv(uint32_t nl, uint32_t part, bool p_scaled = false);
     const DevConv &moddown_conv(uint32_t nl);
@@ -315,8 +329,9 @@ private:
     std::map<uint32_t, DevConv> moddown_cache_;
     std::map<std::string, u64 *> vec_cache_;
     std::map<std::string, u64 *> wt_cache_;  // weight_table
-    u64 *wtmp_ = nullptr;                    // reencrypt_wsum outside the merged flow: a chunk with c0 scaled
+    u64 *wtmp_ = nullptr;                    // chunk_buffer: a chunk with c0 scaled (reencrypt_wsum) or permuted (slot_sum)
     size_t wtmp_words_ = 0;
+    int8_t *d_gal_s_ = nullptr;  // galois_keygen: sigma_g(s)
     std::vector<void *> owned_;
 };
 
