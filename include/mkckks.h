@@ -372,6 +372,49 @@ int mkckks_rotate_batch(mkckks_ctx *c, const uint64_t *d_ct, const uint64_t *d_e
 int mkckks_slot_sum_batch(mkckks_ctx *c, const uint64_t *d_ct, const uint64_t *d_evks, uint64_t *d_out, uint32_t n_ct,
                           uint32_t nl, uint32_t span);
 
+/* ==== ciphertext products: cc->EvalMultKeyGen / cc->EvalMult(ct, ct) / cc->Relinearize / cc->EvalInnerProduct(ct, ct) ===
+ * Upstream CryptoContext calls the reference never makes: everything its mains compute is linear in the encrypted
+ * values.  With them the server can form products of two ENCRYPTED vectors: squared norms, the alignment with an
+ * encrypted reference update, pairwise distances, per-coordinate variances; mkckks_slot_sum_batch then turns a product
+ * into an encrypted inner product, and only that scalar is decrypted.
+ * Tensor product, pointwise mod q_i in EVALUATION format: (a0, a1) x (b0, b1) = (a0 b0, a0 b1 + a1 b0, a1 b1) =: (d0, d1,
+ * d2), a degree-2 ("three-component") ciphertext u64[n_ct][3][nl][N] that decrypts as d0 + d1 s + d2 s^2.
+ * Relinearisation key: the re-encryption key from s^2 to s.  Relinearisation: (d0, d1) + KeySwitch(d2, rlk), the hybrid
+ * key switch of mkckks_reencrypt_batch on the degree-2 component.
+ * Scale rule: the result has scale S_a * S_b on the same limbs, noiseScaleDeg = the sum of the operands'; the caller
+ * rescales with mkckks_rescale_batch.  Headroom: log2(S_a * S_b * |values|^2) must stay below
+ * log2(q_0 ... q_{nl-1}) - 1; the library cannot check it.  Noise: that of one re-encryption plus the product terms
+ * (m_a e_b + m_b e_a + e_a e_b).
+ * Refusals of the compute calls: MKCKKS_E_INVALID for null pointers, nl outside [1, L], n_terms == 0, an output that
+ * overlaps an input (mkckks_mult_relin_batch alone accepts an output that IS an input); a zero n_ct is a no-op; a
+ * host-only context gives MKCKKS_E_NODEVICE.  The ciphertext arrays are read and written 16 bytes at a time and must
+ * be 16-byte aligned (every allocation is; an odd word offset into one is not): MKCKKS_E_INVALID.
+ *
+ * (cc->EvalMultKeyGen) The relinearisation key of s: bit for bit mkckks_rekeygen with NTT(s_old) replaced by sk^2, the
+ * pointwise square of the EVALUATION-form secret over all D limbs: evk[j][0] = pk0 u_j + e0_j + (P mod q_i) sk^2 on digit
+ * j's own limbs (the gadget is 0 elsewhere, and 0 on the P limbs), evk[j][1] = pk1 u_j + e1_j.  Arguments, randomness
+ * layouts and d_evk u64[beta][2][D][N] as mkckks_galois_keygen, without g.  Generated by the OWNER of s (for the server's
+ * products: the owner of the common-domain key).  A relinearisation key for a JOINT key needs a collective protocol,
+ * which this library does not have. */
+int mkckks_relin_keygen(mkckks_ctx *c, const int8_t *d_s, const uint64_t *d_pk, const int8_t *d_u, const int32_t *d_e0,
+                        const int32_t *d_e1, uint64_t *d_evk);
+/* (cc->EvalMultNoRelin, summed) d_out3[b] = sum over t < n_terms of the tensor product of d_a[t][b] and d_b[t][b];
+ * d_a, d_b u64[n_terms][n_ct][2][nl][N], d_out3 u64[n_ct][3][nl][N], canonical.  n_terms = 1 is the plain tensor
+ * product; d_a == d_b is the square (two polynomials are read instead of four).  The lazy-relinearisation form: many
+ * products, ONE key switch.  d_out3 overlaps neither input. */
+int mkckks_tensor_sum_batch(mkckks_ctx *c, const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_out3, uint32_t n_terms,
+                            uint32_t n_ct, uint32_t nl);
+/* (cc->Relinearize) d_out[b] = (d0, d1) + KeySwitch(d2, d_rlk) of d_in3 u64[n_ct][3][nl][N]; d_out u64[n_ct][2][nl][N],
+ * nl <= L (a partial last digit included).  Bit for bit mkckks_eval_add_batch((d0, d1), mkckks_reencrypt_batch((0, d2),
+ * d_rlk)).  d_out never overlaps d_in3: the key switch reads d2 after (d0, d1) were written. */
+int mkckks_relinearize_batch(mkckks_ctx *c, const uint64_t *d_in3, const uint64_t *d_rlk, uint64_t *d_out, uint32_t n_ct,
+                             uint32_t nl);
+/* (cc->EvalMult(ct, ct)) d_out = Relinearize(tensor product of d_a and d_b): bit-identical to mkckks_tensor_sum_batch
+ * with one term followed by mkckks_relinearize_batch, but d2 exists only in the engine's chunk buffer.  d_out may be
+ * exactly d_a or d_b (any other overlap is refused); d_a == d_b squares. */
+int mkckks_mult_relin_batch(mkckks_ctx *c, const uint64_t *d_a, const uint64_t *d_b, const uint64_t *d_rlk, uint64_t *d_out,
+                            uint32_t n_ct, uint32_t nl);
+
 /* ---- cc->Encrypt(pk, pt)  (client/src/encryptModelWeights.cpp:83,91,110) --
  * d_pt u64[n_ct][nl][N] encoded plaintexts (EVALUATION); v int8[n_ct][N];
  * e0,e1 int32[n_ct][N]; out u64[n_ct][2][nl][N]. */

@@ -91,6 +91,10 @@ SYMBOLS = {
     "mkckks_galois_keygen": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp]),
     "mkckks_rotate_batch": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u32]),
     "mkckks_slot_sum_batch": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u32]),
+    "mkckks_relin_keygen": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mkckks_tensor_sum_batch": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u32]),
+    "mkckks_relinearize_batch": (_int, [_vp, _vp, _vp, _vp, _u32, _u32]),
+    "mkckks_mult_relin_batch": (_int, [_vp, _vp, _vp, _vp, _vp, _u32, _u32]),
     "mkckks_keygen_join": (_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "mkckks_partial_decrypt_batch": (_int, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _int]),
     "mkckks_fuse_shares_batch": (_int, [_vp, _vp, _vp, _u32, _u32, _u32]),
@@ -581,6 +585,23 @@ class Context:
     def slot_sum(self, ct, evks, out, n_ct, nl, span):
         """out = ct + its rotations by 1 .. span - 1; evks [log2 span][beta][2][D][N], key k for step 2^k."""
         self._check(self._L.mkckks_slot_sum_batch(self._h, _ptr(ct), _ptr(evks), _ptr(out), n_ct, nl, span))
+
+    # ---- ciphertext products (include/mkckks.h: "ciphertext products")
+    def relin_keygen(self, s, pk, u, e0, e1, evk):
+        """The relinearisation key of s: rekeygen with NTT(s_old) replaced by NTT(s)^2."""
+        self._check(self._L.mkckks_relin_keygen(self._h, _ptr(s), _ptr(pk), _ptr(u), _ptr(e0), _ptr(e1), _ptr(evk)))
+
+    def tensor_sum(self, a, b, out3, n_terms, n_ct, nl):
+        """out3[b] = sum_t (a0 b0, a0 b1 + a1 b0, a1 b1); a, b [n_terms][n_ct][2][nl][N], out3 [n_ct][3][nl][N]."""
+        self._check(self._L.mkckks_tensor_sum_batch(self._h, _ptr(a), _ptr(b), _ptr(out3), n_terms, n_ct, nl))
+
+    def relinearize(self, in3, rlk, out, n_ct, nl):
+        """out = (d0, d1) + KeySwitch(d2, rlk)."""
+        self._check(self._L.mkckks_relinearize_batch(self._h, _ptr(in3), _ptr(rlk), _ptr(out), n_ct, nl))
+
+    def mult_relin(self, a, b, rlk, out, n_ct, nl):
+        """out = Relinearize(a x b); out may be a or b; a is b squares."""
+        self._check(self._L.mkckks_mult_relin_batch(self._h, _ptr(a), _ptr(b), _ptr(rlk), _ptr(out), n_ct, nl))
 
     def encrypt(self, pk, pt, v, e0, e1, ct, n_ct, nl):
         self._check(self._L.mkckks_encrypt_batch(self._h, _ptr(pk), _ptr(pt), _ptr(v), _ptr(e0), _ptr(e1), _ptr(ct),

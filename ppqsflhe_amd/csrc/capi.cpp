@@ -486,6 +486,69 @@ int mkckks_slot_sum_batch(mkckks_ctx *c, const uint64_t *ct, const uint64_t *evk
         c->eng->slot_sum(ct, evks, out, n_ct, nl, span);
     });
 }
+// ---- ciphertext products: every refusal is decided here, before a device is asked for
+// bytes of `count` polynomials of nl limbs, saturated (a count that large overlaps everything)
+static size_t poly_bytes(unsigned __int128 count, uint32_t nl, uint32_t n) {
+    const unsigned __int128 b = count * nl * n * sizeof(uint64_t);
+    return b > (unsigned __int128)(SIZE_MAX / 2) ? SIZE_MAX / 2 : (size_t)b;
+}
+static bool ranges_meet(const void *x, size_t x_bytes, const void *y, size_t y_bytes) {
+    const uintptr_t a = (uintptr_t)x, b = (uintptr_t)y;
+    const uintptr_t a_end = a + x_bytes < a ? UINTPTR_MAX : a + x_bytes, b_end = b + y_bytes < b ? UINTPTR_MAX : b + y_bytes;
+    return a < b_end && b < a_end;
+}
+static void need_aligned16(std::initializer_list<const void *> ptrs) {
+    for (const void *p : ptrs) need(((uintptr_t)p & 15) == 0, "ciphertext arrays must be 16-byte aligned");
+}
+int mkckks_relin_keygen(mkckks_ctx *c, const int8_t *s, const uint64_t *pk, const int8_t *u, const int32_t *e0,
+                        const int32_t *e1, uint64_t *evk) {
+    return guarded([&] {
+        need(c && s && pk && u && e0 && e1 && evk, "null argument");
+        c->eng->relin_keygen(s, pk, u, e0, e1, evk);
+    });
+}
+int mkckks_tensor_sum_batch(mkckks_ctx *c, const uint64_t *a, const uint64_t *b, uint64_t *out3, uint32_t n_terms,
+                            uint32_t n_ct, uint32_t nl) {
+    return guarded([&] {
+        need(c && a && b && out3, "null argument");
+        const mk::ParamSet &ps = c->eng->params();
+        need(nl >= 1 && nl <= ps.L, "nl out of range");
+        need(n_terms >= 1, "n_terms must be at least 1");
+        need_aligned16({a, b, out3});
+        const size_t in_bytes = poly_bytes((unsigned __int128)n_terms * n_ct * 2, nl, ps.n);
+        const size_t out_bytes = poly_bytes((unsigned __int128)n_ct * 3, nl, ps.n);
+        need(!ranges_meet(a, in_bytes, out3, out_bytes) && !ranges_meet(b, in_bytes, out3, out_bytes), "output overlaps input");
+        if (!n_ct) return;
+        c->eng->tensor_sum(a, b, out3, n_terms, n_ct, nl);
+    });
+}
+int mkckks_relinearize_batch(mkckks_ctx *c, const uint64_t *in3, const uint64_t *rlk, uint64_t *out, uint32_t n_ct,
+                             uint32_t nl) {
+    return guarded([&] {
+        need(c && in3 && rlk && out, "null argument");
+        const mk::ParamSet &ps = c->eng->params();
+        need(nl >= 1 && nl <= ps.L, "nl out of range");
+        need_aligned16({in3, out});
+        need(!ranges_meet(in3, poly_bytes((unsigned __int128)n_ct * 3, nl, ps.n), out, poly_bytes((unsigned __int128)n_ct * 2, nl, ps.n)),
+             "output overlaps input");
+        if (!n_ct) return;
+        c->eng->relinearize(in3, rlk, out, n_ct, nl);
+    });
+}
+int mkckks_mult_relin_batch(mkckks_ctx *c, const uint64_t *a, const uint64_t *b, const uint64_t *rlk, uint64_t *out,
+                            uint32_t n_ct, uint32_t nl) {
+    return guarded([&] {
+        need(c && a && b && rlk && out, "null argument");
+        const mk::ParamSet &ps = c->eng->params();
+        need(nl >= 1 && nl <= ps.L, "nl out of range");
+        need_aligned16({a, b, out});
+        const size_t bytes = poly_bytes((unsigned __int128)n_ct * 2, nl, ps.n);
+        need((out == a || !ranges_meet(a, bytes, out, bytes)) && (out == b || !ranges_meet(b, bytes, out, bytes)),
+             "output partially overlaps an input");
+        if (!n_ct) return;
+        c->eng->mult_relin(a, b, rlk, out, n_ct, nl);
+    });
+}
 int mkckks_encrypt_batch(mkckks_ctx *c, const uint64_t *pk, const uint64_t *pt, const int8_t *v, const int32_t *e0,
                          const int32_t *e1, uint64_t *ct, uint32_t n_ct, uint32_t nl) {
     return guarded([&] {

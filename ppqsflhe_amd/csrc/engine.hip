@@ -21,6 +21,7 @@
 #include "fanout_kernels.hpp"
 #include "codec_kernels.hpp"
 #include "galois_kernels.hpp"
+#include "tensor_kernels.hpp"
 #include "sampler_kernels.hpp"
 #include "arith_probe_kernels.hpp"
 #include "../../include/mkckks.h"
@@ -2347,20 +2348,36 @@ void Engine::keygen(const int8_t *s, const u64 *a, const int32_t *e, u64 *pk, u6
     MK_HIP(hipMemcpyAsync(pk + (size_t)D * n, a, (size_t)D * n * sizeof(u64), hipMemcpyDeviceToDevice, stream_));
 }
 
+// the source key's transform se u64[D][N] lives at the head of the key generators' workspace
+u64 *Engine::rekey_workspace() {
+    return workspace((size_t)ps_.D * ps_.n * (1 + 3 * (size_t)ps_.beta) + ps_.D);
+}
+
 void Engine::rekeygen(const int8_t *s_old, const u64 *pk_new, const int8_t *u, const int32_t *e0,
                       const int32_t *e1, u64 *evk) {
     need_device();
-    const uint32_t n = ps_.n, D = ps_.D, L = ps_.L, beta = ps_.beta;
-    const size_t poly = (size_t)D * n;
-    u64 *ws = workspace(poly * (1 + 3 * (size_t)beta) + D);
-    u64 *se = ws, *ue = se + poly, *e0e = ue + poly * beta, *e1e = e0e + poly * beta, *d_gadget = e1e + poly * beta;
+    const uint32_t n = ps_.n, D = ps_.D, L = ps_.L;
+    u64 *se = rekey_workspace();
     EwGeom g{n, L, L};
     k_lift<int8_t><<<ew_grid(n, D, 1), EW_THREADS, 0, stream_>>>(s_old, se, g, d_limb_, D);
+    MK_HIP(hipGetLastError());
+    ntt_launch(se, 1, L, D, false, nullptr, nullptr);
+    rekeygen_from(pk_new, u, e0, e1, evk);
+}
+
+// KeySwitchGenInternal after the source key's transform: evk[j] = (pk0 u_j + e0_j + (P mod q_i) se on digit j's own
+// limbs, pk1 u_j + e1_j) with se u64[D][N], EVALUATION, canonical, at the head of rekey_workspace().  Shared by
+// rekeygen (se = NTT(s_old)), galois_keygen (through rekeygen) and relin_keygen (se = NTT(s)^2).
+void Engine::rekeygen_from(const u64 *pk_new, const int8_t *u, const int32_t *e0, const int32_t *e1, u64 *evk) {
+    const uint32_t n = ps_.n, D = ps_.D, L = ps_.L, beta = ps_.beta;
+    const size_t poly = (size_t)D * n;
+    u64 *ws = rekey_workspace();
+    u64 *se = ws, *ue = se + poly, *e0e = ue + poly * beta, *e1e = e0e + poly * beta, *d_gadget = e1e + poly * beta;
+    EwGeom g{n, L, L};
     k_lift<int8_t><<<ew_grid(n, D, beta), EW_THREADS, 0, stream_>>>(u, ue, g, d_limb_, D);
     k_lift<int32_t><<<ew_grid(n, D, beta), EW_THREADS, 0, stream_>>>(e0, e0e, g, d_limb_, D);
     k_lift<int32_t><<<ew_grid(n, D, beta), EW_THREADS, 0, stream_>>>(e1, e1e, g, d_limb_, D);
     MK_HIP(hipGetLastError());
-    ntt_launch(se, 1, L, D, false, nullptr, nullptr);
     ntt_launch(ue, 3 * beta, L, D, false, nullptr, nullptr);  // ue, e0e, e1e are contiguous
     for (uint32_t part = 0; part < beta; ++part) {
         // gadget P mod q_i on the digit's own limbs, 0 elsewhere (KeySwitchGenInternal)
@@ -2447,6 +2464,95 @@ void Engine::slot_sum(const u64 *ct, const u64 *evks, u64 *out, uint32_t n_ct, u
             launch_automorph(acc, perm, (size_t)cnt * 2 * nl, galois_element((int32_t)(1u << k), ps_.log_n));
             reencrypt_chunk(perm, evks + k * evk_words, acc, cnt, nl, true);
         }
+    }
+}
+
+// ---- ciphertext products ("ciphertext products"); overlaps and alignment are refused in capi.cpp ------------
+
+// the relinearisation key: the re-encryption key from s^2 to s, i.e. rekeygen with NTT(s_old) replaced by NTT(s)^2
+void Engine::relin_keygen(const int8_t *s, const u64 *pk, const int8_t *u, const int32_t *e0, const int32_t *e1, u64 *evk) {
+    need_device();
+    const uint32_t n = ps_.n, D = ps_.D, L = ps_.L;
+    u64 *se = rekey_workspace();
+    EwGeom g{n, L, L};
+    k_lift<int8_t><<<ew_grid(n, D, 1), EW_THREADS, 0, stream_>>>(s, se, g, d_limb_, D);
+    MK_HIP(hipGetLastError());
+    ntt_launch(se, 1, L, D, false, nullptr, nullptr);
+    Opnd x{se, 0, 0}, none{nullptr, 0, 0};
+    k_fma<<<ew_grid(n, D, 1), EW_THREADS, 0, stream_>>>(x, x, none, none, nullptr, 0, se, 0, 0, g, d_limb_, D);
+    MK_HIP(hipGetLastError());
+    rekeygen_from(pk, u, e0, e1, evk);
+}
+
+// one k_tensor launch over `cnt` items; a == b takes the square instance
+void Engine::launch_tensor(const u64 *a, const u64 *b, size_t term_stride, uint32_t n_terms, u64 *o01, size_t o01_stride,
+                           u64 *o2, size_t o2_stride, uint32_t cnt, uint32_t nl) {
+    if (((uintptr_t)a | (uintptr_t)b | (uintptr_t)o01 | (uintptr_t)o2) & 15)
+        throw std::invalid_argument("ciphertext arrays must be 16-byte aligned");
+    if (!cnt) return;
+    const TensorArgs t{a, b, o01, o2, term_stride, o01_stride, o2_stride, n_terms, ps_.n, nl};
+    const dim3 grid((ps_.n / 2 + TENSOR_THREADS - 1) / TENSOR_THREADS, nl, cnt);
+    if (a == b) k_tensor<true><<<grid, TENSOR_THREADS, 0, stream_>>>(t, d_limb_);
+    else k_tensor<false><<<grid, TENSOR_THREADS, 0, stream_>>>(t, d_limb_);
+    MK_HIP(hipGetLastError());
+}
+
+void Engine::tensor_sum(const u64 *a, const u64 *b, u64 *out3, uint32_t n_terms, uint32_t n_ct, uint32_t nl) {
+    need_device();
+    check_nl(nl);
+    if (!n_terms) throw std::invalid_argument("n_terms must be at least 1");
+    const size_t poly = (size_t)nl * ps_.n;
+    constexpr uint32_t MAX_ITEMS = 32768;  // grid.z
+    for (uint32_t done = 0; done < n_ct; done += MAX_ITEMS) {
+        const uint32_t cnt = std::min(MAX_ITEMS, n_ct - done);
+        const size_t in_off = (size_t)done * 2 * poly, out_off = (size_t)done * 3 * poly;
+        launch_tensor(a + in_off, b + in_off, (size_t)n_ct * 2 * poly, n_terms, out3 + out_off, 3 * poly,
+                      out3 + out_off + 2 * poly, 3 * poly, cnt, nl);
+    }
+}
+
+// out[item] += KeySwitch(d2[item], rlk) for `cnt` items, d2 items d2_stride words apart: the hybrid key switch of
+// reencrypt_chunk with d2 in the place of c1 and nothing in the place of c0; the accumulating tail adds onto (d0, d1)
+void Engine::relin_chunk(const u64 *d2, size_t d2_stride, const u64 *rlk, u64 *out, uint32_t cnt, uint32_t nl) {
+    const uint32_t n = ps_.n, K = ps_.K, ext = nl + K, nparts = ps_.num_parts(nl);
+    const size_t w_coef = (size_t)cnt * nl * n, w_dig = (size_t)cnt * nparts * ext * n;
+    const size_t w_til = (size_t)cnt * 2 * ext * n, w_pc = (size_t)cnt * 2 * K * n, w_conv = (size_t)cnt * 2 * nl * n;
+    u64 *ws = workspace(w_coef + w_dig + w_til + w_pc + w_conv);
+    u64 *coef = ws, *dig = coef + w_coef, *til = dig + w_dig, *pc = til + w_til, *conv = pc + w_pc;
+    const bool p_rows = keyswitch_digits(d2, d2_stride, rlk, coef, dig, til, pc, cnt, nl);
+    moddown_core(til, pc, conv, out, (size_t)nl * n, nullptr, 0, 2 * cnt, nl, true, p_rows);
+}
+
+void Engine::relinearize(const u64 *in3, const u64 *rlk, u64 *out, uint32_t n_ct, uint32_t nl) {
+    need_device();
+    check_nl(nl);
+    const uint32_t n = ps_.n;
+    const size_t poly = (size_t)nl * n;
+    for (uint32_t done = 0; done < n_ct; done += knobs_.chunk) {
+        const uint32_t cnt = std::min(knobs_.chunk, n_ct - done);
+        const u64 *src = in3 + (size_t)done * 3 * poly;
+        u64 *dst = out + (size_t)done * 2 * poly;
+        k_copy_slots<<<ew_grid(n, 2 * nl, cnt), EW_THREADS, 0, stream_>>>(src, 3 * poly, 0, dst, 2 * poly, 0, n);
+        MK_HIP(hipGetLastError());
+        relin_chunk(src + 2 * poly, 3 * poly, rlk, dst, cnt, nl);
+    }
+}
+
+// per chunk: k_tensor writes d0, d1 straight into `out` (which may be a or b: it touches a thread's own words only) and
+// d2 into the chunk buffer, the only place it ever exists; the key switch of d2 accumulates onto out
+void Engine::mult_relin(const u64 *a, const u64 *b, const u64 *rlk, u64 *out, uint32_t n_ct, uint32_t nl) {
+    need_device();
+    check_nl(nl);
+    if (!n_ct) return;
+    const size_t poly = (size_t)nl * ps_.n;
+    const uint32_t chunk = std::min(knobs_.chunk, n_ct);
+    u64 *d2 = chunk_buffer((size_t)chunk * poly);
+    for (uint32_t done = 0; done < n_ct; done += chunk) {
+        const uint32_t cnt = std::min(chunk, n_ct - done);
+        const size_t off = (size_t)done * 2 * poly;
+        u64 *dst = out + off;
+        launch_tensor(a + off, b + off, 0, 1, dst, 2 * poly, d2, poly, cnt, nl);
+        relin_chunk(d2, poly, rlk, dst, cnt, nl);
     }
 }
 

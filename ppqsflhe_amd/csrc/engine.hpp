@@ -220,6 +220,15 @@ public:
                        u64 *evk);
     void rotate(const u64 *ct, const u64 *evk, u64 *out, uint32_t n_ct, uint32_t nl, uint32_t g);
     void slot_sum(const u64 *ct, const u64 *evks, u64 *out, uint32_t n_ct, uint32_t nl, uint32_t span);
+    // ciphertext products ("ciphertext products"; kernel: tensor_kernels.hpp)
+    //   relin_keygen: evk = rekeygen with NTT(s_old) replaced by NTT(s)^2 (the re-encryption key from s^2 to s)
+    //   tensor_sum:   out3[b] = sum_t (a0 b0, a0 b1 + a1 b0, a1 b1); a, b u64[n_terms][n_ct][2][nl][N], out3 u64[n_ct][3][nl][N]
+    //   relinearize:  out[b] = (d0, d1) + KeySwitch(d2, rlk); out never overlaps in3
+    //   mult_relin:   relinearize(tensor_sum(a, b, 1 term)); out may be a or b
+    void relin_keygen(const int8_t *s, const u64 *pk, const int8_t *u, const int32_t *e0, const int32_t *e1, u64 *evk);
+    void tensor_sum(const u64 *a, const u64 *b, u64 *out3, uint32_t n_terms, uint32_t n_ct, uint32_t nl);
+    void relinearize(const u64 *in3, const u64 *rlk, u64 *out, uint32_t n_ct, uint32_t nl);
+    void mult_relin(const u64 *a, const u64 *b, const u64 *rlk, u64 *out, uint32_t n_ct, uint32_t nl);
     void lift_ntt(const double *coef, u64 *out, uint32_t n, uint32_t nl);
     void decrypt(const u64 *ct, const u64 *sk, u64 *m, uint32_t n_ct, uint32_t nl);
     // counter-based samplers (ChaCha20 block function under a 256-bit key): element i of stream sid is a pure
@@ -261,6 +270,11 @@ private:
     u64 *workspace(size_t words);  // grow-only scratch arena (stream-ordered reuse)
     u64 *chunk_buffer(size_t words);  // a second grow-only buffer: a chunk of ciphertexts that feeds reencrypt_chunk
     void launch_automorph(const u64 *in, u64 *out, size_t rows, uint32_t g);
+    u64 *rekey_workspace();  // the key generators' workspace; the source key's transform u64[D][N] is its head
+    void rekeygen_from(const u64 *pk_new, const int8_t *u, const int32_t *e0, const int32_t *e1, u64 *evk);
+    void launch_tensor(const u64 *a, const u64 *b, size_t term_stride, uint32_t n_terms, u64 *o01, size_t o01_stride, u64 *o2,
+                       size_t o2_stride, uint32_t cnt, uint32_t nl);
+    void relin_chunk(const u64 *d2, size_t d2_stride, const u64 *rlk, u64 *out, uint32_t cnt, uint32_t nl);
     // p_scaled: the P targets' constants carry ModDown's scale (ParamSet::modup_table_pscaled; the merged n-client flow)
     const DevConv &modup_conv(uint32_t nl, uint32_t part, bool p_scaled = false);
     const DevConv &moddown_conv(uint32_t nl);
@@ -329,7 +343,7 @@ private:
     std::map<uint32_t, DevConv> moddown_cache_;
     std::map<std::string, u64 *> vec_cache_;
     std::map<std::string, u64 *> wt_cache_;  // weight_table
-    u64 *wtmp_ = nullptr;                    // chunk_buffer: a chunk with c0 scaled (reencrypt_wsum) or permuted (slot_sum)
+    u64 *wtmp_ = nullptr;                    // chunk_buffer: a chunk with c0 scaled (reencrypt_wsum), permuted (slot_sum), or d2 (mult_relin)
     size_t wtmp_words_ = 0;
     int8_t *d_gal_s_ = nullptr;  // galois_keygen: sigma_g(s)
     std::vector<void *> owned_;
