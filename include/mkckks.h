@@ -353,8 +353,9 @@ int mkckks_automorphism_secret(mkckks_ctx *c, const int8_t *d_s, int8_t *d_out, 
 /* (cc->EvalRotateKeyGen / cc->EvalSumKeyGen for one element) The Galois key for g is the re-encryption key from
  * sigma_g(s) to s: bit for bit mkckks_rekeygen(sigma_g(d_s), d_pk, d_u, d_e0, d_e1), same layouts and randomness
  * arguments; d_pk is the public key of s; d_evk out u64[beta][2][D][N].  Generated by the OWNER of s (for the server's
- * slot sums: the owner of the common-domain key).  A Galois key for a JOINT key needs a collective protocol, which this
- * library does not have. */
+ * slot sums: the owner of the common-domain key).  A Galois key for a JOINT key (mkckks_keygen_join: nobody holds s) is
+ * made collectively, in one round: every party calls this with its OWN s_p and the JOINT public key, and
+ * mkckks_evk_sum adds the n shares ("collective evaluation keys" below, with the noise and the security rules). */
 int mkckks_galois_keygen(mkckks_ctx *c, const int8_t *d_s, const uint64_t *d_pk, const int8_t *d_u, const int32_t *d_e0,
                          const int32_t *d_e1, uint32_t g, uint64_t *d_evk);
 /* (cc->EvalRotate) d_out[b] = ReEncrypt((sigma_g(c0), sigma_g(c1)), d_evk): word for word what mkckks_reencrypt_batch
@@ -394,8 +395,10 @@ int mkckks_slot_sum_batch(mkckks_ctx *c, const uint64_t *d_ct, const uint64_t *d
  * pointwise square of the EVALUATION-form secret over all D limbs: evk[j][0] = pk0 u_j + e0_j + (P mod q_i) sk^2 on digit
  * j's own limbs (the gadget is 0 elsewhere, and 0 on the P limbs), evk[j][1] = pk1 u_j + e1_j.  Arguments, randomness
  * layouts and d_evk u64[beta][2][D][N] as mkckks_galois_keygen, without g.  Generated by the OWNER of s (for the server's
- * products: the owner of the common-domain key).  A relinearisation key for a JOINT key needs a collective protocol,
- * which this library does not have. */
+ * products: the owner of the common-domain key).  A relinearisation key for a JOINT key is made collectively, in two
+ * rounds: mkckks_rekeygen(s_p, joint pk) summed by mkckks_evk_sum, then mkckks_relin_share summed by mkckks_evk_sum
+ * ("collective evaluation keys" below, with the noise and the security rules).  The compute calls of this section take a
+ * collectively made key unchanged. */
 int mkckks_relin_keygen(mkckks_ctx *c, const int8_t *d_s, const uint64_t *d_pk, const int8_t *d_u, const int32_t *d_e0,
                         const int32_t *d_e1, uint64_t *d_evk);
 /* (cc->EvalMultNoRelin, summed) d_out3[b] = sum over t < n_terms of the tensor product of d_a[t][b] and d_b[t][b];
@@ -642,6 +645,47 @@ int mkckks_combine_key_shares(mkckks_ctx *c, const uint64_t *d_in, const uint64_
  * h_parties are 1-based party indices.  An index of 0 or above MKCKKS_MAX_PARTIES, a duplicate and n_active == 0 are
  * each MKCKKS_E_INVALID. */
 int mkckks_lagrange_at_zero(const mkckks_ctx *c, const uint32_t *h_parties, uint32_t n_active, uint64_t *h_out);
+
+/* ==== collective evaluation keys of a JOINT key: cc->MultiEvalAtIndexKeyGen / cc->MultiEvalSumKeyGen +
+ * cc->MultiAddEvalAutomorphismKeys, and cc->MultiKeySwitchGen + cc->MultiAddEvalKeys + cc->MultiMultEvalKey +
+ * cc->MultiAddEvalMultKeys =========================================================================================
+ * Upstream CryptoContext calls the reference (built with MULTIPARTY) never makes.  With a joint key pk = (sum b_p, a),
+ * S = sum_p s_p, nobody can call mkckks_galois_keygen or mkckks_relin_keygen on S.  Every step below is linear in what
+ * the parties already hold; g_j is the gadget of digit j ((P mod q_i) on digit j's own limbs, 0 elsewhere).
+ *   Galois key for g, ONE round: party p computes mkckks_galois_keygen(s_p, pk_joint, u, e0, e1, g): a public-key
+ *     encryption of P g_j sigma_g(s_p) under the joint key.  mkckks_evk_sum of the n shares encrypts
+ *     P g_j sigma_g(S): a Galois key of the joint key.  Noise: n times one key's.
+ *   Relinearisation key, TWO rounds.  Round 1: party p computes mkckks_rekeygen(s_p, pk_joint, ...) ("own domain ->
+ *     joint domain"); the sum K1 satisfies K1[j][0] + K1[j][1] S = P g_j S + n1, n1 = e_pk U + E0 + E1 S.  Round 2:
+ *     party p computes mkckks_relin_share(K1, sk_p, fresh e0, e1); the sum is (S K1[j][0] + E0', S K1[j][1] + E1'),
+ *     which decrypts under S to P g_j S^2 + S n1 + E0' + E1' S: a relinearisation key of the joint key.
+ *   Noise rule: the key error is dominated by S n1, a product of two polynomials: its standard deviation is about
+ *     sqrt(N * 2n/3) times that of n1 (S has n ternary summands of variance 2/3 per coefficient).  The measured effect
+ *     on decoded values is in DESIGN.md ("collective evaluation keys").
+ * The result is an ordinary u64[beta][2][D][N] key: mkckks_rotate_batch, mkckks_slot_sum_batch,
+ * mkckks_relinearize_batch and mkckks_mult_relin_batch take it unchanged.
+ * Security rules.  A share holds no secret under RLWE (it is a public-key encryption, or K1 times a secret plus fresh
+ * error) and may be sent in the clear.  A single share, or a sum of FEWER than all n, used as a key gives noise and no
+ * error: the library cannot tell.  Every call takes FRESH errors (and u); a repeated error cancels in the difference of
+ * two shares.  ALL n parties of the key epoch take part, once per epoch, while all are present: the t-of-n key shares
+ * of mkckks_share_key play no role here.
+ * Refusals, decided before a device is asked for: MKCKKS_E_INVALID for null pointers, a party count outside
+ * [1, MKCKKS_MAX_PARTIES], an overlap other than the one each call names, and key arrays that are not 16-byte aligned;
+ * a host-only context gives MKCKKS_E_NODEVICE.
+ *
+ * (cc->MultiAddEvalKeys / MultiAddEvalAutomorphismKeys / MultiAddEvalMultKeys) d_out[k] = sum over p of d_in[p][k] mod
+ * q_i on ALL D limbs (mkckks_eval_sum_batch stops at L); d_in u64[n_parties][n_keys][beta][2][D][N], d_out
+ * u64[n_keys][beta][2][D][N], canonical, equal to exact integer arithmetic word for word at any residues (64 terms of
+ * q - 1 included).  d_out may be d_in (the first party's keys); any other overlap is refused.  n_keys = 0 is a no-op. */
+int mkckks_evk_sum(mkckks_ctx *c, const uint64_t *d_in, uint64_t *d_out, uint32_t n_parties, uint32_t n_keys);
+/* (cc->MultiMultEvalKey) round 2 of the relinearisation key: for every digit j, component c and ALL D limbs i (the Q
+ * limbs and the K limbs of P)  d_share[j][c][i] = d_key1[j][c][i] * d_sk[i] + NTT_i(e_c[j]) mod q_i, canonical.
+ * d_key1, d_share u64[beta][2][D][N]; d_sk u64[D][N] as mkckks_keygen / mkckks_keygen_join write it (all D limbs are
+ * read); d_e0, d_e1 int32[beta][N] in COEFFICIENT form (the contract of mkckks_rekeygen).  d_share may be d_key1; any
+ * other overlap is refused.  One fused column + row kernel pair where the ring size has them, else the composition of
+ * lift, transform and multiply-add; all paths give the same bits. */
+int mkckks_relin_share(mkckks_ctx *c, const uint64_t *d_key1, const uint64_t *d_sk, const int32_t *d_e0, const int32_t *d_e1,
+                       uint64_t *d_share);
 
 /* ---- multi-GPU aggregation step (new) -----------------------
  * after an RCCL ncclSum over uint64 of `n_terms` canonical residues per word,

@@ -95,6 +95,8 @@ SYMBOLS = {
     "mkckks_tensor_sum_batch": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u32]),
     "mkckks_relinearize_batch": (_int, [_vp, _vp, _vp, _vp, _u32, _u32]),
     "mkckks_mult_relin_batch": (_int, [_vp, _vp, _vp, _vp, _vp, _u32, _u32]),
+    "mkckks_evk_sum": (_int, [_vp, _vp, _vp, _u32, _u32]),
+    "mkckks_relin_share": (_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "mkckks_keygen_join": (_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "mkckks_partial_decrypt_batch": (_int, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _int]),
     "mkckks_fuse_shares_batch": (_int, [_vp, _vp, _vp, _u32, _u32, _u32]),
@@ -602,6 +604,15 @@ class Context:
     def mult_relin(self, a, b, rlk, out, n_ct, nl):
         """out = Relinearize(a x b); out may be a or b; a is b squares."""
         self._check(self._L.mkckks_mult_relin_batch(self._h, _ptr(a), _ptr(b), _ptr(rlk), _ptr(out), n_ct, nl))
+
+    # ---- collective evaluation keys of a joint key (include/mkckks.h: "collective evaluation keys")
+    def evk_sum(self, shares, out, n_parties, n_keys):
+        """out[k] = sum_p shares[p][k] on all D limbs; shares [n_parties][n_keys][beta][2][D][N]; out may be shares[0]."""
+        self._check(self._L.mkckks_evk_sum(self._h, _ptr(shares), _ptr(out), n_parties, n_keys))
+
+    def relin_share(self, key1, sk, e0, e1, share):
+        """Round 2 of the collective relinearisation key: share = key1 * sk + NTT(e) on all D limbs; share may be key1."""
+        self._check(self._L.mkckks_relin_share(self._h, _ptr(key1), _ptr(sk), _ptr(e0), _ptr(e1), _ptr(share)))
 
     def encrypt(self, pk, pt, v, e0, e1, ct, n_ct, nl):
         self._check(self._L.mkckks_encrypt_batch(self._h, _ptr(pk), _ptr(pt), _ptr(v), _ptr(e0), _ptr(e1), _ptr(ct),

@@ -549,6 +549,35 @@ int mkckks_mult_relin_batch(mkckks_ctx *c, const uint64_t *a, const uint64_t *b,
         c->eng->mult_relin(a, b, rlk, out, n_ct, nl);
     });
 }
+// ---- collective evaluation keys of a joint key: every refusal is decided here, before a device is asked for
+int mkckks_evk_sum(mkckks_ctx *c, const uint64_t *in, uint64_t *out, uint32_t n_parties, uint32_t n_keys) {
+    return guarded([&] {
+        need(c && in && out, "null argument");
+        const mk::ParamSet &ps = c->eng->params();
+        need(n_parties >= 1 && n_parties <= MKCKKS_MAX_PARTIES, "need 1 <= n_parties <= MKCKKS_MAX_PARTIES");
+        need_aligned16({in, out});
+        const size_t set_bytes = poly_bytes((unsigned __int128)n_keys * ps.beta * 2, ps.D, ps.n);
+        const size_t in_bytes = poly_bytes((unsigned __int128)n_parties * n_keys * ps.beta * 2, ps.D, ps.n);
+        need(out == in || !ranges_meet(in, in_bytes, out, set_bytes), "output overlaps the shares (only the first share may be the output)");
+        if (!n_keys) return;
+        c->eng->evk_sum(in, out, n_parties, n_keys);
+    });
+}
+int mkckks_relin_share(mkckks_ctx *c, const uint64_t *key1, const uint64_t *sk, const int32_t *e0, const int32_t *e1,
+                       uint64_t *share) {
+    return guarded([&] {
+        need(c && key1 && sk && e0 && e1 && share, "null argument");
+        const mk::ParamSet &ps = c->eng->params();
+        need_aligned16({key1, sk, share});
+        const size_t key_bytes = poly_bytes((unsigned __int128)ps.beta * 2, ps.D, ps.n), sk_bytes = poly_bytes(1, ps.D, ps.n);
+        const size_t e_bytes = (size_t)ps.beta * ps.n * sizeof(int32_t);
+        need(share == key1 || !ranges_meet(key1, key_bytes, share, key_bytes), "share partially overlaps the round-1 key");
+        need(!ranges_meet(sk, sk_bytes, share, key_bytes) && !ranges_meet(e0, e_bytes, share, key_bytes) &&
+                 !ranges_meet(e1, e_bytes, share, key_bytes),
+             "share overlaps an input");
+        c->eng->relin_share(key1, sk, e0, e1, share);
+    });
+}
 int mkckks_encrypt_batch(mkckks_ctx *c, const uint64_t *pk, const uint64_t *pt, const int8_t *v, const int32_t *e0,
                          const int32_t *e1, uint64_t *ct, uint32_t n_ct, uint32_t nl) {
     return guarded([&] {

@@ -22,6 +22,7 @@
 #include "codec_kernels.hpp"
 #include "galois_kernels.hpp"
 #include "tensor_kernels.hpp"
+#include "relshare_kernels.hpp"
 #include "sampler_kernels.hpp"
 #include "arith_probe_kernels.hpp"
 #include "../../include/mkckks.h"
@@ -618,6 +619,10 @@ Knobs Knobs::from_env() {
     if (const char *e = std::getenv("MKCKKS_PLAIN_FUSED")) {
         if (!std::strcmp(e, "0")) k.plain_fused = 0;
         else if (!std::strcmp(e, "1")) k.plain_fused = 1;
+    }
+    if (const char *e = std::getenv("MKCKKS_RELSHARE_FUSED")) {
+        if (!std::strcmp(e, "0")) k.relshare_fused = 0;
+        else if (!std::strcmp(e, "1")) k.relshare_fused = 1;
     }
     if (const char *e = std::getenv("MKCKKS_ICOL_CONV")) {
         if (e[0] >= '0' && e[0] <= '3' && !e[1]) k.icol_conv = e[0] - '0';
@@ -2611,15 +2616,18 @@ void Engine::decrypt(const u64 *ct, const u64 *sk, u64 *m, uint32_t n_ct, uint32
 // 4 each: two-round rows only) and the class as integral constants.  A ring size without such a pair is the caller's
 // to keep away (the `fused` conditions of the three endpoints): it throws here instead of launching nothing.
 template <typename F>
-static void for_each_radix_class(const NttTables &T, uint32_t nl, F &&f) {
+static void for_each_radix_class(const NttTables &T, const ClassMasks &m, F &&f) {
     bool found = false;
     dispatch<2, 3, 4>(fast_log_h(T.log_r1, 1u << T.log_r2), [&](auto col_h) {
         found = dispatch<2, 3, 4>(fast_row(T.log_r2, 1u << T.log_r1), [&](auto row_h) {
-            for_each_class(T, limb_classes(nl, T),
-                           [&](auto ar, unsigned long long mask, uint32_t nsel) { f(col_h, row_h, ar, mask, nsel); });
+            for_each_class(T, m, [&](auto ar, unsigned long long mask, uint32_t nsel) { f(col_h, row_h, ar, mask, nsel); });
         });
     });
     if (!found) throw std::logic_error("fused endpoint needs a radix column pass and a two-round radix row pass");
+}
+template <typename F>
+static void for_each_radix_class(const NttTables &T, uint32_t nl, F &&f) {
+    for_each_radix_class(T, limb_classes(nl, T), f);
 }
 
 static void launch_rerand(LiftIo li, RerandArgs ra, const NttTables &T, uint32_t cnt, hipStream_t s) {
@@ -2814,6 +2822,75 @@ void Engine::fuse_shares(const u64 *shares, u64 *m, uint32_t n_parties, uint32_t
     EwGeom g{ps_.n, nl, ps_.L};
     // every thread reads its words of all shares before it writes them: m may be shares[0]
     k_sum<<<ew_grid(ps_.n, nl, n_ct), EW_THREADS, 0, stream_>>>(shares, m, g, d_limb_, nl, n_parties, (size_t)n_ct * nl * ps_.n);
+    MK_HIP(hipGetLastError());
+}
+
+// ---- collective evaluation keys of a joint key ("collective evaluation keys"); refusals in capi.cpp -------
+
+// all D limbs of an evaluation-key polynomial by arithmetic class: bit i = limb id i, so bits >= L are the P limbs.  It is
+// the selection ntt_launch(.., L, D, ..) makes (virtual slot v >= nl -> limb id L + v - nl) at nl = L, where v == id.
+static ClassMasks qp_classes(uint32_t D, const NttTables &T) {
+    NttIo sel{};
+    sel.nslots = D;
+    sel.nl = T.L;
+    return slot_classes(sel, T);
+}
+
+// k_sum over the 2 * D limb rows of every (key, digit): geometry {n, D, L} makes row r's limb id r % D.  The lazy sum
+// folds every 4 terms, so 64 terms of q - 1 are exact.  A thread reads its words of all parties before it writes them:
+// out may be in[0].
+void Engine::evk_sum(const u64 *in, u64 *out, uint32_t n_parties, uint32_t n_keys) {
+    need_device();
+    if (!n_parties || n_parties > SHAMIR_MAX_PARTIES) throw std::invalid_argument("need 1 <= n_parties <= MKCKKS_MAX_PARTIES");
+    const uint32_t n = ps_.n, D = ps_.D;
+    const size_t rows = (size_t)n_keys * ps_.beta, row_words = (size_t)2 * D * n;
+    EwGeom g{n, D, ps_.L};
+    for (size_t r0 = 0; r0 < rows; r0 += 32768) {  // grid.z
+        const uint32_t cnt = (uint32_t)std::min<size_t>(32768, rows - r0);
+        k_sum<<<ew_grid(n, 2 * D, cnt), EW_THREADS, 0, stream_>>>(in + r0 * row_words, out + r0 * row_words, g, d_limb_, 2 * D,
+                                                                  n_parties, rows * row_words);
+        MK_HIP(hipGetLastError());
+    }
+}
+
+static void launch_relshare(RelshareLift li, RelshareArgs ra, const NttTables &T, uint32_t polys, hipStream_t s) {
+    for_each_radix_class(T, qp_classes(ra.D, T), [&](auto col_h, auto row_h, auto ar, unsigned long long mask, uint32_t nsel) {
+        constexpr int COL_H = decltype(col_h)::value, ROW_H = decltype(row_h)::value, AR = decltype(ar)::value;
+        li.slot_mask = ra.slot_mask = mask;
+        li.nsel = ra.nsel = nsel;
+        k_relshare_col<COL_H, AR><<<dim3(col_tiles<COL_H>(T), nsel, polys), NTT_THREADS, 0, s>>>(li, T);
+        k_relshare_row<ROW_H, AR><<<dim3(row_tiles<ROW_H>(T) * nsel * polys), NTT_THREADS, 0, s>>>(ra, T);
+    });
+}
+
+void Engine::relin_share(const u64 *key1, const u64 *sk, const int32_t *e0, const int32_t *e1, u64 *share) {
+    need_device();
+    const uint32_t n = ps_.n, D = ps_.D, L = ps_.L, beta = ps_.beta;
+    const size_t poly = (size_t)D * n;
+    // fused: lift inside the column pass, key1 * sk + E inside the row pass's copy-out (two-round rows only); the library
+    // switches take the composition
+    const int col_h = fast_log_h(tabs_.log_r1, 1u << tabs_.log_r2), row_h = fast_row(tabs_.log_r2, 1u << tabs_.log_r1);
+    const bool fused = col_h != 0 && row_h >= 2 && row_h <= 4 && !knobs_.generic_ntt && !knobs_.no_fp64 && !knobs_.no_pm &&
+                       knobs_.relshare_fused != 0;
+    u64 *ws = workspace(2 * beta * poly);
+    if (fused) {
+        const RelshareLift li{e0, e1, ws, D, 0, 0};
+        const RelshareArgs ra{ws, key1, sk, share, D, 0, 0};
+        launch_relshare(li, ra, tabs_, 2 * beta, stream_);
+        MK_HIP(hipGetLastError());
+        return;
+    }
+    // the composition (and the definition): the lifts and transforms of the key generators, one k_fma per component
+    u64 *e0e = ws, *e1e = ws + beta * poly;
+    EwGeom g{n, L, L};
+    k_lift<int32_t><<<ew_grid(n, D, beta), EW_THREADS, 0, stream_>>>(e0, e0e, g, d_limb_, D);
+    k_lift<int32_t><<<ew_grid(n, D, beta), EW_THREADS, 0, stream_>>>(e1, e1e, g, d_limb_, D);
+    MK_HIP(hipGetLastError());
+    ntt_launch(ws, 2 * beta, L, D, false, nullptr, nullptr);
+    Opnd s{sk, 0, 0}, none{nullptr, 0, 0};
+    Opnd k0{key1, 2 * poly, 0}, k1{key1 + poly, 2 * poly, 0}, z0{e0e, poly, 0}, z1{e1e, poly, 0};
+    k_fma<<<ew_grid(n, D, beta), EW_THREADS, 0, stream_>>>(k0, s, z0, none, nullptr, 0, share, 2 * poly, 0, g, d_limb_, D);
+    k_fma<<<ew_grid(n, D, beta), EW_THREADS, 0, stream_>>>(k1, s, z1, none, nullptr, 0, share + poly, 2 * poly, 0, g, d_limb_, D);
     MK_HIP(hipGetLastError());
 }
 

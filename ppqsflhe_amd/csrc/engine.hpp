@@ -73,6 +73,9 @@ struct Knobs {
     int icol_conv = -1;          // MKCKKS_ICOL_CONV=0/1/2/3/auto: fp64-class ModUp targets of an all-fp64 digit converted inside the
                                  // inverse column pass of its sources (k_icol_conv); 0: none, 1..3: that many wherever the digit
                                  // has them, default: icol_conv_targets (profiles/icol_conv_ab.txt)
+    int relshare_fused = 2;      // MKCKKS_RELSHARE_FUSED=0/1: relin_share as the composition (k_lift + transform + k_fma) or as
+                                 // k_relshare_col + k_relshare_row; default: fused wherever the other fused endpoints are
+                                 // (profiles/collective_keys_ab.txt)
     static Knobs from_env();
 };
 
@@ -229,6 +232,12 @@ public:
     void tensor_sum(const u64 *a, const u64 *b, u64 *out3, uint32_t n_terms, uint32_t n_ct, uint32_t nl);
     void relinearize(const u64 *in3, const u64 *rlk, u64 *out, uint32_t n_ct, uint32_t nl);
     void mult_relin(const u64 *a, const u64 *b, const u64 *rlk, u64 *out, uint32_t n_ct, uint32_t nl);
+    // collective evaluation keys of a joint key ("collective evaluation keys"; kernels: relshare_kernels.hpp)
+    //   evk_sum:     out[k] = sum_p in[p][k] on all D limbs; in u64[n_parties][n_keys][beta][2][D][N]; out may be in[0]
+    //   relin_share: share[j][c] = key1[j][c] * sk + NTT(e_c[j]) on all D limbs; key1, share u64[beta][2][D][N], sk u64[D][N],
+    //                e0 / e1 int32[beta][N] COEFFICIENT; share may be key1
+    void evk_sum(const u64 *in, u64 *out, uint32_t n_parties, uint32_t n_keys);
+    void relin_share(const u64 *key1, const u64 *sk, const int32_t *e0, const int32_t *e1, u64 *share);
     void lift_ntt(const double *coef, u64 *out, uint32_t n, uint32_t nl);
     void decrypt(const u64 *ct, const u64 *sk, u64 *m, uint32_t n_ct, uint32_t nl);
     // counter-based samplers (ChaCha20 block function under a 256-bit key): element i of stream sid is a pure

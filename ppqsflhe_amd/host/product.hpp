@@ -19,7 +19,7 @@ struct ProductMeta {
     double scale = 0;
 };
 
-// what a key container of `kind` is called in messages (kinds of hostlib.hpp, rotkeys.hpp and this file)
+// what a key container of `kind` is called in messages (kinds of hostlib.hpp, rotkeys.hpp, evalkeys.hpp and this file)
 inline std::string key_kind_name(uint32_t kind) {
     switch (kind) {
     case 2: return "a public key";
@@ -27,6 +27,8 @@ inline std::string key_kind_name(uint32_t kind) {
     case 4: return "a re-encryption key";
     case 9: return "a rotation-key file";
     case KIND_RELIN_KEY: return "a relinearisation key";
+    case 11: return "a rotation-key share";         // evalkeys.hpp: one party's part of a joint key's keys; fuseEvalKeys
+    case 12: return "a relinearisation-key share";  // sums all parties' shares into the key
     default: return "a container of kind " + std::to_string(kind);
     }
 }

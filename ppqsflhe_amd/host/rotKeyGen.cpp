@@ -4,17 +4,22 @@
 // every slot where the client put it).  For every step r the Galois key of g = 5^r mod 2N is the re-encryption key from
 // sigma_g(s) to s (mkckks_galois_keygen); --sum <span> asks for the steps 1, 2, 4, ... below span that slotSum uses.
 // Run by the OWNER of the key the ciphertexts are under (for a server's aggregate: the owner of the common-domain key);
-// <pubkey> is that same party's public key.  Keys for a JOINT key (threshold decryption) need a collective protocol and
-// are not generated here.  The file holds no secret (rotkeys.hpp).
+// <pubkey> is that same party's public key.  The file holds no secret (rotkeys.hpp).
+// Keys for a JOINT key (keyGen --join: nobody holds s) are made collectively: every party runs the same command with
+// its OWN private key, the JOINT public key and a trailing `--share`; the file is then a rotation-key share (kind 11,
+// evalkeys.hpp), which slotSum refuses, and fuseEvalKeys sums the n parties' shares into the rotation-key file.  The
+// flag changes nothing but the container kind.
+#include "evalkeys.hpp"
 #include "rotkeys.hpp"
 using namespace mkh;
 
 int main(int argc, char *argv[]) {
     auto usage = [&] {
-        std::cerr << "Usage: " << argv[0] << " <cc.json> <privkey> <pubkey> <rotkeys_out> (--steps r1,r2,... | --sum <span>)" << std::endl;
+        std::cerr << "Usage: " << argv[0] << " <cc.json> <privkey> <pubkey> <rotkeys_out> (--steps r1,r2,... | --sum <span>) [--share]" << std::endl;
         return 1;
     };
-    if (argc != 7) return usage();
+    const bool share = argc == 8 && std::string(argv[7]) == "--share";
+    if (argc != 7 && !share) return usage();
     const std::string cc_path = argv[1], sk_path = argv[2], pk_path = argv[3], out_path = argv[4], mode = argv[5], arg = argv[6];
     if (mode != "--steps" && mode != "--sum") return usage();
     std::vector<int32_t> steps;
@@ -86,12 +91,13 @@ int main(int argc, char *argv[]) {
             std::cout << "[rotkeygen] step " << r << ": Galois element " << g << "\n";
         }
         try {
-            write_rot_keys(out_path, rk, N, D, 2 * beta);
+            write_rot_keys(out_path, rk, N, D, 2 * beta, share ? (uint32_t)KIND_ROTKEY_SHARE : (uint32_t)KIND_ROTKEYS);
         } catch (const std::exception &) {
             std::cerr << "[rotkeygen] ERROR: Failed to save rotation keys to " << out_path << std::endl;
             return 1;
         }
-        std::cout << "[rotkeygen] " << rk.keys.size() << " rotation key(s) saved to " << out_path << std::endl;
+        std::cout << "[rotkeygen] " << rk.keys.size() << (share ? " rotation-key share(s) saved to " : " rotation key(s) saved to ")
+                  << out_path << std::endl;
     } catch (const std::exception &e) {
         std::cerr << "[rotkeygen] ERROR: " << e.what() << std::endl;
         return 1;

@@ -16,10 +16,12 @@ struct RotKeys {
     std::map<uint32_t, std::vector<uint64_t>> keys;  // Galois element -> key
 };
 
-inline void write_rot_keys(const std::string &path, const RotKeys &rk, uint32_t ring_dim, uint32_t limbs, uint32_t parts) {
+// kind: KIND_ROTKEYS, or the rotation-key share's (evalkeys.hpp: one party's part of a joint key's keys, same layout)
+inline void write_rot_keys(const std::string &path, const RotKeys &rk, uint32_t ring_dim, uint32_t limbs, uint32_t parts,
+                           uint32_t kind = KIND_ROTKEYS) {
     BlobHeader h{};
     std::memcpy(h.magic, "MKCK", 4);
-    h.version = 1; h.kind = KIND_ROTKEYS; h.ring_dim = ring_dim; h.limbs = limbs; h.parts = parts;
+    h.version = 1; h.kind = kind; h.ring_dim = ring_dim; h.limbs = limbs; h.parts = parts;
     h.slots = (uint32_t)rk.keys.size();
     std::unique_ptr<FILE, FileCloser> f(std::fopen(path.c_str(), "wb"));
     if (!f) throw std::runtime_error("cannot write " + path);
@@ -32,12 +34,17 @@ inline void write_rot_keys(const std::string &path, const RotKeys &rk, uint32_t 
 }
 
 // the error text, empty on success
-inline std::string read_rot_keys(const std::string &path, uint32_t ring_dim, uint32_t limbs, uint32_t parts, RotKeys &out) {
+inline std::string read_rot_keys(const std::string &path, uint32_t ring_dim, uint32_t limbs, uint32_t parts, RotKeys &out,
+                                 uint32_t kind = KIND_ROTKEYS) {
     std::unique_ptr<FILE, FileCloser> f(std::fopen(path.c_str(), "rb"));
     if (!f) return "cannot open rotation keys " + path;
-    BlobHeader h;
-    if (std::fread(&h, sizeof h, 1, f.get()) != 1 || std::memcmp(h.magic, "MKCK", 4) || h.version != 1 || h.kind != KIND_ROTKEYS)
+    BlobHeader h{};
+    if (std::fread(&h, sizeof h, 1, f.get()) != 1 || std::memcmp(h.magic, "MKCK", 4) || h.version != 1 || h.kind != kind) {
+        // one party's share of a joint key's rotation keys (kind 11, evalkeys.hpp) used as a key would give noise
+        if (kind == KIND_ROTKEYS && !std::memcmp(h.magic, "MKCK", 4) && h.version == 1 && h.kind == 11)
+            return path + " is a rotation-key share, not a rotation-key file (fuseEvalKeys sums the parties' shares into one)";
         return path + " is not a rotation-key file";
+    }
     if (h.ring_dim != ring_dim || h.limbs != limbs || h.parts != parts) return "rotation keys do not match the CryptoContext";
     if (h.slots > 64) return "rotation-key file claims " + std::to_string(h.slots) + " entries (at most 64)";
     const size_t words = (size_t)parts * limbs * ring_dim;
