@@ -373,6 +373,46 @@ int mkckks_rotate_batch(mkckks_ctx *c, const uint64_t *d_ct, const uint64_t *d_e
 int mkckks_slot_sum_batch(mkckks_ctx *c, const uint64_t *d_ct, const uint64_t *d_evks, uint64_t *d_out, uint32_t n_ct,
                           uint32_t nl, uint32_t span);
 
+/* ==== linear transforms by diagonals, double hoisted: EvalLinearTransform over cc->EvalFastRotationPrecompute /
+ * cc->EvalFastRotation (upstream ckksrns-advancedshe: EvalLinearTransform, EvalFastRotationExt) ==========================
+ * Upstream calls the reference never makes.  They apply a PUBLIC linear map to an encrypted vector by the diagonal
+ * method,
+ *     out[j] = sum_r diag_r[j] * in[(j + r) mod N/2],
+ * which is what projecting the aggregate on a public basis, undoing a sketch, mixing layers, applying a banded or block
+ * matrix to every block of the update and several inner products with public vectors at once all come down to.
+ * Double hoisting: the ModUp digits of c1 are made ONCE per ciphertext; every rotation is only an eval-key inner product
+ * on permuted digits; the plaintext diagonals are multiplied in while the sum is still over the extended basis Q_l P; ONE
+ * ModDown per component closes the transform.  Against the composition (mkckks_rotate_batch + mkckks_mult_plain_batch per
+ * diagonal, mkckks_eval_sum_batch) that is 1 inverse transform of c1 instead of n_rot, 1 ModUp instead of n_rot and 2
+ * ModDowns instead of 2 n_rot; ModDown's rounding error enters once, after the plaintext products, not n_rot times each
+ * multiplied by a plaintext of the size of the scaling factor.
+ *
+ * (the plaintext side of EvalLinearTransformPrecompute: MakeCKKSPackedPlaintext over the extended basis, upstream
+ * "MakeAuxPlaintext") What mkckks_encode_batch does, over Q_l P: d_pt out u64[n][nl+K][N], EVALUATION, canonical; slots
+ * 0 .. nl-1 are the Q limbs, bit-identical to mkckks_encode_batch, slots nl .. nl+K-1 are the P limbs, the residues of
+ * the same rounded integer polynomial. */
+int mkckks_encode_ext_batch(mkckks_ctx *c, const double *d_vals, uint64_t *d_pt, uint32_t n, uint32_t nl, double scale);
+/* (EvalLinearTransform with EvalFastRotationExt and one closing KeySwitchDown) d_ct, d_out u64[n_ct][2][nl][N], not
+ * overlapping; d_evks u64[n_rot][beta][2][D][N], the Galois key of h_g[r] in slot r (the layout of mkckks_slot_sum_batch);
+ * d_pts u64[n_rot][nl+K][N] from mkckks_encode_ext_batch, shared by all ciphertexts; h_g a HOST array of n_rot Galois
+ * elements.  g = 1 means "no rotation": its key slot is never read (d_evks may be null when every element is 1).
+ * Duplicate elements are allowed.  Definition, bit for bit: with m_i the modulus of extended slot i, d_j the digits
+ * mkckks_modup_batch returns for c1, sigma_g the gather of mkckks_automorphism_batch and (kb, ka)_{r,j} key r,
+ *     A_b[i] = sum_r pt_r[i] ( sum_j sigma_{g_r}(d_j[i]) kb_{r,j}[i] + [i < nl] [P]_{q_i} sigma_{g_r}(c0[i]) )  mod m_i
+ *     A_a[i] = sum_r pt_r[i] ( sum_j sigma_{g_r}(d_j[i]) ka_{r,j}[i] )                                          mod m_i
+ *     (for g_r = 1 the inner key sum is [i < nl] [P]_{q_i} c1[i] in A_a and absent from A_b)
+ *     d_out = ( ModDown(A_b), ModDown(A_a) ), each word for word what mkckks_moddown_batch returns.
+ * P x on the Q limbs passes through ModDown exactly as + x.  Residues are canonical and every sum is exact mod m_i.
+ * Scale and level: for an input at level L - nl with scale S encode the diagonals at sf(level) (noiseScaleDeg 1) or
+ * sf(level + 1) (noiseScaleDeg 2), the rule of mkckks_mult_plain_batch; the output has nl limbs at scale S sf and the
+ * caller rescales with mkckks_rescale_batch.  Headroom is the caller's:
+ *     log2(S sf max_j sum_r |diag_r[j]|) < log2(q_0 ... q_{nl-1}) - 1.
+ * Refusals as in the rotation block: MKCKKS_E_INVALID for null pointers, nl outside [1, L], an even g or g >= 2N, an
+ * output that overlaps an input, arrays that are not 16-byte aligned, more than 6 key-switch digits; n_rot == 0 or
+ * n_ct == 0 is a no-op; a host-only context gives MKCKKS_E_NODEVICE. */
+int mkckks_linear_transform_batch(mkckks_ctx *c, const uint64_t *d_ct, const uint64_t *d_evks, const uint64_t *d_pts,
+                                  const uint32_t *h_g, uint64_t *d_out, uint32_t n_rot, uint32_t n_ct, uint32_t nl);
+
 /* ==== ciphertext products: cc->EvalMultKeyGen / cc->EvalMult(ct, ct) / cc->Relinearize / cc->EvalInnerProduct(ct, ct) ===
  * Upstream CryptoContext calls the reference never makes: everything its mains compute is linear in the encrypted
  * values.  With them the server can form products of two ENCRYPTED vectors: squared norms, the alignment with an

@@ -91,6 +91,8 @@ SYMBOLS = {
     "mkckks_galois_keygen": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp]),
     "mkckks_rotate_batch": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u32]),
     "mkckks_slot_sum_batch": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u32]),
+    "mkckks_encode_ext_batch": (_int, [_vp, _vp, _vp, _u32, _u32, _dbl]),
+    "mkckks_linear_transform_batch": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32]),
     "mkckks_relin_keygen": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mkckks_tensor_sum_batch": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u32]),
     "mkckks_relinearize_batch": (_int, [_vp, _vp, _vp, _vp, _u32, _u32]),
@@ -587,6 +589,19 @@ class Context:
     def slot_sum(self, ct, evks, out, n_ct, nl, span):
         """out = ct + its rotations by 1 .. span - 1; evks [log2 span][beta][2][D][N], key k for step 2^k."""
         self._check(self._L.mkckks_slot_sum_batch(self._h, _ptr(ct), _ptr(evks), _ptr(out), n_ct, nl, span))
+
+    # ---- linear transforms (include/mkckks.h: "linear transforms by diagonals, double hoisted")
+    def encode_ext(self, vals, pt, n, nl, scale):
+        """encode over the extended basis: pt u64[n][nl+K][N], Q limbs (those of encode) then P limbs."""
+        self._check(self._L.mkckks_encode_ext_batch(self._h, _ptr(vals), _ptr(pt), n, nl, float(scale)))
+
+    def linear_transform(self, ct, evks, pts, gs, out, n_ct, nl):
+        """out[b] = sum_r pts[r] * Rotate(ct[b], gs[r]) before the rescale, double hoisted: evks [n_rot][beta][2][D][N],
+        pts [n_rot][nl+K][N] from encode_ext, gs the n_rot Galois elements (host integers; 1: no rotation, no key)."""
+        gs = [int(g) for g in gs]
+        arr = (C.c_uint32 * max(1, len(gs)))(*gs)
+        self._check(self._L.mkckks_linear_transform_batch(self._h, _ptr(ct), _ptr(evks), _ptr(pts), arr, _ptr(out), len(gs),
+                                                          n_ct, nl))
 
     # ---- ciphertext products (include/mkckks.h: "ciphertext products")
     def relin_keygen(self, s, pk, u, e0, e1, evk):

@@ -500,6 +500,39 @@ static bool ranges_meet(const void *x, size_t x_bytes, const void *y, size_t y_b
 static void need_aligned16(std::initializer_list<const void *> ptrs) {
     for (const void *p : ptrs) need(((uintptr_t)p & 15) == 0, "ciphertext arrays must be 16-byte aligned");
 }
+// ---- linear transforms: every refusal is decided here, before a device is asked for (h_g is a host array and is read)
+int mkckks_encode_ext_batch(mkckks_ctx *c, const double *vals, uint64_t *pt, uint32_t n, uint32_t nl, double scale) {
+    return guarded([&] {
+        need(c && vals && pt, "null argument");
+        need(scale > 0, "scale must be positive");
+        need(nl >= 1 && nl <= c->eng->params().L, "nl out of range");
+        c->eng->encode_ext(vals, pt, n, nl, scale);
+    });
+}
+int mkckks_linear_transform_batch(mkckks_ctx *c, const uint64_t *ct, const uint64_t *evks, const uint64_t *pts,
+                                  const uint32_t *h_g, uint64_t *out, uint32_t n_rot, uint32_t n_ct, uint32_t nl) {
+    return guarded([&] {
+        need(c && ct && pts && h_g && out, "null argument");
+        const mk::ParamSet &ps = c->eng->params();
+        need(nl >= 1 && nl <= ps.L, "nl out of range");
+        if (!n_rot || !n_ct) return;
+        bool keyed = false;
+        for (uint32_t r = 0; r < n_rot; ++r) {
+            need_galois(ps, h_g[r]);
+            keyed = keyed || h_g[r] != 1u;
+        }
+        need(evks || !keyed, "null argument");  // a transform of unrotated terms alone reads no key
+        need_aligned16({ct, evks, pts, out});
+        const size_t ct_bytes = poly_bytes((unsigned __int128)n_ct * 2, nl, ps.n);
+        need(!ranges_meet(ct, ct_bytes, out, ct_bytes), "output overlaps input");
+        need(!ranges_meet(pts, poly_bytes(n_rot, nl + ps.K, ps.n), out, ct_bytes), "output overlaps the plaintexts");
+        if (keyed)
+            need(!ranges_meet(evks, poly_bytes((unsigned __int128)n_rot * ps.beta * 2, ps.D, ps.n), out, ct_bytes),
+                 "output overlaps the keys");
+        need(ps.num_parts(nl) <= 6, "more than 6 key-switch digits unsupported");
+        c->eng->linear_transform(ct, evks, pts, h_g, out, n_rot, n_ct, nl);
+    });
+}
 int mkckks_relin_keygen(mkckks_ctx *c, const int8_t *s, const uint64_t *pk, const int8_t *u, const int32_t *e0,
                         const int32_t *e1, uint64_t *evk) {
     return guarded([&] {

@@ -22,6 +22,7 @@
 #include "codec_kernels.hpp"
 #include "galois_kernels.hpp"
 #include "tensor_kernels.hpp"
+#include "lintrans_kernels.hpp"
 #include "relshare_kernels.hpp"
 #include "sampler_kernels.hpp"
 #include "arith_probe_kernels.hpp"
@@ -627,6 +628,9 @@ Knobs Knobs::from_env() {
     if (const char *e = std::getenv("MKCKKS_ICOL_CONV")) {
         if (e[0] >= '0' && e[0] <= '3' && !e[1]) k.icol_conv = e[0] - '0';
     }
+    if (const char *e = std::getenv("MKCKKS_LT_ORDER")) {
+        if (e[0] >= '0' && e[0] <= '2' && !e[1]) k.lt_order = e[0] - '0';
+    }
     return k;
 }
 
@@ -741,7 +745,7 @@ Engine::~Engine() {
     (void)hipDeviceSynchronize();
     for (void *p : {(void *)d_limb_, (void *)d_tw_, (void *)d_tw_sh_, (void *)d_itw_, (void *)d_itw_sh_, (void *)ws_,
                     (void *)d_twb_, (void *)d_itwb_, (void *)d_stamps_,
-                    (void *)d_rot_, (void *)d_ksi_, (void *)d_gal_s_})
+                    (void *)d_rot_, (void *)d_ksi_, (void *)d_gal_s_, (void *)d_lt_g_})
         if (p) (void)hipFree(p);
     for (void *p : owned_) (void)hipFree(p);
     for (auto &kv : wt_cache_) (void)hipFree(kv.second);
@@ -2472,6 +2476,61 @@ void Engine::slot_sum(const u64 *ct, const u64 *evks, u64 *out, uint32_t n_ct, u
     }
 }
 
+// ---- linear transforms ("linear transforms"); refusals of the arguments are decided in capi.cpp -------------
+
+// EvalLinearTransform's shape with EvalFastRotation's hoisting, both hoists: per chunk one ModUp of c1 (modup_core, the
+// digits of mkckks_modup_batch), one launch of k_lt_accum over the extended basis (every rotation an eval-key inner product
+// on permuted digits, the plaintext diagonal multiplied in before the sum leaves Q_l P), one ModDown of both components
+// (moddown_core, the words of mkckks_moddown_batch).
+void Engine::linear_transform(const u64 *ct, const u64 *evks, const u64 *pts, const uint32_t *h_g, u64 *out, uint32_t n_rot,
+                              uint32_t n_ct, uint32_t nl) {
+    need_device();
+    check_nl(nl);
+    if (!n_rot || !n_ct) return;
+    const uint32_t n = ps_.n, K = ps_.K, ext = nl + K, nparts = ps_.num_parts(nl);
+    for (uint32_t r = 0; r < n_rot; ++r)
+        if (!galois_valid(h_g[r], ps_.log_n)) throw std::invalid_argument("Galois element must be odd and below 2N");
+    if (nparts > 6) throw std::invalid_argument("more than 6 key-switch digits unsupported");
+    if (n_rot > lt_g_cap_) {
+        MK_HIP(hipStreamSynchronize(stream_));
+        if (d_lt_g_) MK_HIP(hipFree(d_lt_g_));
+        d_lt_g_ = nullptr;
+        lt_g_cap_ = 0;
+        MK_HIP(hipMalloc(&d_lt_g_, (size_t)n_rot * sizeof(uint32_t)));
+        lt_g_cap_ = n_rot;
+    }
+    // stream-ordered behind the previous call's kernel; the wait keeps the caller's array free to change on return
+    MK_HIP(hipMemcpyAsync(d_lt_g_, h_g, (size_t)n_rot * sizeof(uint32_t), hipMemcpyHostToDevice, stream_));
+    MK_HIP(hipStreamSynchronize(stream_));
+    std::vector<u64> pm(nl);
+    for (uint32_t i = 0; i < nl; ++i) pm[i] = ps_.p_mod(i);
+    const u64 *pmod = limb_vector("pmod_" + std::to_string(nl), pm);
+
+    const uint32_t log_t = std::min(ps_.log_n, LT_LOG_TILE);
+    const size_t ct_words = (size_t)2 * nl * n;
+    const uint32_t chunk = std::min(knobs_.chunk, n_ct);
+    const size_t w_coef = (size_t)chunk * nl * n, w_dig = (size_t)chunk * nparts * ext * n;
+    const size_t w_til = (size_t)chunk * 2 * ext * n, w_pc = (size_t)chunk * 2 * K * n, w_conv = (size_t)chunk * 2 * nl * n;
+    u64 *ws = workspace(w_coef + w_dig + w_til + w_pc + w_conv);
+    u64 *coef = ws, *dig = coef + w_coef, *til = dig + w_dig, *pc = til + w_til, *conv = pc + w_pc;
+    for (uint32_t done = 0; done < n_ct; done += chunk) {
+        const uint32_t cnt = std::min(chunk, n_ct - done);
+        const u64 *c = ct + done * ct_words;
+        modup_core(c + (size_t)nl * n, ct_words, coef, dig, cnt, nl);
+        LtArgs a{c, dig, evks, pts, d_lt_g_, pmod, til, (size_t)ps_.beta * 2 * ps_.D * n,
+                 n_rot, cnt, nl, ext, ps_.L, ps_.D, ps_.alpha, ps_.log_n, log_t,
+                 ext << (ps_.log_n - log_t), knobs_.lt_order == 1 ? 1u : cnt, knobs_.lt_order == 1 ? 1u : 0u,
+                 knobs_.lt_order == 2 ? 0u : 1u};
+        const uint64_t blocks = (uint64_t)((a.groups + LT_XCDS - 1) / LT_XCDS * LT_XCDS) * a.members;
+        if (blocks > 0x7fffffffu) throw std::invalid_argument("batch too large for one launch");
+        dispatch<1, 2, 3, 4, 5, 6>(nparts, [&](auto np) {
+            k_lt_accum<decltype(np)::value><<<dim3((unsigned)blocks), LT_THREADS, 0, stream_>>>(a, d_limb_);
+        });
+        MK_HIP(hipGetLastError());
+        moddown_core(til, pc, conv, out + done * ct_words, (size_t)nl * n, nullptr, 0, 2 * cnt, nl, false);
+    }
+}
+
 // ---- ciphertext products ("ciphertext products"); overlaps and alignment are refused in capi.cpp ------------
 
 // the relinearisation key: the re-encryption key from s^2 to s, i.e. rekeygen with NTT(s_old) replaced by NTT(s)^2
@@ -3054,6 +3113,27 @@ void Engine::encode(const double *vals, u64 *pt, uint32_t cnt, uint32_t nl, doub
     k_lift<double><<<ew_grid(n, nl, cnt), EW_THREADS, 0, stream_>>>(coef, pt, g, d_limb_, nl);
     MK_HIP(hipGetLastError());
     ntt_launch(pt, cnt, nl, nl, false, nullptr, nullptr);
+}
+
+// encode over Q_l P: the same rounded integer polynomial, lifted to every limb of the extended basis
+void Engine::encode_ext(const double *vals, u64 *pt, uint32_t cnt, uint32_t nl, double scale) {
+    need_device();
+    check_nl(nl);
+    if (!cnt) return;
+    const uint32_t n = ps_.n, slots = n / 2, ext = nl + ps_.K;
+    CodecTables t{d_rot_, reinterpret_cast<const double2 *>(d_ksi_), slots, ps_.log_n - 1, 2 * n};
+    u64 *ws = workspace((size_t)cnt * n * 2 + (size_t)cnt * n);
+    double2 *v = reinterpret_cast<double2 *>(ws);
+    double *coef = reinterpret_cast<double *>(ws + (size_t)cnt * n * 2);
+    const dim3 gs((slots + 255) / 256, cnt), gh((slots / 2 + 255) / 256, cnt);
+    k_codec_load<<<gs, 256, 0, stream_>>>(vals, v, slots);
+    for (uint32_t len = slots; len >= 2; len >>= 1) k_fft_special_inv_stage<<<gh, 256, 0, stream_>>>(v, t, len);
+    k_codec_to_coef<<<gs, 256, 0, stream_>>>(v, coef, t, scale);
+    MK_HIP(hipGetLastError());
+    EwGeom g{n, nl, ps_.L};
+    k_lift<double><<<ew_grid(n, ext, cnt), EW_THREADS, 0, stream_>>>(coef, pt, g, d_limb_, ext);
+    MK_HIP(hipGetLastError());
+    ntt_launch(pt, cnt, nl, ext, false, nullptr, nullptr);
 }
 
 const u64 *Engine::garner_table(uint32_t nl) {

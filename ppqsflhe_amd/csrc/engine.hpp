@@ -76,6 +76,10 @@ struct Knobs {
     int relshare_fused = 2;      // MKCKKS_RELSHARE_FUSED=0/1: relin_share as the composition (k_lift + transform + k_fma) or as
                                  // k_relshare_col + k_relshare_row; default: fused wherever the other fused endpoints are
                                  // (profiles/collective_keys_ab.txt)
+    int lt_order = 0;            // MKCKKS_LT_ORDER=0/1/2: how k_lt_accum reuses the key and plaintext tiles the ciphertexts of a
+                                 // chunk share; 0: the workgroups of one (limb, tile) are neighbours on one XCD, 1: one
+                                 // workgroup walks the chunk's ciphertexts, 2: ciphertext-major grid, no reuse intended
+                                 // (profiles/linear_transform_ab.txt)
     static Knobs from_env();
 };
 
@@ -223,6 +227,14 @@ public:
                        u64 *evk);
     void rotate(const u64 *ct, const u64 *evk, u64 *out, uint32_t n_ct, uint32_t nl, uint32_t g);
     void slot_sum(const u64 *ct, const u64 *evks, u64 *out, uint32_t n_ct, uint32_t nl, uint32_t span);
+    // linear transforms by diagonals, double hoisted ("linear transforms"; kernel: lintrans_kernels.hpp)
+    //   encode_ext:       encode over the extended basis: pt u64[n][nl+K][N] EVALUATION, Q limbs then P limbs
+    //   linear_transform: out[b] = (ModDown(A_b), ModDown(A_a)) with A of lintrans_kernels.hpp; evks u64[n_rot][beta][2][D][N],
+    //                     pts u64[n_rot][nl+K][N] shared by the ciphertexts, h_g: n_rot Galois elements on the HOST (1: no
+    //                     rotation, its key is never read); one ModUp per ciphertext, one ModDown per component
+    void encode_ext(const double *vals, u64 *pt, uint32_t n, uint32_t nl, double scale);
+    void linear_transform(const u64 *ct, const u64 *evks, const u64 *pts, const uint32_t *h_g, u64 *out, uint32_t n_rot,
+                          uint32_t n_ct, uint32_t nl);
     // ciphertext products ("ciphertext products"; kernel: tensor_kernels.hpp)
     //   relin_keygen: evk = rekeygen with NTT(s_old) replaced by NTT(s)^2 (the re-encryption key from s^2 to s)
     //   tensor_sum:   out3[b] = sum_t (a0 b0, a0 b1 + a1 b0, a1 b1); a, b u64[n_terms][n_ct][2][nl][N], out3 u64[n_ct][3][nl][N]
@@ -355,6 +367,8 @@ private:
     u64 *wtmp_ = nullptr;                    // chunk_buffer: a chunk with c0 scaled (reencrypt_wsum), permuted (slot_sum), or d2 (mult_relin)
     size_t wtmp_words_ = 0;
     int8_t *d_gal_s_ = nullptr;  // galois_keygen: sigma_g(s)
+    uint32_t *d_lt_g_ = nullptr;  // linear_transform: the call's Galois elements (grow-only)
+    size_t lt_g_cap_ = 0;
     std::vector<void *> owned_;
 };
 
