@@ -13,7 +13,10 @@ GPU (`-m gpu`): the class assertion first, so that an entry which drifts out of 
 the default path, then one battery per entry.  Everything is compared word for word (np.array_equal) with the oracle;
 the one floating-point comparison is the decode, within the 2^-40 of test_gpu_parity.test_encode_decode_on_device: both
 sides decode the same integers, so the bound does not depend on the scale.  Inputs and oracle results of the key-switch
-step are computed once per entry (`ks_case`) and shared with the switch tests."""
+step are computed once per entry (`ks_case`) and shared with the switch tests.
+
+The entry points added since (plaintext products, weighted aggregation, rotations, ciphertext products, collective keys,
+the share protocols, linear transforms) run on the same table in tests/test_lattice_evaluation.py."""
 import numpy as np
 import pytest
 
