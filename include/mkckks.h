@@ -458,6 +458,85 @@ int mkckks_relinearize_batch(mkckks_ctx *c, const uint64_t *d_in3, const uint64_
 int mkckks_mult_relin_batch(mkckks_ctx *c, const uint64_t *d_a, const uint64_t *d_b, const uint64_t *d_rlk, uint64_t *d_out,
                             uint32_t n_ct, uint32_t nl);
 
+/* ==== polynomial evaluation: cc->EvalPoly (ckksrns-advancedshe EvalPolyPS), fused Paterson-Stockmeyer products ==========
+ * A non-linear function of an encrypted slot: p(x) = c_0 + c_1 x + ... + c_d x^d in the power basis, 2 <= d <= 63,
+ * applied to every slot of every ciphertext: clipping by a polynomial approximation of min(1, C / sqrt(t)) at an
+ * encrypted squared norm, smooth signs, activations after a linear transform.  Upstream call the reference never makes.
+ *
+ * Input: ciphertexts x at nl limbs, noiseScaleDeg 1, scale S_1 (a host double).
+ * Plan.  B = the smallest power of two with B^2 >= d + 1 (2, 4 or 8), G = ceil((d + 1) / B), 2 <= G <= B; coefficients
+ * beyond d are zero.  p(x) = sum_{j<G} sum_{i<B} c_{jB+i} x^i y^j with y = x^B.
+ * Power ladder of a base z: z^1 = z; for k >= 2 with i = ceil(k / 2), j = k - i:
+ *     z^k = mkckks_rescale_batch(mkckks_mult_relin_batch(z^i, prefix(z^j, nl_i))) at nl_k = nl_i - 1 limbs,
+ *     S_k = S_i * S_j / q_{nl_i - 1}, computed in that order in doubles,
+ * prefix(., m) = the first m limbs of both components (the level cut of mkckks_compress_batch, without its rescale).  The
+ * depth of z^k is ceil(log2 k).  Babies x^1 .. x^{B-1}; y = x^{B/2} x^{B/2} by the same rule (it is power B of the ladder
+ * on x); giants y^1 .. y^{G-1} by the ladder on y.  x^0 and y^0 are the virtual ciphertext "1" with scale 1.
+ * nl_T = the smallest limb count among babies and giants = nl - log2 B - ceil(log2(G - 1)) (ceil(log2 1) = 0).
+ * Constants.  nl_out = nl_T - 2 >= 1, else the call is refused.  S_out = the standard scale of the output's level,
+ * mkckks_scaling_factor(L - nl_out): the result adds to and multiplies with any ordinary ciphertext there.  With
+ * Sigma = S_out * q_{nl_T-1} * q_{nl_T-2}:  w_{j,i} = c_{jB+i} * (Sigma / (S_{x^i} * S_{y^j})),  M_{j,i} = rint(w_{j,i}) as an
+ * integer (a double at or above 2^53 is one, so M is exact at any size), used as its residue mod each q_t, t < nl_T; a
+ * negative M is q - (|M| mod q).  A non-finite w, or |w| >= q_0 ... q_{nl_T-1} / 2, is MKCKKS_E_INVALID.
+ * Fused outer sum, on the first nl_T limbs, pointwise mod q_t, b_i = prefix(x^i), g_j = prefix(y^j):
+ *     Q_j = sum_{i>=1} M_{j,i} b_i                                              (two components, never stored)
+ *     (d0, d1, d2) = sum_{j>=1} [Q_j (x) g_j + M_{j,0} (g_j, 0)] + (Q_0, 0) + (M_{0,0}, 0, 0)
+ * (x) the tensor product of mkckks_tensor_sum_batch; M_{0,0} is added to every word of d0 (a constant polynomial is a
+ * constant vector in EVALUATION form).  All results canonical; every sum is exact mod q_t.
+ * Close: mkckks_relinearize_batch at nl_T, mkckks_rescale_batch at nl_T and at nl_T - 1: u64[n_ct][2][nl_out][N] at scale
+ * S_out, noiseScaleDeg 1.
+ * Cost: depth log2 B + ceil(log2(G - 1)) + 2 (up to two levels more than the recursive form's ceil(log2(d + 1)), spent
+ * for ONE fused pass); (B - 1) + (G - 2) + 1 relinearisations against d - 1 for Horner's rule (d = 15: 6 against 14).
+ * Headroom, the caller's: Sigma * sum_k |c_k| A^k < q_0 ... q_{nl_T-1} / 2 for |x| <= A; the library cannot check it
+ * (evalPoly --max-abs does).  Noise: that of the ladder's products, amplified by |p'(x)|.
+ * Refusals of the compute calls follow the products block: MKCKKS_E_INVALID for null pointers, arrays that are not 16-byte
+ * aligned, an output that overlaps an input, limb counts outside their ranges, more key-switch digits than
+ * mkckks_relinearize_batch accepts; a zero n_ct is a no-op; a host-only context gives MKCKKS_E_NODEVICE.
+ * MKCKKS_POLY_FUSED=0 runs the outer sum as the composition (mkckks_eval_wsum_batch's kernel per giant index on packed
+ * prefix copies, mkckks_tensor_sum_batch's kernel, the constant column and term), =1 as the fused kernel; unset, the
+ * engine chooses.  The bits are the same. */
+#define MKCKKS_POLY_MAX_DEGREE 63
+#define MKCKKS_POLY_MAX_B 8
+struct mkckks_poly_plan {
+    uint32_t B, G;        /* baby and giant counts: x^0 .. x^{B-1}, y^0 .. y^{G-1}                    */
+    uint32_t nl_T;        /* limbs of the outer sum                                                    */
+    uint32_t nl_out;      /* limbs of the result                                                       */
+    uint32_t n_relin;     /* relinearisations: (B - 1) + (G - 2) + 1                                   */
+    uint32_t depth;       /* levels consumed: nl - nl_out                                              */
+    uint32_t baby_nl[MKCKKS_POLY_MAX_B - 1];  /* limbs of x^1 .. x^{B-1} (the first B - 1 entries)   */
+    uint32_t giant_nl[MKCKKS_POLY_MAX_B - 1]; /* limbs of y^1 .. y^{G-1} (the first G - 1 entries)   */
+};
+/* Host-only and pure (works on a device = -1 context).  MKCKKS_E_INVALID for a degree outside [2, 63], nl outside [1, L]
+ * or a plan with nl_out < 1 (the message names the limbs needed).  The function and the structure share their name: the
+ * structure is always written `struct mkckks_poly_plan`. */
+int mkckks_poly_plan(const mkckks_ctx *c, uint32_t degree, uint32_t nl, struct mkckks_poly_plan *out);
+/* The ladder: d_out = z^1 .. z^n_pow of d_z u64[n_ct][2][nl][N] at scale scale_in.  Power k is packed
+ * u64[n_ct][2][nl_k][N] (nl_k = nl - ceil(log2 k)) directly behind power k - 1: its word offset is
+ * n_ct * 2 * N * (nl_1 + ... + nl_{k-1}), derivable from h_nl_out.  h_nl_out / h_scale_out (HOST, n_pow entries each,
+ * either may be null) receive nl_k and S_k.  1 <= n_pow <= 64 with nl - ceil(log2 n_pow) >= 1.  Bit-identical to the loop
+ * of packed prefix copy + mkckks_mult_relin_batch + mkckks_rescale_batch.  d_out overlaps neither d_z nor the key. */
+int mkckks_powers_batch(mkckks_ctx *c, const uint64_t *d_z, const uint64_t *d_rlk, uint64_t *d_out, uint32_t n_ct,
+                        uint32_t nl, uint32_t n_pow, double scale_in, uint32_t *h_nl_out, double *h_scale_out);
+/* Host-only.  h_w (HOST, double[G][B]) receives w_{j,i}, *scale_out receives S_out: the ladder's scale arithmetic
+ * reproduced on the host.  h_coef: degree + 1 coefficients; a zero coefficient gives an exact zero; a non-finite one is
+ * MKCKKS_E_INVALID, as is everything mkckks_poly_plan refuses. */
+int mkckks_poly_weights(const mkckks_ctx *c, const double *h_coef, uint32_t degree, uint32_t nl, double scale_in,
+                        double *h_w, double *scale_out);
+/* The fused outer sum for caller-supplied operands and weights: d_baby = x^1 .. x^{B-1} and d_giant = y^1 .. y^{G-1},
+ * each packed like the output of mkckks_powers_batch with the limb counts h_baby_nl[B-1] / h_giant_nl[G-1] (HOST; every
+ * one in [nl_T, L]), read in place at their first nl_T limbs; h_w HOST double[G][B].  B in {2, 4, 8}, 2 <= G <= B.
+ * d_out3 u64[n_ct][3][nl_T][N] overlaps no input. */
+int mkckks_poly_tensor_batch(mkckks_ctx *c, const uint64_t *d_baby, const uint32_t *h_baby_nl, const uint64_t *d_giant,
+                             const uint32_t *h_giant_nl, const double *h_w, uint64_t *d_out3, uint32_t B, uint32_t G,
+                             uint32_t n_ct, uint32_t nl_T);
+/* The whole algorithm, workspace-chunked like mkckks_mult_relin_batch: d_out u64[n_ct][2][nl_out][N] = p(d_ct), scale
+ * *scale_out (nullable) = S_out.  Bit-identical to mkckks_powers_batch (on x with n_pow = B, then on y = its power B with
+ * n_pow = G - 1) + mkckks_poly_weights + mkckks_poly_tensor_batch + mkckks_relinearize_batch + mkckks_rescale_batch
+ * twice.  d_ct is not modified; d_out overlaps neither d_ct nor the key. */
+int mkckks_poly_eval_batch(mkckks_ctx *c, const uint64_t *d_ct, const uint64_t *d_rlk, const double *h_coef,
+                           uint32_t degree, uint64_t *d_out, uint32_t n_ct, uint32_t nl, double scale_in,
+                           double *scale_out);
+
 /* ---- cc->Encrypt(pk, pt)  (client/src/encryptModelWeights.cpp:83,91,110) --
  * d_pt u64[n_ct][nl][N] encoded plaintexts (EVALUATION); v int8[n_ct][N];
  * e0,e1 int32[n_ct][N]; out u64[n_ct][2][nl][N]. */

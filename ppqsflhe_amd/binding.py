@@ -35,6 +35,15 @@ class _Info(C.Structure):
                 ("alpha", C.c_uint32), ("beta", C.c_uint32), ("slots", C.c_uint32)]
 
 
+POLY_MAX_DEGREE, POLY_MAX_B = 63, 8  # MKCKKS_POLY_MAX_DEGREE, MKCKKS_POLY_MAX_B
+
+
+class _PolyPlan(C.Structure):
+    _fields_ = [("B", C.c_uint32), ("G", C.c_uint32), ("nl_T", C.c_uint32), ("nl_out", C.c_uint32),
+                ("n_relin", C.c_uint32), ("depth", C.c_uint32), ("baby_nl", C.c_uint32 * (POLY_MAX_B - 1)),
+                ("giant_nl", C.c_uint32 * (POLY_MAX_B - 1))]
+
+
 # every symbol include/mkckks.h declares: name -> (restype, argtypes)
 _vp, _u32, _u64p, _sz, _int, _dbl = C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_int, C.c_double
 SYMBOLS = {
@@ -97,6 +106,11 @@ SYMBOLS = {
     "mkckks_tensor_sum_batch": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u32]),
     "mkckks_relinearize_batch": (_int, [_vp, _vp, _vp, _vp, _u32, _u32]),
     "mkckks_mult_relin_batch": (_int, [_vp, _vp, _vp, _vp, _vp, _u32, _u32]),
+    "mkckks_poly_plan": (_int, [_vp, _u32, _u32, _vp]),
+    "mkckks_powers_batch": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _dbl, _vp, _vp]),
+    "mkckks_poly_weights": (_int, [_vp, _vp, _u32, _u32, _dbl, _vp, C.POINTER(_dbl)]),
+    "mkckks_poly_tensor_batch": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32]),
+    "mkckks_poly_eval_batch": (_int, [_vp, _vp, _vp, _vp, _u32, _vp, _u32, _u32, _dbl, C.POINTER(_dbl)]),
     "mkckks_evk_sum": (_int, [_vp, _vp, _vp, _u32, _u32]),
     "mkckks_relin_share": (_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "mkckks_keygen_join": (_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
@@ -619,6 +633,61 @@ class Context:
     def mult_relin(self, a, b, rlk, out, n_ct, nl):
         """out = Relinearize(a x b); out may be a or b; a is b squares."""
         self._check(self._L.mkckks_mult_relin_batch(self._h, _ptr(a), _ptr(b), _ptr(rlk), _ptr(out), n_ct, nl))
+
+    # ---- polynomial evaluation (include/mkckks.h: "polynomial evaluation")
+    def poly_plan(self, degree, nl):
+        """The plan of a degree-`degree` evaluation from nl limbs: dict(B, G, nl_T, nl_out, n_relin, depth, baby_nl [B-1],
+        giant_nl [G-1]).  Host only."""
+        p = _PolyPlan()
+        self._check(self._L.mkckks_poly_plan(self._h, int(degree), int(nl), C.byref(p)))
+        return dict(B=p.B, G=p.G, nl_T=p.nl_T, nl_out=p.nl_out, n_relin=p.n_relin, depth=p.depth,
+                    baby_nl=list(p.baby_nl[:p.B - 1]), giant_nl=list(p.giant_nl[:p.G - 1]))
+
+    def powers(self, z, rlk, out, n_ct, nl, n_pow, scale_in):
+        """out = z^1 .. z^n_pow, power k packed [n_ct][2][nl_k][N] behind power k - 1; returns (nl_k list, S_k list)."""
+        n_pow = int(n_pow)
+        if not 1 <= n_pow <= 64:
+            raise ValueError("n_pow must be in [1, 64]")
+        nls, scales = (C.c_uint32 * n_pow)(), (C.c_double * n_pow)()
+        self._check(self._L.mkckks_powers_batch(self._h, _ptr(z), _ptr(rlk), _ptr(out), n_ct, nl, n_pow, float(scale_in),
+                                                C.addressof(nls), C.addressof(scales)))
+        return list(nls), list(scales)
+
+    def poly_weights(self, coef, nl, scale_in):
+        """(w float64[G][B], S_out) of the polynomial with the power-basis coefficients coef[0 .. d] from nl limbs.  Host only."""
+        c = np.ascontiguousarray(coef, dtype=np.float64)
+        if c.ndim != 1 or not 3 <= c.size <= POLY_MAX_DEGREE + 1:
+            raise ValueError("coef must hold the 3 .. 64 coefficients of a polynomial of degree 2 .. 63")
+        plan = self.poly_plan(c.size - 1, nl)
+        w = np.zeros((plan["G"], plan["B"]), dtype=np.float64)
+        s_out = C.c_double()
+        self._check(self._L.mkckks_poly_weights(self._h, c.ctypes.data, c.size - 1, int(nl), float(scale_in), w.ctypes.data,
+                                                C.byref(s_out)))
+        return w, s_out.value
+
+    def poly_tensor(self, baby, baby_nl, giant, giant_nl, w, out3, n_ct, nl_T):
+        """out3 [n_ct][3][nl_T][N] = the fused outer sum over babies x^1 .. x^{B-1} and giants y^1 .. y^{G-1} (each packed
+        like the output of powers, limb counts baby_nl / giant_nl) with the weights w float64[G][B]."""
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        if w.ndim != 2:
+            raise ValueError("w must be float64[G][B]")
+        G, B = w.shape
+        if len(baby_nl) != B - 1 or len(giant_nl) != G - 1:
+            raise ValueError("baby_nl needs B - 1 entries and giant_nl G - 1")
+        bn = (C.c_uint32 * max(1, B - 1))(*[int(v) for v in baby_nl])
+        gn = (C.c_uint32 * max(1, G - 1))(*[int(v) for v in giant_nl])
+        self._check(self._L.mkckks_poly_tensor_batch(self._h, _ptr(baby), C.addressof(bn), _ptr(giant), C.addressof(gn),
+                                                     w.ctypes.data, _ptr(out3), B, G, n_ct, nl_T))
+
+    def poly_eval(self, ct, rlk, coef, out, n_ct, nl, scale_in):
+        """out [n_ct][2][nl_out][N] = p(ct) slot-wise for the power-basis coefficients coef[0 .. d]; returns S_out."""
+        c = np.ascontiguousarray(coef, dtype=np.float64)
+        if c.ndim != 1 or not 3 <= c.size <= POLY_MAX_DEGREE + 1:
+            raise ValueError("coef must hold the 3 .. 64 coefficients of a polynomial of degree 2 .. 63")
+        s_out = C.c_double()
+        self._check(self._L.mkckks_poly_eval_batch(self._h, _ptr(ct), _ptr(rlk), c.ctypes.data, c.size - 1, _ptr(out), n_ct,
+                                                   int(nl), float(scale_in), C.byref(s_out)))
+        return s_out.value
 
     # ---- collective evaluation keys of a joint key (include/mkckks.h: "collective evaluation keys")
     def evk_sum(self, shares, out, n_parties, n_keys):

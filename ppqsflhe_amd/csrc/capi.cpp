@@ -582,6 +582,96 @@ int mkckks_mult_relin_batch(mkckks_ctx *c, const uint64_t *a, const uint64_t *b,
         c->eng->mult_relin(a, b, rlk, out, n_ct, nl);
     });
 }
+// ---- polynomial evaluation: every refusal is decided here, before a device is asked for (the h_ arrays are host arrays)
+static_assert(MKCKKS_POLY_MAX_DEGREE == mk::POLY_MAX_DEGREE && MKCKKS_POLY_MAX_B == mk::POLY_MAX_B, "polynomial limits");
+static_assert(sizeof(struct mkckks_poly_plan) == sizeof(mk::PolyPlan), "mkckks_poly_plan mirrors mk::PolyPlan");
+int mkckks_poly_plan(const mkckks_ctx *c, uint32_t degree, uint32_t nl, struct mkckks_poly_plan *out) {
+    return guarded([&] {
+        need(c && out, "null argument");
+        const mk::PolyPlan p = c->eng->params().poly_plan(degree, nl);
+        std::memcpy(out, &p, sizeof(p));
+    });
+}
+// words of powers 1 .. n_pow of n_ct ciphertexts, from the ladder's limb counts
+static size_t ladder_bytes(const uint32_t *nlk, uint32_t n_pow, uint32_t n_ct, uint32_t n) {
+    unsigned __int128 limbs = 0;
+    for (uint32_t k = 0; k < n_pow; ++k) limbs += nlk[k];
+    const unsigned __int128 b = limbs * n_ct * 2 * n * sizeof(uint64_t);
+    return b > (unsigned __int128)(SIZE_MAX / 2) ? SIZE_MAX / 2 : (size_t)b;
+}
+int mkckks_powers_batch(mkckks_ctx *c, const uint64_t *d_z, const uint64_t *d_rlk, uint64_t *d_out, uint32_t n_ct, uint32_t nl,
+                        uint32_t n_pow, double scale_in, uint32_t *h_nl_out, double *h_scale_out) {
+    return guarded([&] {
+        need(c && d_z && d_rlk && d_out, "null argument");
+        const mk::ParamSet &ps = c->eng->params();
+        need(nl >= 1 && nl <= ps.L, "nl out of range");
+        need(n_pow >= 1 && n_pow <= 64, "n_pow must be in [1, 64]");
+        need(scale_in > 0, "scale must be positive");
+        std::vector<uint32_t> nlk(n_pow);
+        std::vector<double> sk(n_pow);
+        ps.power_ladder(nl, n_pow, scale_in, nlk.data(), sk.data());
+        need_aligned16({d_z, d_out});
+        const size_t out_bytes = ladder_bytes(nlk.data(), n_pow, n_ct, ps.n);
+        need(!ranges_meet(d_z, poly_bytes((unsigned __int128)n_ct * 2, nl, ps.n), d_out, out_bytes), "output overlaps input");
+        need(!ranges_meet(d_rlk, poly_bytes((unsigned __int128)ps.beta * 2, ps.D, ps.n), d_out, out_bytes), "output overlaps the key");
+        need(n_pow < 2 || ps.num_parts(nl) <= 6, "more than 6 key-switch digits unsupported");
+        if (h_nl_out) std::memcpy(h_nl_out, nlk.data(), n_pow * sizeof(uint32_t));
+        if (h_scale_out) std::memcpy(h_scale_out, sk.data(), n_pow * sizeof(double));
+        if (!n_ct) return;
+        c->eng->powers(d_z, d_rlk, d_out, n_ct, nl, n_pow);
+    });
+}
+int mkckks_poly_weights(const mkckks_ctx *c, const double *h_coef, uint32_t degree, uint32_t nl, double scale_in, double *h_w,
+                        double *scale_out) {
+    return guarded([&] {
+        need(c && h_coef && h_w && scale_out, "null argument");
+        const mk::ParamSet &ps = c->eng->params();
+        const mk::PolyPlan p = ps.poly_plan(degree, nl);
+        std::vector<double> w((size_t)p.B * p.G);
+        *scale_out = ps.poly_weights(h_coef, degree, nl, scale_in, w.data());
+        std::memcpy(h_w, w.data(), w.size() * sizeof(double));
+    });
+}
+int mkckks_poly_tensor_batch(mkckks_ctx *c, const uint64_t *d_baby, const uint32_t *h_baby_nl, const uint64_t *d_giant,
+                             const uint32_t *h_giant_nl, const double *h_w, uint64_t *d_out3, uint32_t B, uint32_t G,
+                             uint32_t n_ct, uint32_t nl_T) {
+    return guarded([&] {
+        need(c && d_baby && h_baby_nl && d_giant && h_giant_nl && h_w && d_out3, "null argument");
+        const mk::ParamSet &ps = c->eng->params();
+        need(B == 2 || B == 4 || B == 8, "B must be 2, 4 or 8");
+        need(G >= 2 && G <= B, "G must be in [2, B]");
+        need(nl_T >= 1 && nl_T <= ps.L, "nl_T out of range");
+        for (uint32_t i = 0; i + 1 < B; ++i) need(h_baby_nl[i] >= nl_T && h_baby_nl[i] <= ps.L, "a baby's limb count is outside [nl_T, L]");
+        for (uint32_t j = 0; j + 1 < G; ++j) need(h_giant_nl[j] >= nl_T && h_giant_nl[j] <= ps.L, "a giant's limb count is outside [nl_T, L]");
+        need_aligned16({d_baby, d_giant, d_out3});
+        const size_t out_bytes = poly_bytes((unsigned __int128)n_ct * 3, nl_T, ps.n);
+        need(!ranges_meet(d_baby, ladder_bytes(h_baby_nl, B - 1, n_ct, ps.n), d_out3, out_bytes) &&
+                 !ranges_meet(d_giant, ladder_bytes(h_giant_nl, G - 1, n_ct, ps.n), d_out3, out_bytes),
+             "output overlaps input");
+        (void)ps.poly_constants(h_w, B * G, nl_T);  // the weights' refusals, before a device is asked for
+        if (!n_ct) return;
+        c->eng->poly_tensor(d_baby, h_baby_nl, d_giant, h_giant_nl, h_w, d_out3, B, G, n_ct, nl_T);
+    });
+}
+int mkckks_poly_eval_batch(mkckks_ctx *c, const uint64_t *d_ct, const uint64_t *d_rlk, const double *h_coef, uint32_t degree,
+                           uint64_t *d_out, uint32_t n_ct, uint32_t nl, double scale_in, double *scale_out) {
+    return guarded([&] {
+        need(c && d_ct && d_rlk && h_coef && d_out, "null argument");
+        const mk::ParamSet &ps = c->eng->params();
+        const mk::PolyPlan p = ps.poly_plan(degree, nl);
+        std::vector<double> w((size_t)p.B * p.G);
+        const double s_out = ps.poly_weights(h_coef, degree, nl, scale_in, w.data());
+        (void)ps.poly_constants(w.data(), p.B * p.G, p.nl_T);
+        need_aligned16({d_ct, d_out});
+        const size_t out_bytes = poly_bytes((unsigned __int128)n_ct * 2, p.nl_out, ps.n);
+        need(!ranges_meet(d_ct, poly_bytes((unsigned __int128)n_ct * 2, nl, ps.n), d_out, out_bytes), "output overlaps input");
+        need(!ranges_meet(d_rlk, poly_bytes((unsigned __int128)ps.beta * 2, ps.D, ps.n), d_out, out_bytes), "output overlaps the key");
+        need(ps.num_parts(nl) <= 6, "more than 6 key-switch digits unsupported");
+        if (scale_out) *scale_out = s_out;
+        if (!n_ct) return;
+        c->eng->poly_eval(d_ct, d_rlk, h_coef, degree, d_out, n_ct, nl, scale_in);
+    });
+}
 // ---- collective evaluation keys of a joint key: every refusal is decided here, before a device is asked for
 int mkckks_evk_sum(mkckks_ctx *c, const uint64_t *in, uint64_t *out, uint32_t n_parties, uint32_t n_keys) {
     return guarded([&] {

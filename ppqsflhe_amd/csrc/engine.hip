@@ -23,6 +23,7 @@
 #include "galois_kernels.hpp"
 #include "tensor_kernels.hpp"
 #include "lintrans_kernels.hpp"
+#include "poly_kernels.hpp"
 #include "relshare_kernels.hpp"
 #include "sampler_kernels.hpp"
 #include "arith_probe_kernels.hpp"
@@ -628,6 +629,10 @@ Knobs Knobs::from_env() {
     if (const char *e = std::getenv("MKCKKS_ICOL_CONV")) {
         if (e[0] >= '0' && e[0] <= '3' && !e[1]) k.icol_conv = e[0] - '0';
     }
+    if (const char *e = std::getenv("MKCKKS_POLY_FUSED")) {
+        if (!std::strcmp(e, "0")) k.poly_fused = 0;
+        else if (!std::strcmp(e, "1")) k.poly_fused = 1;
+    }
     if (const char *e = std::getenv("MKCKKS_LT_ORDER")) {
         if (e[0] >= '0' && e[0] <= '2' && !e[1]) k.lt_order = e[0] - '0';
     }
@@ -750,6 +755,7 @@ Engine::~Engine() {
     for (void *p : owned_) (void)hipFree(p);
     for (auto &kv : wt_cache_) (void)hipFree(kv.second);
     if (wtmp_) (void)hipFree(wtmp_);
+    if (poly_buf_) (void)hipFree(poly_buf_);
     if (up_stream_) {
         (void)hipStreamDestroy(up_stream_);
         (void)hipStreamDestroy(down_stream_);
@@ -910,6 +916,18 @@ u64 *Engine::chunk_buffer(size_t words) {
         wtmp_words_ = words;
     }
     return wtmp_;
+}
+
+u64 *Engine::poly_buffer(size_t words) {
+    if (words > poly_buf_words_) {
+        MK_HIP(hipStreamSynchronize(stream_));
+        if (poly_buf_) MK_HIP(hipFree(poly_buf_));
+        poly_buf_ = nullptr;
+        poly_buf_words_ = 0;
+        MK_HIP(hipMalloc(&poly_buf_, words * sizeof(u64)));
+        poly_buf_words_ = words;
+    }
+    return poly_buf_;
 }
 
 const u64 *Engine::limb_vector(const std::string &key, const std::vector<u64> &vals) {
@@ -2617,6 +2635,234 @@ void Engine::mult_relin(const u64 *a, const u64 *b, const u64 *rlk, u64 *out, ui
         u64 *dst = out + off;
         launch_tensor(a + off, b + off, 0, 1, dst, 2 * poly, d2, poly, cnt, nl);
         relin_chunk(d2, poly, rlk, dst, cnt, nl);
+    }
+}
+
+// ---- polynomial evaluation ("polynomial evaluation"); overlaps and alignment are refused in capi.cpp -----------
+
+// the composition's constant column and closing row (MKCKKS_POLY_FUSED=0 only)
+// ct[item][0][l] += f[l]: the constant M_{j,0} enters component 0 of Q_j, i.e. Q_j + M_{j,0} (1, 0)
+__global__ void k_poly_add_const(u64 *ct, EwGeom g, const LimbConst *limb, const u64 *f) {
+    EW_PROLOGUE(g.nl)
+    const u64 q = limb[slot].q, c = f[slot];
+    const size_t off = ((size_t)item * 2 * g.nl + slot) * g.n + idx;
+    ulong2 v = ld2(ct + off);
+    v.x = add_mod(v.x, c, q);
+    v.y = add_mod(v.y, c, q);
+    st2(ct + off, v);
+}
+// out3[item][c][l] += q0[item][c][l] for c < 2: (Q'_0, 0) onto the tensor sum; grid.y = 2 * nl
+__global__ void k_poly_add_row(u64 *out3, const u64 *q0, EwGeom g, const LimbConst *limb) {
+    EW_PROLOGUE(2 * g.nl)
+    const u64 q = limb[slot % g.nl].q;
+    const size_t in = ((size_t)item * 2 * g.nl + slot) * g.n + idx, out = ((size_t)item * 3 * g.nl + slot) * g.n + idx;
+    ulong2 v = ld2(out3 + out);
+    const ulong2 a = ld2(q0 + in);
+    v.x = add_mod(v.x, a.x, q);
+    v.y = add_mod(v.y, a.y, q);
+    st2(out3 + out, v);
+}
+
+// Device table of a call's constants, cached per (weights, B, G, nl_T) like weight_table and in the same cache:
+// M u64[G][B][nl_T] (k_poly_tensor), then the same constants as weight-table entries [G][B][nl_T][WT_WORDS] (k_wsum_ct of
+// the composition reads M and its Shoup companion)
+const u64 *Engine::poly_table(const double *w, uint32_t B, uint32_t G, uint32_t nl_T) {
+    std::string key((const char *)w, (size_t)B * G * sizeof(double));
+    key += "@poly" + std::to_string(B) + "," + std::to_string(G) + "," + std::to_string(nl_T);
+    auto it = wt_cache_.find(key);
+    if (it != wt_cache_.end()) return it->second;
+    const std::vector<u64> m = ps_.poly_constants(w, B * G, nl_T);  // throws on a weight that does not fit
+    std::vector<u64> t(m.size() * (1 + WT_WORDS), 0);
+    std::copy(m.begin(), m.end(), t.begin());
+    for (size_t e = 0; e < m.size(); ++e) {
+        u64 *wt = &t[m.size() + e * WT_WORDS];
+        wt[0] = m[e];
+        wt[1] = h_shoup(m[e], ps_.moduli[e % nl_T]);
+    }
+    if (wt_cache_.size() >= 64) {
+        MK_HIP(hipStreamSynchronize(stream_));
+        for (auto &kv : wt_cache_) MK_HIP(hipFree(kv.second));
+        wt_cache_.clear();
+    }
+    u64 *d = nullptr;
+    MK_HIP(hipMalloc(&d, t.size() * sizeof(u64)));
+    wt_cache_[key] = d;
+    MK_HIP(hipMemcpy(d, t.data(), t.size() * sizeof(u64), hipMemcpyHostToDevice));
+    return d;
+}
+
+// words of scratch poly_tensor_core needs: none for the kernel; the composition packs the operands' prefixes and keeps
+// every Q_j
+size_t Engine::poly_tensor_scratch(uint32_t B, uint32_t G, uint32_t cnt, uint32_t nl_T) const {
+    if (poly_tensor_fused(B, G, knobs_.poly_fused)) return 0;
+    return (size_t)(B - 1 + G - 1 + G) * cnt * 2 * nl_T * ps_.n;
+}
+
+void Engine::poly_tensor_core(const PolyOpnd *baby, const PolyOpnd *giant, const u64 *table, u64 *out3, uint32_t B, uint32_t G,
+                              uint32_t cnt, uint32_t nl_T, u64 *scratch) {
+    const uint32_t n = ps_.n;
+    if (!cnt) return;
+    if (poly_tensor_fused(B, G, knobs_.poly_fused)) {
+        PolyArgs t{};
+        for (uint32_t i = 0; i + 1 < B; ++i) t.baby[i] = baby[i];
+        for (uint32_t j = 0; j + 1 < G; ++j) t.giant[j] = giant[j];
+        t.m = table;
+        t.out3 = out3;
+        t.G = G;
+        t.n = n;
+        t.nl_T = nl_T;
+        const dim3 grid((n / 2 + POLY_THREADS - 1) / POLY_THREADS, nl_T, cnt);
+        if (!dispatch<2, 4, 8>(B, [&](auto b) {
+                k_poly_tensor<decltype(b)::value><<<grid, POLY_THREADS, 0, stream_>>>(t, d_limb_);
+            }))
+            throw std::invalid_argument("B must be 2, 4 or 8");
+        MK_HIP(hipGetLastError());
+        return;
+    }
+    // the composition: packed prefix copies, eval_wsum's kernel per giant index, the constant column, tensor_sum's kernel
+    // over the giants, the closing row
+    const size_t poly = (size_t)nl_T * n, term = (size_t)cnt * 2 * poly;
+    u64 *bp = scratch, *gp = bp + (B - 1) * term, *qs = gp + (G - 1) * term;  // qs[0] = Q'_0, qs[j] = Q'_j
+    for (uint32_t i = 0; i + 1 < B; ++i)
+        k_copy_slots<<<ew_grid(n, nl_T, 2 * cnt), EW_THREADS, 0, stream_>>>(baby[i].p, (size_t)baby[i].nl * n, 0, bp + i * term,
+                                                                             poly, 0, n);
+    for (uint32_t j = 0; j + 1 < G; ++j)
+        k_copy_slots<<<ew_grid(n, nl_T, 2 * cnt), EW_THREADS, 0, stream_>>>(giant[j].p, (size_t)giant[j].nl * n, 0,
+                                                                             gp + j * term, poly, 0, n);
+    MK_HIP(hipGetLastError());
+    const size_t m_words = (size_t)G * B * nl_T;
+    EwGeom g{n, nl_T, ps_.L};
+    for (uint32_t j = 0; j < G; ++j) {
+        const u64 *wt = table + m_words + ((size_t)j * B + 1) * nl_T * WT_WORDS;  // terms i = 1 .. B - 1 of row j
+        k_wsum_ct<<<ew_grid(n, 2 * nl_T, cnt), EW_THREADS, 0, stream_>>>(bp, qs + j * term, g, d_limb_, 2 * nl_T, B - 1, term, wt,
+                                                                          nl_T, 0);
+        k_poly_add_const<<<ew_grid(n, nl_T, cnt), EW_THREADS, 0, stream_>>>(qs + j * term, g, d_limb_,
+                                                                             table + (size_t)j * B * nl_T);
+    }
+    MK_HIP(hipGetLastError());
+    launch_tensor(qs + term, gp, term, G - 1, out3, 3 * poly, out3 + 2 * poly, 3 * poly, cnt, nl_T);
+    k_poly_add_row<<<ew_grid(n, 2 * nl_T, cnt), EW_THREADS, 0, stream_>>>(out3, qs, g, d_limb_);
+    MK_HIP(hipGetLastError());
+}
+
+void Engine::poly_tensor(const u64 *baby, const uint32_t *baby_nl, const u64 *giant, const uint32_t *giant_nl, const double *w,
+                         u64 *out3, uint32_t B, uint32_t G, uint32_t n_ct, uint32_t nl_T) {
+    need_device();
+    check_nl(nl_T);
+    if (!n_ct) return;
+    const uint32_t n = ps_.n;
+    const u64 *table = poly_table(w, B, G, nl_T);
+    constexpr uint32_t MAX_ITEMS = 32768;  // grid.z
+    const uint32_t step = std::min(n_ct, MAX_ITEMS);
+    const size_t scratch_words = poly_tensor_scratch(B, G, step, nl_T);
+    u64 *scratch = scratch_words ? poly_buffer(scratch_words) : nullptr;
+    for (uint32_t done = 0; done < n_ct; done += step) {
+        const uint32_t cnt = std::min(step, n_ct - done);
+        PolyOpnd bo[POLY_MAX_B - 1] = {}, go[POLY_MAX_B - 1] = {};
+        size_t off = 0;  // power k of a packed array starts behind the n_ct items of power k - 1
+        for (uint32_t i = 0; i + 1 < B; ++i) {
+            bo[i] = PolyOpnd{baby + off + (size_t)done * 2 * baby_nl[i] * n, baby_nl[i], 0};
+            off += (size_t)n_ct * 2 * baby_nl[i] * n;
+        }
+        off = 0;
+        for (uint32_t j = 0; j + 1 < G; ++j) {
+            go[j] = PolyOpnd{giant + off + (size_t)done * 2 * giant_nl[j] * n, giant_nl[j], 0};
+            off += (size_t)n_ct * 2 * giant_nl[j] * n;
+        }
+        poly_tensor_core(bo, go, table, out3 + (size_t)done * 3 * nl_T * n, B, G, cnt, nl_T, scratch);
+    }
+}
+
+void Engine::power_ladder_core(u64 *const *pw, const uint32_t *nlk, const u64 *rlk, uint32_t cnt, uint32_t n_pow, u64 *scratch) {
+    const uint32_t n = ps_.n;
+    u64 *pre = scratch, *prod = scratch + (size_t)cnt * 2 * nlk[1] * n;
+    for (uint32_t k = 2; k <= n_pow; ++k) {
+        const uint32_t i = (k + 1) / 2, j = k - i, nli = nlk[i];
+        const u64 *b = pw[j];
+        if (nlk[j] != nli) {  // the level cut: the first nl_i limbs of both components, packed
+            k_copy_slots<<<ew_grid(n, nli, 2 * cnt), EW_THREADS, 0, stream_>>>(pw[j], (size_t)nlk[j] * n, 0, pre, (size_t)nli * n, 0,
+                                                                             n);
+            MK_HIP(hipGetLastError());
+            b = pre;
+        }
+        mult_relin(pw[i], b, rlk, prod, cnt, nli);
+        rescale(prod, pw[k], cnt, nli, nullptr);
+    }
+}
+
+void Engine::powers(const u64 *z, const u64 *rlk, u64 *out, uint32_t n_ct, uint32_t nl, uint32_t n_pow) {
+    need_device();
+    check_nl(nl);
+    std::vector<uint32_t> nlk(n_pow + 1);
+    ps_.power_ladder(nl, n_pow, 1.0, nlk.data() + 1, nullptr);
+    if (!n_ct) return;
+    const uint32_t n = ps_.n;
+    MK_HIP(hipMemcpyAsync(out, z, (size_t)n_ct * 2 * nl * n * sizeof(u64), hipMemcpyDeviceToDevice, stream_));
+    if (n_pow < 2) return;
+    const uint32_t chunk = std::min(knobs_.chunk, n_ct);
+    u64 *scratch = poly_buffer((size_t)2 * chunk * 2 * nl * n);
+    std::vector<size_t> off(n_pow + 1, 0);
+    for (uint32_t k = 2; k <= n_pow; ++k) off[k] = off[k - 1] + (size_t)n_ct * 2 * nlk[k - 1] * n;
+    std::vector<u64 *> pw(n_pow + 1, nullptr);
+    for (uint32_t done = 0; done < n_ct; done += chunk) {
+        const uint32_t cnt = std::min(chunk, n_ct - done);
+        for (uint32_t k = 1; k <= n_pow; ++k) pw[k] = out + off[k] + (size_t)done * 2 * nlk[k] * n;
+        power_ladder_core(pw.data(), nlk.data(), rlk, cnt, n_pow, scratch);
+    }
+}
+
+// per chunk, everything but the input and the output in the poly buffer: x^2 .. x^B (= y), y^2 .. y^(G-1), the ladder's
+// scratch, the outer sum, its relinearisation and the first rescale.  x^1 is the input where it is
+void Engine::poly_eval(const u64 *ct, const u64 *rlk, const double *coef, uint32_t degree, u64 *out, uint32_t n_ct, uint32_t nl,
+                       double scale_in) {
+    need_device();
+    const PolyPlan p = ps_.poly_plan(degree, nl);
+    std::vector<double> w((size_t)p.B * p.G);
+    ps_.poly_weights(coef, degree, nl, scale_in, w.data());
+    if (!n_ct) return;
+    const uint32_t n = ps_.n, B = p.B, G = p.G, nl_T = p.nl_T;
+    uint32_t nlx[POLY_MAX_B + 1] = {}, nly[POLY_MAX_B] = {};
+    ps_.power_ladder(nl, B, 1.0, nlx + 1, nullptr);
+    ps_.power_ladder(nlx[B], G - 1, 1.0, nly + 1, nullptr);
+    const u64 *table = poly_table(w.data(), B, G, nl_T);
+    const uint32_t chunk = std::min(knobs_.chunk, n_ct);
+    const size_t ctw = (size_t)chunk * 2 * n;  // words of a chunk's ciphertexts per limb
+    size_t words = 0, off_x[POLY_MAX_B + 1] = {}, off_y[POLY_MAX_B] = {};
+    for (uint32_t k = 2; k <= B; ++k) {
+        off_x[k] = words;
+        words += ctw * nlx[k];
+    }
+    for (uint32_t k = 2; k < G; ++k) {
+        off_y[k] = words;
+        words += ctw * nly[k];
+    }
+    const size_t off_ladder = words;
+    words += 2 * ctw * nl;
+    const size_t off_out3 = words;
+    words += (size_t)chunk * 3 * nl_T * n;
+    const size_t off_relin = words;
+    words += ctw * nl_T;
+    const size_t off_resc = words;
+    words += ctw * (nl_T - 1);
+    const size_t off_comp = words;
+    words += poly_tensor_scratch(B, G, chunk, nl_T);
+    u64 *buf = poly_buffer(words);
+    for (uint32_t done = 0; done < n_ct; done += chunk) {
+        const uint32_t cnt = std::min(chunk, n_ct - done);
+        u64 *pwx[POLY_MAX_B + 1] = {}, *pwy[POLY_MAX_B] = {};
+        pwx[1] = const_cast<u64 *>(ct) + (size_t)done * 2 * nl * n;  // read only: the ladder writes pw[k] for k >= 2
+        for (uint32_t k = 2; k <= B; ++k) pwx[k] = buf + off_x[k];
+        power_ladder_core(pwx, nlx, rlk, cnt, B, buf + off_ladder);
+        pwy[1] = pwx[B];
+        for (uint32_t k = 2; k < G; ++k) pwy[k] = buf + off_y[k];
+        power_ladder_core(pwy, nly, rlk, cnt, G - 1, buf + off_ladder);
+        PolyOpnd bo[POLY_MAX_B - 1] = {}, go[POLY_MAX_B - 1] = {};
+        for (uint32_t i = 1; i < B; ++i) bo[i - 1] = PolyOpnd{pwx[i], nlx[i], 0};
+        for (uint32_t j = 1; j < G; ++j) go[j - 1] = PolyOpnd{pwy[j], nly[j], 0};
+        poly_tensor_core(bo, go, table, buf + off_out3, B, G, cnt, nl_T, buf + off_comp);
+        relinearize(buf + off_out3, rlk, buf + off_relin, cnt, nl_T);
+        rescale(buf + off_relin, buf + off_resc, cnt, nl_T, nullptr);
+        rescale(buf + off_resc, out + (size_t)done * 2 * p.nl_out * n, cnt, nl_T - 1, nullptr);
     }
 }
 

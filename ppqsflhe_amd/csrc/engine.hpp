@@ -80,6 +80,9 @@ struct Knobs {
                                  // chunk share; 0: the workgroups of one (limb, tile) are neighbours on one XCD, 1: one
                                  // workgroup walks the chunk's ciphertexts, 2: ciphertext-major grid, no reuse intended
                                  // (profiles/linear_transform_ab.txt)
+    int poly_fused = 2;          // MKCKKS_POLY_FUSED=0/1: poly_tensor as the composition (eval_wsum per giant index on packed prefix
+                                 // copies + tensor_sum + the constant column and term) or as k_poly_tensor; default:
+                                 // poly_tensor_fused (profiles/poly_ab.txt)
     static Knobs from_env();
 };
 
@@ -108,6 +111,16 @@ inline uint32_t icol_conv_targets(uint32_t n_fp, uint64_t grid, int mode) {
         if ((n_fp - nt) % 2 == 0) return nt;
     return 0;
 }
+
+// The form poly_tensor takes for a (B, G) plan: true = k_poly_tensor, false = the composition.  mode 0 / 1 force a form,
+// anything else chooses: the kernel for every plan -- it is 4.6 x to 6.3 x faster on each measured (B, G), which are all
+// three instances with G = 2, 3, 4 and 8, the largest plan (8, 8) included (profiles/poly_ab.txt); a plan that measures
+// otherwise gets its exception here.
+inline bool poly_tensor_fused(uint32_t /*B*/, uint32_t /*G*/, int mode) {
+    return mode != 0;
+}
+
+struct PolyOpnd;  // poly_kernels.hpp
 
 class Engine {
 public:
@@ -244,6 +257,18 @@ public:
     void tensor_sum(const u64 *a, const u64 *b, u64 *out3, uint32_t n_terms, uint32_t n_ct, uint32_t nl);
     void relinearize(const u64 *in3, const u64 *rlk, u64 *out, uint32_t n_ct, uint32_t nl);
     void mult_relin(const u64 *a, const u64 *b, const u64 *rlk, u64 *out, uint32_t n_ct, uint32_t nl);
+    // polynomial evaluation ("polynomial evaluation"; kernel: poly_kernels.hpp; plan, scales and constants:
+    // ParamSet::poly_plan / power_ladder / poly_weights / poly_constants)
+    //   powers:      out = z^1 .. z^n_pow, power k packed u64[n_ct][2][nl_k][N] behind power k - 1; z^k =
+    //                rescale(mult_relin(z^i, prefix(z^j, nl_i))), i = ceil(k / 2), j = k - i
+    //   poly_tensor: the fused outer sum over caller-supplied babies and giants (packed like the output of powers) and
+    //                weights w HOST double[G][B]; out3 u64[n_ct][3][nl_T][N]
+    //   poly_eval:   powers of x up to y = x^B, powers of y, poly_tensor, relinearize, rescale twice; chunked
+    void powers(const u64 *z, const u64 *rlk, u64 *out, uint32_t n_ct, uint32_t nl, uint32_t n_pow);
+    void poly_tensor(const u64 *baby, const uint32_t *baby_nl, const u64 *giant, const uint32_t *giant_nl, const double *w,
+                     u64 *out3, uint32_t B, uint32_t G, uint32_t n_ct, uint32_t nl_T);
+    void poly_eval(const u64 *ct, const u64 *rlk, const double *coef, uint32_t degree, u64 *out, uint32_t n_ct, uint32_t nl,
+                   double scale_in);
     // collective evaluation keys of a joint key ("collective evaluation keys"; kernels: relshare_kernels.hpp)
     //   evk_sum:     out[k] = sum_p in[p][k] on all D limbs; in u64[n_parties][n_keys][beta][2][D][N]; out may be in[0]
     //   relin_share: share[j][c] = key1[j][c] * sk + NTT(e_c[j]) on all D limbs; key1, share u64[beta][2][D][N], sk u64[D][N],
@@ -296,6 +321,13 @@ private:
     void launch_tensor(const u64 *a, const u64 *b, size_t term_stride, uint32_t n_terms, u64 *o01, size_t o01_stride, u64 *o2,
                        size_t o2_stride, uint32_t cnt, uint32_t nl);
     void relin_chunk(const u64 *d2, size_t d2_stride, const u64 *rlk, u64 *out, uint32_t cnt, uint32_t nl);
+    u64 *poly_buffer(size_t words);  // a third grow-only buffer: the powers and intermediates of a chunk (poly_eval)
+    // pw[k] = z^k for k = 2 .. n_pow from pw[1] (1-based; nlk[k] its limbs); scratch: 2 * cnt * 2 * nlk[1] * N words
+    void power_ladder_core(u64 *const *pw, const uint32_t *nlk, const u64 *rlk, uint32_t cnt, uint32_t n_pow, u64 *scratch);
+    const u64 *poly_table(const double *w, uint32_t B, uint32_t G, uint32_t nl_T);
+    size_t poly_tensor_scratch(uint32_t B, uint32_t G, uint32_t cnt, uint32_t nl_T) const;
+    void poly_tensor_core(const PolyOpnd *baby, const PolyOpnd *giant, const u64 *table, u64 *out3, uint32_t B, uint32_t G,
+                          uint32_t cnt, uint32_t nl_T, u64 *scratch);
     // p_scaled: the P targets' constants carry ModDown's scale (ParamSet::modup_table_pscaled; the merged n-client flow)
     const DevConv &modup_conv(uint32_t nl, uint32_t part, bool p_scaled = false);
     const DevConv &moddown_conv(uint32_t nl);
@@ -366,6 +398,8 @@ private:
     std::map<std::string, u64 *> wt_cache_;  // weight_table
     u64 *wtmp_ = nullptr;                    // chunk_buffer: a chunk with c0 scaled (reencrypt_wsum), permuted (slot_sum), or d2 (mult_relin)
     size_t wtmp_words_ = 0;
+    u64 *poly_buf_ = nullptr;  // poly_buffer
+    size_t poly_buf_words_ = 0;
     int8_t *d_gal_s_ = nullptr;  // galois_keygen: sigma_g(s)
     uint32_t *d_lt_g_ = nullptr;  // linear_transform: the call's Galois elements (grow-only)
     size_t lt_g_cap_ = 0;

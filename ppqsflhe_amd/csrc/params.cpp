@@ -403,4 +403,104 @@ void ParamSet::lagrange_at_zero(const uint32_t *parties, uint32_t n_active, u64 
         }
 }
 
+// ---- polynomial evaluation: plan, ladder scales, weights and constants (include/mkckks.h: "polynomial evaluation") ------
+
+static uint32_t ceil_log2(uint32_t v) {
+    uint32_t r = 0;
+    while ((1u << r) < v) ++r;
+    return r;
+}
+
+void ParamSet::power_ladder(uint32_t nl, uint32_t n_pow, double scale_in, uint32_t *nl_out, double *scale_out) const {
+    if (nl < 1 || nl > L) throw std::invalid_argument("nl out of range");
+    if (n_pow < 1 || n_pow > 64) throw std::invalid_argument("n_pow must be in [1, 64]");
+    if (ceil_log2(n_pow) >= nl) throw std::invalid_argument("the power ladder needs nl - ceil(log2 n_pow) >= 1 limbs");
+    std::vector<uint32_t> nlk(n_pow + 1);
+    std::vector<double> sk(n_pow + 1);
+    nlk[1] = nl;
+    sk[1] = scale_in;
+    for (uint32_t k = 2; k <= n_pow; ++k) {
+        const uint32_t i = (k + 1) / 2, j = k - i;
+        nlk[k] = nlk[i] - 1;
+        const double prod = sk[i] * sk[j];
+        sk[k] = prod / (double)moduli[nlk[i] - 1];
+    }
+    for (uint32_t k = 1; k <= n_pow; ++k) {
+        if (nl_out) nl_out[k - 1] = nlk[k];
+        if (scale_out) scale_out[k - 1] = sk[k];
+    }
+}
+
+PolyPlan ParamSet::poly_plan(uint32_t degree, uint32_t nl) const {
+    if (degree < 2 || degree > POLY_MAX_DEGREE) throw std::invalid_argument("degree must be in [2, 63]");
+    if (nl < 1 || nl > L) throw std::invalid_argument("nl out of range");
+    PolyPlan p{};
+    p.B = 2;
+    while (p.B * p.B < degree + 1) p.B *= 2;
+    p.G = (degree + p.B) / p.B;  // ceil((degree + 1) / B)
+    const uint32_t log_b = ceil_log2(p.B), log_g = ceil_log2(p.G - 1);
+    p.depth = log_b + log_g + 2;
+    if (nl < p.depth + 1)
+        throw std::invalid_argument("degree " + std::to_string(degree) + " needs " + std::to_string(p.depth + 1) +
+                                    " limbs, the input has " + std::to_string(nl));
+    p.nl_T = nl - log_b - log_g;
+    p.nl_out = p.nl_T - 2;
+    p.n_relin = (p.B - 1) + (p.G - 2) + 1;
+    for (uint32_t i = 1; i < p.B; ++i) p.baby_nl[i - 1] = nl - ceil_log2(i);
+    for (uint32_t j = 1; j < p.G; ++j) p.giant_nl[j - 1] = nl - log_b - ceil_log2(j);
+    return p;
+}
+
+double ParamSet::poly_weights(const double *coef, uint32_t degree, uint32_t nl, double scale_in, double *w) const {
+    const PolyPlan p = poly_plan(degree, nl);
+    if (!(scale_in > 0) || !std::isfinite(scale_in)) throw std::invalid_argument("scale must be positive and finite");
+    for (uint32_t k = 0; k <= degree; ++k)
+        if (!std::isfinite(coef[k])) throw std::invalid_argument("coefficient " + std::to_string(k) + " is not finite");
+    double sx[POLY_MAX_B + 1], sy[POLY_MAX_B];  // sx[i]: scale of x^i, sx[B] that of y; sy[j]: scale of y^j
+    uint32_t nlx[POLY_MAX_B];
+    power_ladder(nl, p.B, scale_in, nlx, sx + 1);
+    sx[0] = sy[0] = 1.0;
+    power_ladder(nlx[p.B - 1], p.G - 1, sx[p.B], nullptr, sy + 1);
+    const double s_out = sf.at(L - p.nl_out);
+    const double sigma = s_out * (double)moduli[p.nl_T - 1] * (double)moduli[p.nl_T - 2];
+    for (uint32_t j = 0; j < p.G; ++j)
+        for (uint32_t i = 0; i < p.B; ++i) {
+            const uint32_t k = j * p.B + i;
+            const double c = k <= degree ? coef[k] : 0.0;
+            const double den = sx[i] * sy[j];
+            w[k] = c == 0.0 ? 0.0 : c * (sigma / den);
+        }
+    return s_out;
+}
+
+std::vector<u64> ParamSet::poly_constants(const double *w, uint32_t count, uint32_t nl_T) const {
+    if (nl_T < 1 || nl_T > L) throw std::invalid_argument("nl_T out of range");
+    long double half = 0.5L;
+    for (uint32_t t = 0; t < nl_T; ++t) half *= (long double)moduli[t];
+    std::vector<u64> out((size_t)count * nl_T);
+    for (uint32_t k = 0; k < count; ++k) {
+        if (!std::isfinite(w[k])) throw std::invalid_argument("weight " + std::to_string(k) + " is not finite");
+        const double a = std::fabs(w[k]);
+        if ((long double)a >= half)
+            throw std::invalid_argument("weight " + std::to_string(k) + " does not fit half the modulus of its level");
+        // M = rint(|w|) as m * 2^sh: below 2^63 the rounded double converts exactly; above, a double is m * 2^sh with m < 2^53
+        u64 m;
+        int sh = 0;
+        if (a < 9223372036854775808.0) {
+            m = (u64)std::nearbyint(a);
+        } else {
+            const double f = std::frexp(a, &sh);  // a = f * 2^sh, 0.5 <= f < 1
+            m = (u64)std::ldexp(f, 53);
+            sh -= 53;
+        }
+        for (uint32_t t = 0; t < nl_T; ++t) {
+            const u64 q = moduli[t];
+            u64 r = m % q;
+            if (sh) r = h_mulmod(r, h_powmod(2, (u64)sh, q), q);
+            out[(size_t)k * nl_T + t] = (w[k] < 0 && r) ? q - r : r;
+        }
+    }
+    return out;
+}
+
 }  // namespace mk

@@ -46,6 +46,14 @@ struct BaseConvTable {
 // meets an fp64-class target as lo [S/s_0]_t + hi [S/s_0 2^30]_t, two exact FMA products of 30-bit factors.
 std::vector<u64> hat_as_doubles(const BaseConvTable &t, const std::vector<u64> &moduli);
 
+// Plan of a fused Paterson-Stockmeyer evaluation (include/mkckks.h: "polynomial evaluation"): p(x) = sum_j sum_i
+// c_{jB+i} x^i y^j with y = x^B.  baby_nl[i - 1] / giant_nl[j - 1]: limbs of x^i (0 < i < B) and y^j (0 < j < G).
+constexpr uint32_t POLY_MAX_DEGREE = 63, POLY_MAX_B = 8;
+struct PolyPlan {
+    uint32_t B, G, nl_T, nl_out, n_relin, depth;
+    uint32_t baby_nl[POLY_MAX_B - 1], giant_nl[POLY_MAX_B - 1];
+};
+
 struct ParamSet {
     uint32_t log_n = 0, n = 0;
     uint32_t L = 0, K = 0, D = 0;  // #Q limbs, #P limbs, L+K
@@ -97,6 +105,19 @@ struct ParamSet {
     // [1, LAGRANGE_MAX_PARTIES], a duplicate and an empty set throw std::invalid_argument
     static constexpr uint32_t LAGRANGE_MAX_PARTIES = 64;
     void lagrange_at_zero(const uint32_t *parties, uint32_t n_active, u64 *out) const;
+    // polynomial evaluation, host side.  Every scale below is the same few double operations in a fixed order (a product
+    // then a quotient, never a multiply-add), so a restatement in another language gives the same bits.
+    //   power_ladder: limbs and scales of z^1 .. z^n_pow from z at nl limbs and scale_in: with i = ceil(k / 2), j = k - i,
+    //                 nl_k = nl_i - 1 and S_k = S_i * S_j / q_{nl_i - 1}.  Throws unless 1 <= n_pow <= 64 and every nl_k >= 1
+    //   poly_plan:    throws for a degree outside [2, 63], nl outside [1, L] or nl_out < 1
+    //   poly_weights: w[j * B + i] = c_{jB+i} * (Sigma / (S_{x^i} * S_{y^j})) with Sigma = S_out * q_{nl_T-1} * q_{nl_T-2};
+    //                 returns S_out = sf(L - nl_out).  Throws on a non-finite coefficient
+    //   poly_constants: out[k * nl_T + t] = rint(w[k]) mod q_t (a negative one as q - (|M| mod q)); throws on a non-finite
+    //                 w or |w| >= q_0 ... q_{nl_T-1} / 2
+    void power_ladder(uint32_t nl, uint32_t n_pow, double scale_in, uint32_t *nl_out, double *scale_out) const;
+    PolyPlan poly_plan(uint32_t degree, uint32_t nl) const;
+    double poly_weights(const double *coef, uint32_t degree, uint32_t nl, double scale_in, double *w) const;
+    std::vector<u64> poly_constants(const double *w, uint32_t count, uint32_t nl_T) const;
 };
 
 }  // namespace mk
