@@ -412,6 +412,42 @@ int mkckks_encode_ext_batch(mkckks_ctx *c, const double *d_vals, uint64_t *d_pt,
  * n_ct == 0 is a no-op; a host-only context gives MKCKKS_E_NODEVICE. */
 int mkckks_linear_transform_batch(mkckks_ctx *c, const uint64_t *d_ct, const uint64_t *d_evks, const uint64_t *d_pts,
                                   const uint32_t *h_g, uint64_t *d_out, uint32_t n_rot, uint32_t n_ct, uint32_t nl);
+/* (the baby-step giant-step form of the same transform) Every step is r = G + b with n1 baby steps b and n2 giant steps
+ * G, and
+ *     out = sum_G rot_G( sum_b rot_{-G}(diag_{G+b}) * rot_b(x) ),
+ * which needs about n1 + n2 Galois keys where the call above needs n1 n2 (a 128 x 128 block: 30 keys of ~50 MB each at
+ * N = 2^16 in place of 254).  d_ct, d_out u64[n_ct][2][nl][N], not overlapping; h_gb[n1], h_gg[n2] HOST arrays of Galois
+ * elements; d_bkeys u64[n1][beta][2][D][N] and d_gkeys u64[n2][..]: slot k holds the key of element k, the slot of an
+ * element 1 is never read and either array may be null when all its elements are 1; d_pts u64[n2][n1][nl+K][N] from
+ * mkckks_encode_ext_batch, entry (t, b) the diagonal of step G_t + b rolled RIGHT by G_t slots; h_present HOST
+ * uint8[n2][n1]: the plaintext slot of an absent entry is never read, a giant row without a present entry costs nothing
+ * (its ModDown and ModUp included), a baby column without one is not computed.  Duplicate elements are allowed.
+ * Definition, bit for bit (notation of the call above; all residues canonical, every sum exact mod m_i):
+ *   babies, g = h_gb[b]:
+ *     Bb_b[i] = sum_j sigma_g(d_j[i]) kb_{b,j}[i] + [i < nl] [P]_{q_i} sigma_g(c0[i])
+ *     Ba_b[i] = sum_j sigma_g(d_j[i]) ka_{b,j}[i]
+ *     (g = 1:  Bb_b[i] = [i < nl] [P]_{q_i} c0[i],  Ba_b[i] = [i < nl] [P]_{q_i} c1[i])
+ *   inner sums, for each giant t:
+ *     Ub_t[i] = sum_{b present} pt_{t,b}[i] Bb_b[i],   Ua_t[i] = sum_{b present} pt_{t,b}[i] Ba_b[i]
+ *   giants, g = h_gg[t]:  g = 1 adds (Ub_t, Ua_t) to (A_b, A_a); otherwise v_t = ModDown(Ua_t) (u64[nl][N], word for word
+ *   mkckks_moddown_batch), e_j the mkckks_modup_batch digits of v_t, and
+ *     A_b[i] += sigma_g(Ub_t[i]) + sum_j sigma_g(e_j[i]) kgb_{t,j}[i]
+ *     A_a[i] +=                    sum_j sigma_g(e_j[i]) kga_{t,j}[i]
+ *   (Ub_t carries the factor P already: it is permuted on all nl + K slots and not multiplied again)
+ *   d_out = ( ModDown(A_b), ModDown(A_a) ).
+ * With n2 = 1 and h_gg[0] = 1 the call returns the words of mkckks_linear_transform_batch on the same keys, plaintexts
+ * and elements.  Scale, level and headroom follow that call.  Noise: one key switch per level of the tree and one ModDown
+ * rounding per giant, which enters before no plaintext product.  Workspace: babies, inner sums and giant digits are per
+ * ciphertext; the ciphertexts are taken in chunks of min(MKCKKS_CHUNK, max(1, cap / per-ciphertext words)) with a cap of
+ * 2 GiB (MKCKKS_BSGS_WS_MIB, in MiB, overrides it); the bits do not depend on the chunk.
+ * Refusals: MKCKKS_E_INVALID for null pointers, an even g or g >= 2N, n1 or n2 equal to 0 or above MKCKKS_BSGS_MAX, nl
+ * outside [1, L], an output that overlaps an input, arrays that are not 16-byte aligned, more than 6 key-switch digits;
+ * n_ct == 0 or no present entry at all is a no-op; a host-only context gives MKCKKS_E_NODEVICE. */
+#define MKCKKS_BSGS_MAX 64
+int mkckks_linear_transform_bsgs_batch(mkckks_ctx *c, const uint64_t *d_ct, const uint64_t *d_bkeys, const uint32_t *h_gb,
+                                       uint32_t n1, const uint64_t *d_gkeys, const uint32_t *h_gg, uint32_t n2,
+                                       const uint64_t *d_pts, const uint8_t *h_present, uint64_t *d_out, uint32_t n_ct,
+                                       uint32_t nl);
 
 /* ==== ciphertext products: cc->EvalMultKeyGen / cc->EvalMult(ct, ct) / cc->Relinearize / cc->EvalInnerProduct(ct, ct) ===
  * Upstream CryptoContext calls the reference never makes: everything its mains compute is linear in the encrypted

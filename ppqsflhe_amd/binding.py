@@ -102,6 +102,7 @@ SYMBOLS = {
     "mkckks_slot_sum_batch": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u32]),
     "mkckks_encode_ext_batch": (_int, [_vp, _vp, _vp, _u32, _u32, _dbl]),
     "mkckks_linear_transform_batch": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32]),
+    "mkckks_linear_transform_bsgs_batch": (_int, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _u32, _u32]),
     "mkckks_relin_keygen": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mkckks_tensor_sum_batch": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u32]),
     "mkckks_relinearize_batch": (_int, [_vp, _vp, _vp, _vp, _u32, _u32]),
@@ -616,6 +617,19 @@ class Context:
         arr = (C.c_uint32 * max(1, len(gs)))(*gs)
         self._check(self._L.mkckks_linear_transform_batch(self._h, _ptr(ct), _ptr(evks), _ptr(pts), arr, _ptr(out), len(gs),
                                                           n_ct, nl))
+
+    def linear_transform_bsgs(self, ct, bkeys, gb, gkeys, gg, pts, present, out, n_ct, nl):
+        """The baby-step giant-step form: out[b] = sum_t Rotate(sum_b pts[t][b] * Rotate(ct[b], gb[b]), gg[t]) before the
+        rescale.  bkeys [n1][beta][2][D][N] and gkeys [n2][..] (None when every element of the list is 1), gb / gg the
+        Galois elements (host integers), pts [n2][n1][nl+K][N] from encode_ext, present: n2 x n1 host flags."""
+        gb, gg = [int(g) for g in gb], [int(g) for g in gg]
+        flags = [1 if f else 0 for row in present for f in row]
+        a_gb, a_gg = (C.c_uint32 * max(1, len(gb)))(*gb), (C.c_uint32 * max(1, len(gg)))(*gg)
+        a_pr = (C.c_uint8 * max(1, len(flags)))(*flags)
+        if len(flags) != len(gb) * len(gg):
+            raise ValueError("present must be n2 rows of n1 flags")
+        self._check(self._L.mkckks_linear_transform_bsgs_batch(self._h, _ptr(ct), _ptr(bkeys), a_gb, len(gb), _ptr(gkeys),
+                                                               a_gg, len(gg), _ptr(pts), a_pr, _ptr(out), n_ct, nl))
 
     # ---- ciphertext products (include/mkckks.h: "ciphertext products")
     def relin_keygen(self, s, pk, u, e0, e1, evk):

@@ -533,6 +533,42 @@ int mkckks_linear_transform_batch(mkckks_ctx *c, const uint64_t *ct, const uint6
         c->eng->linear_transform(ct, evks, pts, h_g, out, n_rot, n_ct, nl);
     });
 }
+int mkckks_linear_transform_bsgs_batch(mkckks_ctx *c, const uint64_t *ct, const uint64_t *bkeys, const uint32_t *h_gb,
+                                       uint32_t n1, const uint64_t *gkeys, const uint32_t *h_gg, uint32_t n2,
+                                       const uint64_t *pts, const uint8_t *h_present, uint64_t *out, uint32_t n_ct,
+                                       uint32_t nl) {
+    return guarded([&] {
+        need(c && ct && h_gb && h_gg && pts && h_present && out, "null argument");
+        const mk::ParamSet &ps = c->eng->params();
+        need(n1 >= 1 && n1 <= MKCKKS_BSGS_MAX && n2 >= 1 && n2 <= MKCKKS_BSGS_MAX, "n1 and n2 must be in [1, MKCKKS_BSGS_MAX]");
+        need(nl >= 1 && nl <= ps.L, "nl out of range");
+        bool bkeyed = false, gkeyed = false, any = false;
+        for (uint32_t b = 0; b < n1; ++b) {
+            need_galois(ps, h_gb[b]);
+            bkeyed = bkeyed || h_gb[b] != 1u;
+        }
+        for (uint32_t t = 0; t < n2; ++t) {
+            need_galois(ps, h_gg[t]);
+            gkeyed = gkeyed || h_gg[t] != 1u;
+        }
+        need((bkeys || !bkeyed) && (gkeys || !gkeyed), "null argument");
+        need_aligned16({ct, bkeys, gkeys, pts, out});
+        const size_t ct_bytes = poly_bytes((unsigned __int128)n_ct * 2, nl, ps.n);
+        need(!ranges_meet(ct, ct_bytes, out, ct_bytes), "output overlaps input");
+        need(!ranges_meet(pts, poly_bytes((unsigned __int128)n1 * n2, nl + ps.K, ps.n), out, ct_bytes),
+             "output overlaps the plaintexts");
+        if (bkeyed)
+            need(!ranges_meet(bkeys, poly_bytes((unsigned __int128)n1 * ps.beta * 2, ps.D, ps.n), out, ct_bytes),
+                 "output overlaps the keys");
+        if (gkeyed)
+            need(!ranges_meet(gkeys, poly_bytes((unsigned __int128)n2 * ps.beta * 2, ps.D, ps.n), out, ct_bytes),
+                 "output overlaps the keys");
+        need(ps.num_parts(nl) <= 6, "more than 6 key-switch digits unsupported");
+        for (size_t k = 0; k < (size_t)n1 * n2; ++k) any = any || h_present[k];
+        if (!n_ct || !any) return;
+        c->eng->linear_transform_bsgs(ct, bkeys, h_gb, n1, gkeys, h_gg, n2, pts, h_present, out, n_ct, nl);
+    });
+}
 int mkckks_relin_keygen(mkckks_ctx *c, const int8_t *s, const uint64_t *pk, const int8_t *u, const int32_t *e0,
                         const int32_t *e1, uint64_t *evk) {
     return guarded([&] {

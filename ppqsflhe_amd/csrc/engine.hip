@@ -23,6 +23,7 @@
 #include "galois_kernels.hpp"
 #include "tensor_kernels.hpp"
 #include "lintrans_kernels.hpp"
+#include "bsgs_kernels.hpp"
 #include "poly_kernels.hpp"
 #include "relshare_kernels.hpp"
 #include "sampler_kernels.hpp"
@@ -635,6 +636,14 @@ Knobs Knobs::from_env() {
     }
     if (const char *e = std::getenv("MKCKKS_LT_ORDER")) {
         if (e[0] >= '0' && e[0] <= '2' && !e[1]) k.lt_order = e[0] - '0';
+    }
+    if (const char *e = std::getenv("MKCKKS_BSGS_FUSED")) {
+        if (!std::strcmp(e, "0")) k.bsgs_fused = 0;
+        else if (!std::strcmp(e, "1")) k.bsgs_fused = 1;
+    }
+    if (const char *e = std::getenv("MKCKKS_BSGS_WS_MIB")) {
+        const long v = std::atol(e);
+        if (v >= 1 && v <= (1l << 20)) k.bsgs_ws_mib = (uint32_t)v;
     }
     return k;
 }
@@ -2546,6 +2555,187 @@ void Engine::linear_transform(const u64 *ct, const u64 *evks, const u64 *pts, co
         });
         MK_HIP(hipGetLastError());
         moddown_core(til, pc, conv, out + done * ct_words, (size_t)nl * n, nullptr, 0, 2 * cnt, nl, false);
+    }
+}
+
+// The baby-step giant-step form (definition: include/mkckks.h; kernels: bsgs_kernels.hpp).  The plan is compacted on the
+// host first: a baby whose column has no present entry and a giant whose row has none are dropped (they cost nothing,
+// their ModDown and ModUp included), the giants with a key come first so that their Ua_t are one contiguous batch.
+// Per chunk: modup_core(c1); k_bsgs_baby; k_bsgs_inner; ONE moddown_core and ONE modup_core over the keyed giants of
+// every ciphertext of the chunk; k_bsgs_giant; moddown_core of both components.
+// Workspace: babies, inner sums and giant digits are per ciphertext (words per ciphertext below); the chunk is
+// min(knobs.chunk, max(1, cap / that)), cap = Knobs::bsgs_ws_mib (2 GiB; MKCKKS_BSGS_WS_MIB).  Every word of the result is
+// a function of its own ciphertext alone, so the bits do not depend on the chunk.
+void Engine::linear_transform_bsgs(const u64 *ct, const u64 *bkeys, const uint32_t *h_gb, uint32_t n1, const u64 *gkeys,
+                                   const uint32_t *h_gg, uint32_t n2, const u64 *pts, const uint8_t *h_present, u64 *out,
+                                   uint32_t n_ct, uint32_t nl) {
+    need_device();
+    check_nl(nl);
+    if (!n1 || !n2 || n1 > BSGS_MAX || n2 > BSGS_MAX) throw std::invalid_argument("n1 and n2 must be in [1, 64]");
+    const uint32_t n = ps_.n, K = ps_.K, ext = nl + K, nparts = ps_.num_parts(nl);
+    for (uint32_t b = 0; b < n1; ++b)
+        if (!galois_valid(h_gb[b], ps_.log_n)) throw std::invalid_argument("Galois element must be odd and below 2N");
+    for (uint32_t t = 0; t < n2; ++t)
+        if (!galois_valid(h_gg[t], ps_.log_n)) throw std::invalid_argument("Galois element must be odd and below 2N");
+    if (nparts > 6) throw std::invalid_argument("more than 6 key-switch digits unsupported");
+    if (!n_ct) return;
+    // the compacted plan
+    std::vector<uint32_t> babies, giants;
+    for (uint32_t b = 0; b < n1; ++b)
+        for (uint32_t t = 0; t < n2; ++t)
+            if (h_present[(size_t)t * n1 + b]) {
+                babies.push_back(b);
+                break;
+            }
+    for (int keyed = 1; keyed >= 0; --keyed)
+        for (uint32_t t = 0; t < n2; ++t) {
+            if ((h_gg[t] != 1u) != (keyed == 1)) continue;
+            for (uint32_t b = 0; b < n1; ++b)
+                if (h_present[(size_t)t * n1 + b]) {
+                    giants.push_back(t);
+                    break;
+                }
+        }
+    if (babies.empty()) return;
+    const uint32_t n1c = (uint32_t)babies.size(), n2c = (uint32_t)giants.size();
+    uint32_t nk = 0;
+    for (uint32_t t : giants) nk += h_gg[t] != 1u;
+    // device copy of the plan: bg[n1c] bk[n1c] gg[n2c] gk[n2c] ptidx[n2c][n1c]
+    std::vector<uint32_t> meta;
+    for (uint32_t b : babies) meta.push_back(h_gb[b]);
+    for (uint32_t b : babies) meta.push_back(b);
+    for (uint32_t t : giants) meta.push_back(h_gg[t]);
+    for (uint32_t t : giants) meta.push_back(t);
+    for (uint32_t t : giants)
+        for (uint32_t b : babies) meta.push_back(h_present[(size_t)t * n1 + b] ? t * n1 + b : BSGS_ABSENT);
+    if (meta.size() > lt_g_cap_) {
+        MK_HIP(hipStreamSynchronize(stream_));
+        if (d_lt_g_) MK_HIP(hipFree(d_lt_g_));
+        d_lt_g_ = nullptr;
+        lt_g_cap_ = 0;
+        MK_HIP(hipMalloc(&d_lt_g_, meta.size() * sizeof(uint32_t)));
+        lt_g_cap_ = meta.size();
+    }
+    MK_HIP(hipMemcpyAsync(d_lt_g_, meta.data(), meta.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream_));
+    MK_HIP(hipStreamSynchronize(stream_));
+    const uint32_t *d_bg = d_lt_g_, *d_bk = d_bg + n1c, *d_gg = d_bk + n1c, *d_gk = d_gg + n2c, *d_ptidx = d_gk + n2c;
+    std::vector<u64> pm(nl);
+    for (uint32_t i = 0; i < nl; ++i) pm[i] = ps_.p_mod(i);
+    const u64 *pmod = limb_vector("pmod_" + std::to_string(nl), pm);
+
+    const uint32_t log_t = std::min(ps_.log_n, LT_LOG_TILE);
+    const size_t ct_words = (size_t)2 * nl * n, qw = (size_t)nl * n, ew = (size_t)ext * n, kw = (size_t)K * n;
+    const uint32_t nmd = std::max(nk, 2u);  // polynomials per ciphertext of the larger ModDown
+    // words per ciphertext: c1's coefficients and digits, the babies, the inner sums, per keyed giant v_t, its coefficients
+    // and its digits, the accumulators, the scratch of the larger ModDown
+    // (the composition arm: a ciphertext (0, v_t), one key-switched giant and one permuted Ub_t more)
+    const bool fused = knobs_.bsgs_fused != 0;
+    const size_t w_comp = fused ? 0 : 2 * qw + 3 * ew;
+    const size_t per_ct = qw + nparts * ew + (size_t)n1c * 2 * ew + (size_t)n2c * 2 * ew + (size_t)nk * (2 * qw + nparts * ew) +
+                          2 * ew + (size_t)nmd * (kw + qw) + w_comp;
+    const size_t cap_words = (size_t)knobs_.bsgs_ws_mib * (1u << 20) / sizeof(u64);
+    const uint32_t chunk = (uint32_t)std::min<size_t>(std::min(knobs_.chunk, n_ct), std::max<size_t>(1, cap_words / per_ct));
+    u64 *ws = workspace(per_ct * chunk);
+    u64 *coef = ws, *dig = coef + chunk * qw, *bab = dig + (size_t)chunk * nparts * ew, *ub = bab + (size_t)chunk * n1c * 2 * ew;
+    u64 *ua = ub + (size_t)chunk * n2c * ew, *v = ua + (size_t)chunk * n2c * ew, *coef2 = v + (size_t)chunk * nk * qw;
+    u64 *dig2 = coef2 + (size_t)chunk * nk * qw, *til = dig2 + (size_t)chunk * nk * nparts * ew, *pc = til + (size_t)chunk * 2 * ew;
+    u64 *conv = pc + (size_t)chunk * nmd * kw, *ctg = conv + (size_t)chunk * nmd * qw, *tmp_t = ctg + (size_t)chunk * 2 * qw;
+    u64 *tmp_u = tmp_t + (size_t)chunk * 2 * ew;
+    const size_t evk_words = (size_t)ps_.beta * 2 * ps_.D * n;
+    const u64 *ones = fused ? nullptr : limb_vector("ones_" + std::to_string(ext), std::vector<u64>(ew, 1));
+    for (uint32_t done = 0; done < n_ct; done += chunk) {
+        const uint32_t cnt = std::min(chunk, n_ct - done);
+        const u64 *c = ct + done * ct_words;
+        modup_core(c + qw, ct_words, coef, dig, cnt, nl);
+        const uint32_t groups = ext << (ps_.log_n - log_t);
+        if (!fused) {
+            // MKCKKS_BSGS_FUSED=0: the same sums from the kernels the direct transform has.  k_lt_accum with ONE rotation
+            // and an all-ones plaintext is a baby (and the key-switched part of a giant, on the ciphertext (0, v_t));
+            // k_fma multiplies and adds over the extended basis; k_automorph permutes Ub_t.  Every step stores canonical
+            // residues of exact sums, so the bits are those of the fused kernels.  Layouts: babies [n1c][cnt][2][ext][N].
+            const EwGeom eg{n, nl, ps_.L};
+            const Opnd none{nullptr, 0, 0}, one{ones, 0, 0};
+            auto accum1 = [&](const u64 *cts, const u64 *digs, const u64 *key, const uint32_t *d_g, u64 *dst) {
+                LtArgs a{cts, digs, key, ones, d_g, pmod, dst, evk_words, 1, cnt, nl, ext, ps_.L, ps_.D, ps_.alpha, ps_.log_n, log_t,
+                         groups, cnt, 0u, 1u};
+                const uint64_t blocks = (uint64_t)((groups + LT_XCDS - 1) / LT_XCDS * LT_XCDS) * cnt;
+                if (blocks > 0x7fffffffu) throw std::invalid_argument("batch too large for one launch");
+                dispatch<1, 2, 3, 4, 5, 6>(nparts, [&](auto np) {
+                    k_lt_accum<decltype(np)::value><<<dim3((unsigned)blocks), LT_THREADS, 0, stream_>>>(a, d_limb_);
+                });
+                MK_HIP(hipGetLastError());
+            };
+            // out = x y + z (+ w) over `polys` polynomials of ext slots
+            auto fma = [&](Opnd x, Opnd y, Opnd z, Opnd w, u64 *o, size_t o_stride, uint32_t polys) {
+                k_fma<<<ew_grid(n, ext, polys), EW_THREADS, 0, stream_>>>(x, y, z, w, nullptr, 0, o, o_stride, 0, eg, d_limb_, ext);
+                MK_HIP(hipGetLastError());
+            };
+            for (uint32_t b = 0; b < n1c; ++b)
+                accum1(c, dig, h_gb[babies[b]] != 1u ? bkeys + (size_t)babies[b] * evk_words : nullptr, d_bg + b,
+                       bab + (size_t)b * cnt * 2 * ew);
+            for (uint32_t t = 0; t < n2c; ++t) {
+                bool first = true;
+                for (uint32_t b = 0; b < n1c; ++b) {
+                    const uint32_t idx = meta[2 * n1c + 2 * n2c + (size_t)t * n1c + b];
+                    if (idx == BSGS_ABSENT) continue;
+                    const Opnd pt{pts + (size_t)idx * ew, 0, 0};
+                    for (uint32_t k = 0; k < 2; ++k) {
+                        u64 *u = (k ? ua : ub) + (size_t)t * cnt * ew;
+                        fma(Opnd{bab + ((size_t)b * cnt * 2 + k) * ew, 2 * ew, 0}, pt, first ? none : Opnd{u, ew, 0}, none, u, ew, cnt);
+                    }
+                    first = false;
+                }
+            }
+            if (nk) {
+                moddown_core(ua, pc, conv, v, qw, nullptr, 0, nk * cnt, nl, false);
+                modup_core(v, qw, coef2, dig2, nk * cnt, nl);
+                MK_HIP(hipMemsetAsync(ctg, 0, (size_t)cnt * 2 * qw * sizeof(u64), stream_));
+            }
+            for (uint32_t t = 0; t < n2c; ++t) {
+                const u64 *ubt = ub + (size_t)t * cnt * ew, *uat = ua + (size_t)t * cnt * ew;
+                const Opnd zb = t ? Opnd{til, 2 * ew, 0} : none, za = t ? Opnd{til + ew, 2 * ew, 0} : none;
+                if (t < nk) {
+                    k_copy_slots<<<ew_grid(n, nl, cnt), EW_THREADS, 0, stream_>>>(v + (size_t)t * cnt * qw, qw, 0, ctg + qw, 2 * qw, 0, n);
+                    MK_HIP(hipGetLastError());
+                    accum1(ctg, dig2 + (size_t)t * cnt * nparts * ew, gkeys + (size_t)giants[t] * evk_words, d_gg + t, tmp_t);
+                    launch_automorph(ubt, tmp_u, (size_t)cnt * ext, h_gg[giants[t]]);
+                    fma(Opnd{tmp_t, 2 * ew, 0}, one, zb, Opnd{tmp_u, ew, 0}, til, 2 * ew, cnt);
+                    fma(Opnd{tmp_t + ew, 2 * ew, 0}, one, za, none, til + ew, 2 * ew, cnt);
+                } else {
+                    fma(Opnd{ubt, ew, 0}, one, zb, none, til, 2 * ew, cnt);
+                    fma(Opnd{uat, ew, 0}, one, za, none, til + ew, 2 * ew, cnt);
+                }
+            }
+            moddown_core(til, pc, conv, out + done * ct_words, qw, nullptr, 0, 2 * cnt, nl, false);
+            continue;
+        }
+        BsgsArgs a{};
+        a.ct = c; a.dig = dig; a.evks = bkeys; a.pts = nullptr; a.g = d_bg; a.pmod = pmod; a.til = bab;
+        a.evk_words = evk_words;
+        a.n_rot = n1c; a.cnt = cnt; a.nl = nl; a.ext = ext; a.L = ps_.L; a.D = ps_.D; a.alpha = ps_.alpha;
+        a.log_n = ps_.log_n; a.log_t = log_t; a.groups = groups; a.members = cnt; a.walk = 0; a.xcd_order = 1;
+        a.kidx = d_bk;
+        const uint64_t blocks = (uint64_t)((groups + LT_XCDS - 1) / LT_XCDS * LT_XCDS) * cnt;
+        if (blocks > 0x7fffffffu) throw std::invalid_argument("batch too large for one launch");
+        dispatch<1, 2, 3, 4, 5, 6>(nparts, [&](auto np) {
+            k_bsgs_baby<decltype(np)::value><<<dim3((unsigned)blocks), LT_THREADS, 0, stream_>>>(a, d_limb_);
+        });
+        MK_HIP(hipGetLastError());
+        BsgsInnerArgs in{bab, pts, d_ptidx, ub, ua, n1c, n2c, cnt, nl, ext, ps_.L, ps_.log_n, log_t, groups, cnt, 1u};
+        k_bsgs_inner<<<dim3((unsigned)blocks), LT_THREADS, 0, stream_>>>(in, d_limb_);
+        MK_HIP(hipGetLastError());
+        if (nk) {  // the keyed giants are giants [0, nk): Ua_t of all of them, one batch
+            moddown_core(ua, pc, conv, v, qw, nullptr, 0, nk * cnt, nl, false);
+            modup_core(v, qw, coef2, dig2, nk * cnt, nl);
+        }
+        BsgsArgs gi = a;
+        gi.ct = nullptr; gi.dig = dig2; gi.evks = gkeys; gi.g = d_gg; gi.til = til; gi.n_rot = nk; gi.kidx = d_gk;
+        gi.v = v; gi.ub = ub; gi.ua = ua; gi.n_all = n2c;
+        dispatch<1, 2, 3, 4, 5, 6>(nparts, [&](auto np) {
+            k_bsgs_giant<decltype(np)::value><<<dim3((unsigned)blocks), LT_THREADS, 0, stream_>>>(gi, d_limb_);
+        });
+        MK_HIP(hipGetLastError());
+        moddown_core(til, pc, conv, out + done * ct_words, qw, nullptr, 0, 2 * cnt, nl, false);
     }
 }
 

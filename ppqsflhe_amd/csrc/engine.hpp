@@ -83,6 +83,11 @@ struct Knobs {
     int poly_fused = 2;          // MKCKKS_POLY_FUSED=0/1: poly_tensor as the composition (eval_wsum per giant index on packed prefix
                                  // copies + tensor_sum + the constant column and term) or as k_poly_tensor; default:
                                  // poly_tensor_fused (profiles/poly_ab.txt)
+    int bsgs_fused = 1;          // MKCKKS_BSGS_FUSED=0: linear_transform_bsgs as the composition of k_lt_accum (one rotation, an
+                                 // all-ones plaintext) per baby and per giant, k_fma and k_automorph; default: k_bsgs_baby,
+                                 // k_bsgs_inner, k_bsgs_giant (profiles/lt_bsgs_ab.txt)
+    uint32_t bsgs_ws_mib = 2048; // MKCKKS_BSGS_WS_MIB: cap on the workspace of linear_transform_bsgs (babies, inner sums and
+                                 // giant digits are per ciphertext); the chunk shrinks to fit, down to one ciphertext
     static Knobs from_env();
 };
 
@@ -248,6 +253,13 @@ public:
     void encode_ext(const double *vals, u64 *pt, uint32_t n, uint32_t nl, double scale);
     void linear_transform(const u64 *ct, const u64 *evks, const u64 *pts, const uint32_t *h_g, u64 *out, uint32_t n_rot,
                           uint32_t n_ct, uint32_t nl);
+    //   linear_transform_bsgs: the baby-step giant-step form (kernels: bsgs_kernels.hpp; definition: include/mkckks.h):
+    //                     bkeys u64[n1][beta][2][D][N], gkeys u64[n2][..], pts u64[n2][n1][nl+K][N], h_gb / h_gg / h_present
+    //                     on the HOST; per chunk one ModUp of c1, the babies, the inner sums, one ModDown and one ModUp over
+    //                     all keyed giants, the giants, one ModDown per component
+    void linear_transform_bsgs(const u64 *ct, const u64 *bkeys, const uint32_t *h_gb, uint32_t n1, const u64 *gkeys,
+                               const uint32_t *h_gg, uint32_t n2, const u64 *pts, const uint8_t *h_present, u64 *out,
+                               uint32_t n_ct, uint32_t nl);
     // ciphertext products ("ciphertext products"; kernel: tensor_kernels.hpp)
     //   relin_keygen: evk = rekeygen with NTT(s_old) replaced by NTT(s)^2 (the re-encryption key from s^2 to s)
     //   tensor_sum:   out3[b] = sum_t (a0 b0, a0 b1 + a1 b0, a1 b1); a, b u64[n_terms][n_ct][2][nl][N], out3 u64[n_ct][3][nl][N]

@@ -98,6 +98,15 @@ struct LtOps<LT_INT> {
     }
     static MK_D void fold(Acc &, const LimbConst &, const PmK &) {}
     static MK_D u64 out(const Acc &a, const LimbConst &, const PmK &) { return a.v; }
+    // the pieces the baby-step giant-step kernels add (bsgs_kernels.hpp): an inner sum as a canonical residue, an outer
+    // sum of products of canonical residues, an outer sum of reduced inner sums; the cadences are those of add
+    static MK_D u64 red(const Sum &s, const LimbConst &lc, const PmK &) { return reduce_wide(s.h, s.l, lc); }
+    static MK_D void addw(Acc &a, Word x, Word pt, const LimbConst &lc, const PmK &) {
+        a.v = add_mod(a.v, mul_mod(x, pt, lc), lc.q);
+    }
+    static MK_D void addr(Acc &a, const Sum &s, const LimbConst &lc, const PmK &) {
+        a.v = add_mod(a.v, reduce_wide(s.h, s.l, lc), lc.q);
+    }
 };
 
 template <>
@@ -120,6 +129,13 @@ struct LtOps<LT_PM> {
         a.h = 0;
     }
     static MK_D u64 out(const Acc &a, const LimbConst &lc, const PmK &P) { return pm_reduce128(a.h, a.l, P, lc.q); }
+    static MK_D u64 red(const Sum &s, const LimbConst &lc, const PmK &P) { return pm_reduce128(s.h, s.l, P, lc.q); }
+    static MK_D void addw(Acc &a, Word x, Word pt, const LimbConst &, const PmK &) { mac128(a.h, a.l, x, pt); }
+    static MK_D void addr(Acc &a, const Sum &s, const LimbConst &lc, const PmK &P) {
+        const u64 u = pm_reduce128(s.h, s.l, P, lc.q);  // LT_PM_ROT residues and one carried: far below 2^(2k+6)
+        a.l += u;
+        a.h += a.l < u;
+    }
 };
 
 template <>
@@ -143,13 +159,28 @@ struct LtOps<LT_FP> {
     }
     static MK_D void fold(Acc &a, const LimbConst &lc, const PmK &) { a.v = fp_reduce(a.v, lc.qd, lc.qinv); }
     static MK_D u64 out(const Acc &a, const LimbConst &lc, const PmK &) { return fp_to_canonical(a.v, lc.qd, lc.qinv); }
+    static MK_D u64 red(const Sum &s, const LimbConst &lc, const PmK &) { return fp_to_canonical(s.s, lc.qd, lc.qinv); }
+    // x canonical: a product within 0.97 q; folded every LT_FP_ROT terms the sum stays within 0.51 q + 4 * 0.97 q
+    static MK_D void addw(Acc &a, Word x, Word pt, const LimbConst &lc, const PmK &) {
+        a.v += fp_mulmod_any(x, pt, lc.qd, lc.qinv);
+    }
+    static MK_D void addr(Acc &a, const Sum &s, const LimbConst &lc, const PmK &) { a.v += fp_reduce(s.s, lc.qd, lc.qinv); }
 };
 
 MK_D ulonglong2 lt_ld(const u64 *row, uint32_t pair) { return reinterpret_cast<const ulonglong2 *>(row)[pair]; }
 
+// What a tile does with the inner sums of its rotations (bsgs_kernels.hpp has the two other kernels):
+//   LT_ACCUM  k_lt_accum: multiplies them by the rotation's plaintext and sums over the rotations
+//   LT_BABY   k_bsgs_baby: stores each rotation's reduced pair to til u64[cnt][n_rot][2][ext][N]; no plaintext, no outer sum
+//   LT_GIANT  k_bsgs_giant: rotation r < n_rot is a giant WITH a key, whose own digits come from a.dig / a.v at item
+//             r cnt + item; in the place of [P] sigma(c0) stands sigma(Ub_r) on ALL ext slots, unmultiplied; the reduced
+//             sums are added over the giants, no plaintext; the giants [n_rot, n_all) have no key and add (Ub_r, Ua_r)
+// In the last two modes the key of rotation r is key slot a.kidx[r] (the engine compacts the plan).
+enum { LT_ACCUM = 0, LT_BABY = 1, LT_GIANT = 2 };
+
 // one (ciphertext, extended slot, output tile): all rotations
-template <int CLS, int NPARTS>
-MK_D void lt_tile(const LtArgs &a, const LimbConst &lc, uint32_t item, uint32_t slot, uint32_t id, uint32_t dbase,
+template <int CLS, int NPARTS, int MODE = LT_ACCUM, class Args = LtArgs>
+MK_D void lt_tile(const Args &a, const LimbConst &lc, uint32_t item, uint32_t slot, uint32_t id, uint32_t dbase,
                   ulonglong2 *lds) {
     typedef LtOps<CLS> Op;
     typedef typename Op::Word Word;
@@ -164,10 +195,23 @@ MK_D void lt_tile(const LtArgs &a, const LimbConst &lc, uint32_t item, uint32_t 
         cl[p] = min(c[p], pairs - 1u);  // clamped: loads stay inside the tile
     }
     // rows of this (item, slot): component 0 / 1 of the ciphertext (Q slots), the digits
-    const u64 *c0row = a.ct + ((size_t)item * 2 * a.nl + slot) * n;
-    const u64 *c1row = c0row + (size_t)a.nl * n;
-    const u64 *dig0 = a.dig + ((size_t)item * NPARTS * a.ext + slot) * n;  // digit j: a.ext rows further each
-    const Word pmod = Op::in(isq ? a.pmod[slot] : 0);
+    const u64 *c0row, *c1row, *dig0;
+    if constexpr (MODE != LT_GIANT) {
+        c0row = a.ct + ((size_t)item * 2 * a.nl + slot) * n;
+        c1row = c0row + (size_t)a.nl * n;
+        dig0 = a.dig + ((size_t)item * NPARTS * a.ext + slot) * n;  // digit j: a.ext rows further each
+    }
+    // giant r of this item (LT_GIANT): v_r in the place of c1 (read on Q slots only; the row index is clamped, not
+    // selected), Ub_r in the place of c0 (every slot)
+    auto giant_rows = [&](uint32_t r) __attribute__((always_inline)) {
+        if constexpr (MODE == LT_GIANT) {
+            const size_t it = (size_t)r * a.cnt + item;
+            c0row = a.ub + (it * a.ext + slot) * n;
+            dig0 = a.dig + (it * NPARTS * a.ext + slot) * n;
+            c1row = a.v + (it * a.nl + min(slot, a.nl - 1u)) * n;
+        }
+    };
+    const Word pmod = Op::in(MODE == LT_GIANT ? 1 : isq ? a.pmod[slot] : 0);
 
     // The prefetch registers of one rotation.  Every load below is unconditional and only its ADDRESS is selected (an
     // unrotated term reads c1 in the place of digit 0 and the plaintext row in the place of its absent key; a P slot reads
@@ -175,10 +219,17 @@ MK_D void lt_tile(const LtArgs &a, const LimbConst &lc, uint32_t item, uint32_t 
     // the arrays on the stack.  Words read through a substituted address are never used.
     ulonglong2 S[NT][LT_PAIRS], kb[NPARTS][LT_PAIRS], ka[NPARTS][LT_PAIRS], pt[LT_PAIRS];
     auto load = [&](uint32_t r, uint32_t g) __attribute__((always_inline)) {
-        const bool keyed = g != 1u;
-        const u64 *ptrow = a.pts + ((size_t)r * a.ext + slot) * n + dbase;
+        const bool keyed = MODE == LT_GIANT || g != 1u;
+        giant_rows(r);
+        // the stand-in address of an absent key: the plaintext row, or a row of this tile that the mode does read
+        const u64 *ptrow;
+        if constexpr (MODE == LT_ACCUM) {
+            ptrow = a.pts + ((size_t)r * a.ext + slot) * n + dbase;
 #pragma unroll
-        for (int p = 0; p < LT_PAIRS; ++p) pt[p] = lt_ld(ptrow, cl[p]);
+            for (int p = 0; p < LT_PAIRS; ++p) pt[p] = lt_ld(ptrow, cl[p]);
+        } else {
+            ptrow = dig0 + dbase;
+        }
         const uint32_t sbase = galois_src(dbase, g, a.log_n) & ~tmask;  // g = 1: the own tile
 #pragma unroll
         for (int j = 0; j < NPARTS; ++j) {
@@ -188,10 +239,12 @@ MK_D void lt_tile(const LtArgs &a, const LimbConst &lc, uint32_t item, uint32_t 
 #pragma unroll
             for (int p = 0; p < LT_PAIRS; ++p) S[j][p] = lt_ld(drow + sbase, cl[p]);
         }
-        const u64 *zrow = isq ? c0row : dig0;
+        const u64 *zrow = (MODE == LT_GIANT || isq) ? c0row : dig0;
 #pragma unroll
         for (int p = 0; p < LT_PAIRS; ++p) S[NPARTS][p] = lt_ld(zrow + sbase, cl[p]);
-        const u64 *key = a.evks + (size_t)r * a.evk_words + (size_t)id * n + dbase;
+        uint32_t kslot = r;
+        if constexpr (MODE != LT_ACCUM) kslot = a.kidx[r];
+        const u64 *key = a.evks + (size_t)kslot * a.evk_words + (size_t)id * n + dbase;
 #pragma unroll
         for (int j = 0; j < NPARTS; ++j) {
             const u64 *kbrow = keyed ? key + ((size_t)j * 2 + 0) * a.D * n : ptrow;  // g = 1: the key slot is never read
@@ -206,12 +259,12 @@ MK_D void lt_tile(const LtArgs &a, const LimbConst &lc, uint32_t item, uint32_t 
 
     typename Op::Acc accb[LT_PAIRS][2], acca[LT_PAIRS][2];
     uint32_t g = a.g[0], pending = 0;
-    load(0, g);
+    if (MODE != LT_GIANT || a.n_rot) load(0, g);  // a plan may have no giant with a key (a.g has an entry all the same)
     for (uint32_t r = 0; r < a.n_rot; ++r) {
         // this rotation's operands leave the prefetch registers: the source tiles through LDS, permuted (g = 1: the
         // identity, so an unrotated term of a Q slot takes the same way; on a P slot it adds nothing and only prefetches)
         ulonglong2 d[NT][LT_PAIRS], ckb[NPARTS][LT_PAIRS], cka[NPARTS][LT_PAIRS], cpt[LT_PAIRS];
-        const bool keyed = g != 1u, active = keyed || isq;  // block-uniform
+        const bool keyed = MODE == LT_GIANT || g != 1u, active = keyed || isq;  // block-uniform
         if (active) {
             __syncthreads();  // the previous rotation's reads are done
 #pragma unroll
@@ -232,7 +285,7 @@ MK_D void lt_tile(const LtArgs &a, const LimbConst &lc, uint32_t item, uint32_t 
         }
 #pragma unroll
         for (int p = 0; p < LT_PAIRS; ++p) {
-            cpt[p] = pt[p];
+            if constexpr (MODE == LT_ACCUM) cpt[p] = pt[p];
 #pragma unroll
             for (int j = 0; j < NPARTS; ++j) {
                 ckb[j][p] = kb[j][p];
@@ -243,8 +296,19 @@ MK_D void lt_tile(const LtArgs &a, const LimbConst &lc, uint32_t item, uint32_t 
             g = a.g[r + 1];
             load(r + 1, g);
         }
+        // a baby's pair of this tile: an unrotated baby is zero on the P slots
+        ulonglong2 *bb = nullptr, *ba = nullptr;
+        if constexpr (MODE == LT_BABY) {
+            bb = reinterpret_cast<ulonglong2 *>(a.til + ((((size_t)item * a.n_rot + r) * 2 + 0) * a.ext + slot) * n + dbase);
+            ba = bb + (size_t)a.ext * (n / 2);
+            if (!active) {
+#pragma unroll
+                for (int p = 0; p < LT_PAIRS; ++p)
+                    if (c[p] < pairs) bb[c[p]] = ba[c[p]] = make_ulonglong2(0, 0);
+            }
+        }
         if (!active) continue;
-        if (Op::FOLD_ROT && pending == Op::FOLD_ROT) {
+        if (MODE != LT_BABY && Op::FOLD_ROT && pending == Op::FOLD_ROT) {
 #pragma unroll
             for (int p = 0; p < LT_PAIRS; ++p) {
 #pragma unroll
@@ -256,6 +320,7 @@ MK_D void lt_tile(const LtArgs &a, const LimbConst &lc, uint32_t item, uint32_t 
             pending = 0;
         }
         ++pending;
+        ulonglong2 rb[LT_PAIRS], ra[LT_PAIRS];  // LT_BABY: the reduced pair
 #pragma unroll
         for (int p = 0; p < LT_PAIRS; ++p) {
 #pragma unroll
@@ -272,10 +337,57 @@ MK_D void lt_tile(const LtArgs &a, const LimbConst &lc, uint32_t item, uint32_t 
                 } else {
                     Op::mac(sa, w(d[0][p]), pmod, 0, lc, P);  // [P] c1
                 }
-                if (isq) Op::mac(sb, w(d[NPARTS][p]), pmod, NPARTS, lc, P);  // [P] sigma(c0)
-                const Word ptw = w(cpt[p]);
-                Op::add(accb[p][h], sb, ptw, lc, P);
-                Op::add(acca[p][h], sa, ptw, lc, P);
+                // [P] sigma(c0) (LT_GIANT: sigma(Ub_r), every slot)
+                if (MODE == LT_GIANT || isq) Op::mac(sb, w(d[NPARTS][p]), pmod, NPARTS, lc, P);
+                if constexpr (MODE == LT_ACCUM) {
+                    const Word ptw = w(cpt[p]);
+                    Op::add(accb[p][h], sb, ptw, lc, P);
+                    Op::add(acca[p][h], sa, ptw, lc, P);
+                } else if constexpr (MODE == LT_GIANT) {
+                    Op::addr(accb[p][h], sb, lc, P);
+                    Op::addr(acca[p][h], sa, lc, P);
+                } else {
+                    (h ? rb[p].y : rb[p].x) = Op::red(sb, lc, P);
+                    (h ? ra[p].y : ra[p].x) = Op::red(sa, lc, P);
+                }
+            }
+        }
+        if constexpr (MODE == LT_BABY) {
+#pragma unroll
+            for (int p = 0; p < LT_PAIRS; ++p)
+                if (c[p] < pairs) {
+                    bb[c[p]] = rb[p];
+                    ba[c[p]] = ra[p];
+                }
+        }
+    }
+    if constexpr (MODE == LT_BABY) return;
+    if constexpr (MODE == LT_GIANT) {  // the giants without a key: (Ub_r, Ua_r) of the own tile, as they are
+        for (uint32_t r = a.n_rot; r < a.n_all; ++r) {
+            const size_t row = (((size_t)r * a.cnt + item) * a.ext + slot) * n + dbase;
+            if (Op::FOLD_ROT && pending == Op::FOLD_ROT) {
+#pragma unroll
+                for (int p = 0; p < LT_PAIRS; ++p) {
+#pragma unroll
+                    for (int h = 0; h < 2; ++h) {
+                        Op::fold(accb[p][h], lc, P);
+                        Op::fold(acca[p][h], lc, P);
+                    }
+                }
+                pending = 0;
+            }
+            ++pending;
+#pragma unroll
+            for (int p = 0; p < LT_PAIRS; ++p) {
+                const ulonglong2 xb = lt_ld(a.ub + row, cl[p]), xa = lt_ld(a.ua + row, cl[p]);
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    typename Op::Sum sb, sa;
+                    Op::mac(sb, Op::in(h ? xb.y : xb.x), pmod, 0, lc, P);
+                    Op::mac(sa, Op::in(h ? xa.y : xa.x), pmod, 0, lc, P);
+                    Op::addr(accb[p][h], sb, lc, P);
+                    Op::addr(acca[p][h], sa, lc, P);
+                }
             }
         }
     }
@@ -292,7 +404,40 @@ MK_D void lt_tile(const LtArgs &a, const LimbConst &lc, uint32_t item, uint32_t 
     }
 }
 
-// grid.x = round_up(groups, 8) * members.  NPARTS is the digit count of the level
+// the (group, member) of a workgroup under the args' grid order; grid.x = round_up(groups, 8) * members
+template <class Args>
+MK_D void lt_place(const Args &a, uint32_t &grp, uint32_t &m) {
+    if (a.xcd_order) {  // ids congruent mod 8 share an XCD: a group's members follow each other there
+        const uint32_t seq = blockIdx.x / LT_XCDS;
+        m = seq % a.members;
+        grp = (seq / a.members) * LT_XCDS + blockIdx.x % LT_XCDS;
+    } else {
+        const uint32_t padded = gridDim.x / a.members;
+        m = blockIdx.x / padded;
+        grp = blockIdx.x % padded;
+    }
+}
+
+// a workgroup of k_lt_accum and of the two kernels of bsgs_kernels.hpp that share its tile
+template <int NPARTS, int MODE, class Args>
+MK_D void lt_block(const Args &a, const LimbConst *limb, ulonglong2 *lds) {
+    uint32_t grp, m;
+    lt_place(a, grp, m);
+    if (grp >= a.groups) return;
+    const uint32_t log_tiles = a.log_n - a.log_t;
+    const uint32_t slot = grp >> log_tiles, dbase = (grp & ((1u << log_tiles) - 1u)) << a.log_t;
+    const uint32_t id = limb_id_of(slot, a.nl, a.L);
+    const LimbConst lc = limb[id];
+    const uint32_t first = a.walk ? 0u : m, last = a.walk ? a.cnt : m + 1u;
+    for (uint32_t item = first; item < last; ++item) {
+        if (lc.fp) lt_tile<LT_FP, NPARTS, MODE>(a, lc, item, slot, id, dbase, lds);
+        else if (lc.pm) lt_tile<LT_PM, NPARTS, MODE>(a, lc, item, slot, id, dbase, lds);
+        else lt_tile<LT_INT, NPARTS, MODE>(a, lc, item, slot, id, dbase, lds);
+    }
+}
+
+// NPARTS is the digit count of the level.  The body is lt_block's, written out: through the helper two instances compile
+// to other register counts than profiles/linear_transform_static.txt records
 template <int NPARTS>
 __global__ __launch_bounds__(LT_THREADS) void k_lt_accum(LtArgs a, const LimbConst *limb) {
     __shared__ ulonglong2 lds[(NPARTS + 1) * LT_TILE_PAIRS];

@@ -12,16 +12,67 @@
 // <rotkeys> is the file rotKeyGen --steps wrote for the key the input is under (a file fuseEvalKeys made of the parties'
 // shares works unchanged); a step it lacks is an error that names the step.  The output keeps the input's envelope form
 // (JSON or MKWS) and the layers' names and shapes.
+// With a trailing `--bsgs <n1|auto>` the transform runs in its baby-step giant-step form (bsgs.hpp;
+// mkckks_linear_transform_bsgs_batch): the key file needs the keys of the plan's baby and giant steps only, about
+// n1 + n2 where the direct form needs one per diagonal.  `linearTransform <cc_path> --bsgs-steps <n1|auto>
+// (<diagonals.json> | --block <matrix.json>)` needs no device and no key file: it prints the plan's steps, the list
+// rotKeyGen --steps takes.
+#include "bsgs.hpp"
 #include "lintrans.hpp"
 #include "rotkeys.hpp"
 using namespace mkh;
 
+// linearTransform <cc_path> --bsgs-steps <n1|auto> (<diagonals.json> | --block <matrix.json>)
+static int bsgs_steps_main(int argc, char *argv[]) {
+    const bool block = argc == 6;
+    if (block && std::string(argv[4]) != "--block") return -1;
+    uint32_t n1 = 0;
+    std::string err = bsgs_parse_n1(argv[3], n1);
+    CcFile cc;
+    if (err.empty()) {
+        try {
+            cc = read_cc(argv[1]);
+        } catch (const std::exception &) {
+            std::cerr << "[lintrans] ERROR: Failed to load CryptoContext from " << argv[1] << std::endl;
+            return 1;
+        }
+    }
+    Diagonals dg;
+    BsgsPlan plan;
+    const size_t slots = err.empty() ? (size_t)1 << (cc.p.log_n - 1) : 0;
+    if (err.empty()) err = load_diagonals(argv[block ? 5 : 4], block, slots, dg);
+    if (err.empty()) err = bsgs_plan(dg, slots, n1, false, plan);
+    if (!err.empty()) {
+        std::cerr << "[lintrans] ERROR: " << err << std::endl;
+        return 1;
+    }
+    std::cout << bsgs_steps_line(plan) << std::endl;
+    return 0;
+}
+
 int main(int argc, char *argv[]) {
     auto usage = [&] {
         std::cerr << "Usage: " << argv[0]
-                  << " <cc_path> <rotkeys> (<diagonals.json> | --block <matrix.json>) <input_encfile> <output_encfile>" << std::endl;
+                  << " <cc_path> <rotkeys> (<diagonals.json> | --block <matrix.json>) <input_encfile> <output_encfile>"
+                     " [--bsgs <n1|auto>]\n       "
+                  << argv[0] << " <cc_path> --bsgs-steps <n1|auto> (<diagonals.json> | --block <matrix.json>)" << std::endl;
         return 1;
     };
+    if ((argc == 5 || argc == 6) && std::string(argv[2]) == "--bsgs-steps") {
+        const int rc = bsgs_steps_main(argc, argv);
+        return rc < 0 ? usage() : rc;
+    }
+    bool bsgs = false;
+    uint32_t bsgs_n1 = 0;
+    if (argc >= 8 && std::string(argv[argc - 2]) == "--bsgs") {
+        const std::string err = bsgs_parse_n1(argv[argc - 1], bsgs_n1);
+        if (!err.empty()) {
+            std::cerr << "[lintrans] ERROR: " << err << std::endl;
+            return 1;
+        }
+        bsgs = true;
+        argc -= 2;
+    }
     if (argc != 6 && argc != 7) return usage();
     const bool block = argc == 7;
     if (block && std::string(argv[3]) != "--block") return usage();
@@ -55,14 +106,35 @@ int main(int argc, char *argv[]) {
             return 1;
         }
         const size_t key_words = (size_t)beta * 2 * D * N;
-        std::vector<uint32_t> gs(n_rot);
-        std::vector<const std::vector<uint64_t> *> step_keys(n_rot, nullptr);
-        for (size_t k = 0; k < n_rot; ++k) {
-            Session::check(mkckks_galois_element(s.ctx(), dg.steps[k], &gs[k]));
+        // the steps whose keys the call reads: the diagonals' own, or (--bsgs) the plan's babies, then its giants
+        BsgsPlan plan;
+        if (bsgs) {
+            const std::string perr = bsgs_plan(dg, slots, bsgs_n1, true, plan);
+            if (!perr.empty()) {
+                std::cerr << "[lintrans] ERROR: " << perr << std::endl;
+                return 1;
+            }
+        }
+        const size_t n1 = plan.babies.size(), n2 = plan.giants.size();
+        std::vector<int32_t> key_steps = dg.steps;
+        if (bsgs) {
+            key_steps = plan.babies;
+            key_steps.insert(key_steps.end(), plan.giants.begin(), plan.giants.end());
+        }
+        const size_t n_keys = key_steps.size();
+        std::vector<uint32_t> gs(n_keys);
+        std::vector<const std::vector<uint64_t> *> step_keys(n_keys, nullptr);
+        for (size_t k = 0; k < n_keys; ++k) {
+            Session::check(mkckks_galois_element(s.ctx(), key_steps[k], &gs[k]));
             if (gs[k] == 1) continue;  // no rotation: no key
+            if (bsgs && k < n1) {      // a baby no present entry uses is not computed: no key
+                bool used = false;
+                for (size_t t = 0; t < n2; ++t) used = used || plan.present[t * n1 + k];
+                if (!used) continue;
+            }
             const auto it = rk.keys.find(gs[k]);
             if (it == rk.keys.end()) {
-                std::cerr << "[lintrans] ERROR: rotation keys " << keys_path << " have no key for step " << dg.steps[k]
+                std::cerr << "[lintrans] ERROR: rotation keys " << keys_path << " have no key for step " << key_steps[k]
                           << " (Galois element " << gs[k] << "); rotKeyGen --steps makes the keys of the diagonals' steps" << std::endl;
                 return 1;
             }
@@ -97,15 +169,22 @@ int main(int argc, char *argv[]) {
             uint64_t *d_in = s.to_device(flat.data(), flat.size());
             seeds.expand(s, d_in, nl, 0, B);
             // the diagonals over the extended basis, at the scaling factor of a plaintext product with these ciphertexts
-            double *d_vals = s.to_device(dg.values.data(), dg.values.size());
-            uint64_t *d_pts = s.alloc<uint64_t>(n_rot * (size_t)(nl + K) * N);
-            Session::check(mkckks_encode_ext_batch(s.ctx(), d_vals, d_pts, (uint32_t)n_rot, nl, sf));
-            uint64_t *d_keys = s.alloc<uint64_t>(n_rot * key_words);
-            for (size_t k = 0; k < n_rot; ++k)
+            const std::vector<double> &vals = bsgs ? plan.values : dg.values;  // --bsgs: [n2][n1][slots], absent entries zero
+            const size_t n_pts = vals.size() / slots;
+            double *d_vals = s.to_device(vals.data(), vals.size());
+            uint64_t *d_pts = s.alloc<uint64_t>(n_pts * (size_t)(nl + K) * N);
+            Session::check(mkckks_encode_ext_batch(s.ctx(), d_vals, d_pts, (uint32_t)n_pts, nl, sf));
+            uint64_t *d_keys = s.alloc<uint64_t>(n_keys * key_words);  // --bsgs: the babies' slots, then the giants'
+            for (size_t k = 0; k < n_keys; ++k)
                 if (step_keys[k])
                     Session::check(mkckks_upload(s.ctx(), d_keys + k * key_words, step_keys[k]->data(), key_words * sizeof(uint64_t)));
             uint64_t *d_lt = s.alloc<uint64_t>(B * (size_t)2 * nl * N);
-            Session::check(mkckks_linear_transform_batch(s.ctx(), d_in, d_keys, d_pts, gs.data(), d_lt, (uint32_t)n_rot, (uint32_t)B, nl));
+            if (bsgs)
+                Session::check(mkckks_linear_transform_bsgs_batch(s.ctx(), d_in, d_keys, gs.data(), (uint32_t)n1, d_keys + n1 * key_words,
+                                                                  gs.data() + n1, (uint32_t)n2, d_pts, plan.present.data(), d_lt,
+                                                                  (uint32_t)B, nl));
+            else
+                Session::check(mkckks_linear_transform_batch(s.ctx(), d_in, d_keys, d_pts, gs.data(), d_lt, (uint32_t)n_rot, (uint32_t)B, nl));
             // the bookkeeping of a plaintext product (scale_aggregate's --slot-weights rules)
             Ciphertext meta = first;
             uint64_t *d_out = d_lt;
@@ -122,6 +201,9 @@ int main(int argc, char *argv[]) {
             }
             store_agg_items(s, items, d_out, meta, outputJson);
             std::cout << "[lintrans] " << B << " ciphertext(s), " << n_rot << " diagonal(s) each, " << slots << " slots\n";
+            if (bsgs)
+                std::cout << "[lintrans] bsgs n1=" << plan.n1 << ": " << plan.n_babies << " baby and " << plan.n_giants
+                          << " giant key(s)\n";
         }
         try {
             write_envelope(outputJson, output_encfile, binary);
