@@ -573,6 +573,82 @@ int mkckks_poly_eval_batch(mkckks_ctx *c, const uint64_t *d_ct, const uint64_t *
                            uint32_t degree, uint64_t *d_out, uint32_t n_ct, uint32_t nl, double scale_in,
                            double *scale_out);
 
+/* ==== Chebyshev series: cc->EvalChebyshevSeries / EvalChebyshevFunction (ckksrns-advancedshe), on the machinery above =====
+ * p(u) = c_0 T_0(u) + c_1 T_1(u) + ... + c_d T_d(u), 2 <= d <= 63, T_k the Chebyshev polynomials of the first kind, for
+ * a function fitted on an interval [a, b]: |T_k| <= 1 there and the coefficients of a fit decay, where the power-basis
+ * coefficients of the same polynomial grow with the degree (the interpolant of 1 / sqrt(t) on [0.25, 4]: 5.0 at d = 15,
+ * 9.3e2 at d = 31, 3.6e8 at d = 63) and every bit of that growth is a bit of the ciphertext's precision.  c_0 is the
+ * plain coefficient of T_0 (numpy.polynomial.chebyshev's convention); upstream's EvalChebyshevSeries takes c_0 / 2 there.
+ * Upstream calls the reference never makes.
+ *
+ * Interval.  (a, b) exactly (-1, 1): u = x at nl_u = nl limbs, S_u = S_in.  Otherwise one level is spent: alpha = 2 / (b - a),
+ * beta = -(a + b) / (b - a), nl_u = nl - 1, Sigma_1 = mkckks_scaling_factor(L - nl_u) * q_{nl-1} and
+ *     u = mkckks_rescale_batch(mkckks_affine_batch(x, alpha * (Sigma_1 / S_in), beta * Sigma_1)),
+ * so u = alpha x + beta sits at the standard scale of its level, S_u = mkckks_scaling_factor(L - nl_u).  All in doubles, in
+ * the order written.
+ * Affine map: out = M_a * in + (M_c, 0) with M_a = rint(w_mul), M_c = rint(w_add) as exact integers (the rule of M_{j,i} in
+ * the polynomial block, its refusals included), pointwise mod q_t on nl limbs; M_c is added to every word of component 0.
+ * No rescale: the result has scale S_in * M_a.
+ * Ladder of a base u (T_1 = u, T_0 = the constant 1 with scale 1): for k >= 2 with i = ceil(k / 2), j = k - i (i - j is 0 or 1)
+ *     T_k = 2 T_i T_j - T_{i-j}
+ *     T_k = mkckks_rescale_batch(mkckks_relinearize_batch(cheb_tensor(T_i, T_j, T_{i-j}; w))) at nl_k = nl_i - 1 limbs,
+ *     S_k = S_i * S_j / q_{nl_i - 1},   w = S_i * S_j / S_{i-j}   (the product first, then the quotient; S_0 = 1),
+ * the index split, limb counts and scales of the power ladder above (the factor 2 is an integer and leaves the scale
+ * alone).  T_{jB} = T_j(T_B): the giants are the same ladder on y = T_B.
+ * Ladder step before relinearisation, cheb_tensor(a, b, t; w), on the first nl limbs of a, b, t (each read in place at its
+ * own limb count >= nl), pointwise mod q_l, M = rint(w) as an exact integer by the rule of M_{j,i}:
+ *     d0 = 2 a0 b0 - M t0,   d1 = 2 (a0 b1 + a1 b0) - M t1,   d2 = 2 a1 b1      (t absent: t0 = 1, t1 = 0)
+ * M makes the scale of t equal to S_a * S_b exactly, in an integer, so the difference is formed before the rescale.  All
+ * results canonical.
+ * Block rewrite.  With the plan (B, G, nl_T, nl_out, limb counts) = mkckks_poly_plan(d, nl_u) and T_{jB+i} = 2 T_i T_{jB} -
+ * T_{(j-1)B+(B-i)} for j >= 1, 0 < i < B, the series becomes sum_j sum_i m_{j,i} T_i T_{jB}.  In doubles, in this order:
+ *     c' = c padded with zeros to B * G
+ *     for j = G - 1 down to 1:  for i = B - 1 down to 1:  m[j][i] = 2 c'[jB+i];  c'[(j-1)B + (B-i)] -= c'[jB+i]
+ *                               m[j][0] = c'[jB]
+ *     m[0][i] = c'[i] for 0 <= i < B
+ * Weights: w_{j,i} = m_{j,i} * (Sigma / (S_{T_i} * S_{y_j})) exactly as mkckks_poly_weights forms them from c (an m of zero
+ * gives an exact zero), S_out and Sigma as there.  Outer sum: mkckks_poly_tensor_batch with babies T_1 .. T_{B-1} and giants
+ * T_B, T_{2B}, ..; then mkckks_relinearize_batch at nl_T and mkckks_rescale_batch at nl_T and nl_T - 1: u64[n_ct][2][nl_out][N]
+ * at scale S_out.  Cost: that of mkckks_poly_eval_batch at the same degree, plus the level and the streaming pass of the map.
+ * Headroom, the caller's: Sigma * sum |m_{j,i}| < q_0 ... q_{nl_T-1} / 2 suffices for |u| <= 1, because |T_k| <= 1 (evalPoly
+ * --cheb checks it).  Outside [a, b] the T_k grow like the powers and nothing holds.
+ * Refusals of the compute calls follow the polynomial block: MKCKKS_E_INVALID for null pointers (d_t alone may be null),
+ * arrays that are not 16-byte aligned, an output that overlaps an input (mkckks_affine_batch alone accepts an output that
+ * IS its input), limb counts outside their ranges, a >= b or a non-finite bound, a weight that is not finite or does not
+ * fit half the modulus of its level (a ladder step's weight S_i * S_j included), a plan with nl_out < 1 (the message names
+ * the limbs needed); a zero n_ct is a no-op; a host-only context gives MKCKKS_E_NODEVICE.
+ * MKCKKS_CHEB_FUSED=0 runs the ladder step from the kernels of the blocks above (packed prefix copies, the tensor
+ * product, doubling and - M t by the weighted sum's kernel and the constant column's), =1 as the fused kernel; unset, the
+ * engine chooses.  The bits are the same. */
+/* (cc->EvalMult(ct, const) + cc->EvalAdd(ct, const)) d_out = M_a * d_in + (M_c, 0); d_in, d_out u64[n_ct][2][nl][N].  d_out
+ * may be exactly d_in. */
+int mkckks_affine_batch(mkckks_ctx *c, const uint64_t *d_in, uint64_t *d_out, uint32_t n_ct, uint32_t nl, double w_mul,
+                        double w_add);
+/* One ladder step before relinearisation for caller-supplied operands: d_a u64[n_ct][2][nl_a][N], d_b ..[nl_b].., d_t
+ * ..[nl_t].. or null (the constant; nl_t is then ignored), each limb count in [nl, L]; d_a == d_b squares (two polynomials
+ * are read) and needs nl_a == nl_b.  d_out3 u64[n_ct][3][nl][N] overlaps no input. */
+int mkckks_cheb_tensor_batch(mkckks_ctx *c, const uint64_t *d_a, uint32_t nl_a, const uint64_t *d_b, uint32_t nl_b,
+                             const uint64_t *d_t, uint32_t nl_t, double w, uint64_t *d_out3, uint32_t n_ct, uint32_t nl);
+/* The ladder: d_out = T_1 .. T_n of d_u u64[n_ct][2][nl][N] at scale scale_in, packed like the output of
+ * mkckks_powers_batch (T_k u64[n_ct][2][nl_k][N] directly behind T_{k-1}); h_nl_out / h_scale_out (HOST, n entries each,
+ * either may be null) receive nl_k and S_k.  1 <= n <= 64 with nl - ceil(log2 n) >= 1.  Bit-identical to the loop of
+ * mkckks_cheb_tensor_batch + mkckks_relinearize_batch + mkckks_rescale_batch.  d_out overlaps neither d_u nor the key. */
+int mkckks_cheb_ladder_batch(mkckks_ctx *c, const uint64_t *d_u, const uint64_t *d_rlk, uint64_t *d_out, uint32_t n_ct,
+                             uint32_t nl, uint32_t n, double scale_in, uint32_t *h_nl_out, double *h_scale_out);
+/* Host-only and pure (works on a device = -1 context).  h_coef: the degree + 1 series coefficients c_0 .. c_d; nl and
+ * scale_in are those of u.  h_w (HOST, double[G][B]) receives w_{j,i}, *scale_out receives S_out.  Refusals as
+ * mkckks_poly_weights. */
+int mkckks_cheb_weights(const mkckks_ctx *c, const double *h_coef, uint32_t degree, uint32_t nl, double scale_in,
+                        double *h_w, double *scale_out);
+/* The whole algorithm, workspace-chunked like mkckks_poly_eval_batch: d_out u64[n_ct][2][nl_out][N] = p(alpha d_ct + beta),
+ * scale *scale_out (nullable) = S_out.  Bit-identical to mkckks_affine_batch + mkckks_rescale_batch (unless (a, b) is
+ * (-1, 1)) + mkckks_cheb_ladder_batch (on u with n = B, then on y = its T_B with n = G - 1) + mkckks_cheb_weights +
+ * mkckks_poly_tensor_batch + mkckks_relinearize_batch + mkckks_rescale_batch twice.  d_ct is not modified; d_out overlaps
+ * neither d_ct nor the key. */
+int mkckks_cheb_eval_batch(mkckks_ctx *c, const uint64_t *d_ct, const uint64_t *d_rlk, const double *h_coef,
+                           uint32_t degree, double a, double b, uint64_t *d_out, uint32_t n_ct, uint32_t nl,
+                           double scale_in, double *scale_out);
+
 /* ---- cc->Encrypt(pk, pt)  (client/src/encryptModelWeights.cpp:83,91,110) --
  * d_pt u64[n_ct][nl][N] encoded plaintexts (EVALUATION); v int8[n_ct][N];
  * e0,e1 int32[n_ct][N]; out u64[n_ct][2][nl][N]. */

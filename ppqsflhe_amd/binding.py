@@ -112,6 +112,11 @@ SYMBOLS = {
     "mkckks_poly_weights": (_int, [_vp, _vp, _u32, _u32, _dbl, _vp, C.POINTER(_dbl)]),
     "mkckks_poly_tensor_batch": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32]),
     "mkckks_poly_eval_batch": (_int, [_vp, _vp, _vp, _vp, _u32, _vp, _u32, _u32, _dbl, C.POINTER(_dbl)]),
+    "mkckks_affine_batch": (_int, [_vp, _vp, _vp, _u32, _u32, _dbl, _dbl]),
+    "mkckks_cheb_tensor_batch": (_int, [_vp, _vp, _u32, _vp, _u32, _vp, _u32, _dbl, _vp, _u32, _u32]),
+    "mkckks_cheb_ladder_batch": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _dbl, _vp, _vp]),
+    "mkckks_cheb_weights": (_int, [_vp, _vp, _u32, _u32, _dbl, _vp, C.POINTER(_dbl)]),
+    "mkckks_cheb_eval_batch": (_int, [_vp, _vp, _vp, _vp, _u32, _dbl, _dbl, _vp, _u32, _u32, _dbl, C.POINTER(_dbl)]),
     "mkckks_evk_sum": (_int, [_vp, _vp, _vp, _u32, _u32]),
     "mkckks_relin_share": (_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "mkckks_keygen_join": (_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
@@ -701,6 +706,49 @@ class Context:
         s_out = C.c_double()
         self._check(self._L.mkckks_poly_eval_batch(self._h, _ptr(ct), _ptr(rlk), c.ctypes.data, c.size - 1, _ptr(out), n_ct,
                                                    int(nl), float(scale_in), C.byref(s_out)))
+        return s_out.value
+
+    # ---- Chebyshev series (include/mkckks.h: "Chebyshev series")
+    def affine(self, inp, out, n_ct, nl, w_mul, w_add):
+        """out = rint(w_mul) * inp + (rint(w_add), 0) as exact integers mod q_t; no rescale; out may be inp."""
+        self._check(self._L.mkckks_affine_batch(self._h, _ptr(inp), _ptr(out), n_ct, int(nl), float(w_mul), float(w_add)))
+
+    def cheb_tensor(self, a, nl_a, b, nl_b, t, nl_t, w, out3, n_ct, nl):
+        """out3 [n_ct][3][nl][N] = (2 a0 b0 - M t0, 2 (a0 b1 + a1 b0) - M t1, 2 a1 b1), M = rint(w); a, b, t read in place at
+        nl_a, nl_b, nl_t limbs; t None is the constant 1; a is b squares."""
+        self._check(self._L.mkckks_cheb_tensor_batch(self._h, _ptr(a), int(nl_a), _ptr(b), int(nl_b), _ptr(t), int(nl_t),
+                                                     float(w), _ptr(out3), n_ct, int(nl)))
+
+    def cheb_ladder(self, u, rlk, out, n_ct, nl, n, scale_in):
+        """out = T_1(u) .. T_n(u), T_k packed [n_ct][2][nl_k][N] behind T_{k-1}; returns (nl_k list, S_k list)."""
+        n = int(n)
+        if not 1 <= n <= 64:
+            raise ValueError("n must be in [1, 64]")
+        nls, scales = (C.c_uint32 * n)(), (C.c_double * n)()
+        self._check(self._L.mkckks_cheb_ladder_batch(self._h, _ptr(u), _ptr(rlk), _ptr(out), n_ct, int(nl), n, float(scale_in),
+                                                     C.addressof(nls), C.addressof(scales)))
+        return list(nls), list(scales)
+
+    def cheb_weights(self, coef, nl, scale_in):
+        """(w float64[G][B], S_out) of the series sum_k coef[k] T_k(u) for u at nl limbs and scale scale_in.  Host only."""
+        c = np.ascontiguousarray(coef, dtype=np.float64)
+        if c.ndim != 1 or not 3 <= c.size <= POLY_MAX_DEGREE + 1:
+            raise ValueError("coef must hold the 3 .. 64 coefficients of a series of degree 2 .. 63")
+        plan = self.poly_plan(c.size - 1, nl)
+        w = np.zeros((plan["G"], plan["B"]), dtype=np.float64)
+        s_out = C.c_double()
+        self._check(self._L.mkckks_cheb_weights(self._h, c.ctypes.data, c.size - 1, int(nl), float(scale_in), w.ctypes.data,
+                                                C.byref(s_out)))
+        return w, s_out.value
+
+    def cheb_eval(self, ct, rlk, coef, a, b, out, n_ct, nl, scale_in):
+        """out [n_ct][2][nl_out][N] = sum_k coef[k] T_k(u) slot-wise, u = the map of [a, b] onto [-1, 1]; returns S_out."""
+        c = np.ascontiguousarray(coef, dtype=np.float64)
+        if c.ndim != 1 or not 2 <= c.size <= POLY_MAX_DEGREE + 2:  # degrees 1 and 64 reach the library, which refuses them
+            raise ValueError("coef must hold the coefficients of a series of degree 2 .. 63")
+        s_out = C.c_double()
+        self._check(self._L.mkckks_cheb_eval_batch(self._h, _ptr(ct), _ptr(rlk), c.ctypes.data, c.size - 1, float(a), float(b),
+                                                   _ptr(out), n_ct, int(nl), float(scale_in), C.byref(s_out)))
         return s_out.value
 
     # ---- collective evaluation keys of a joint key (include/mkckks.h: "collective evaluation keys")

@@ -708,6 +708,129 @@ int mkckks_poly_eval_batch(mkckks_ctx *c, const uint64_t *d_ct, const uint64_t *
         c->eng->poly_eval(d_ct, d_rlk, h_coef, degree, d_out, n_ct, nl, scale_in);
     });
 }
+// ---- Chebyshev series: every refusal is decided here, before a device is asked for (the h_ arrays are host arrays)
+int mkckks_affine_batch(mkckks_ctx *c, const uint64_t *d_in, uint64_t *d_out, uint32_t n_ct, uint32_t nl, double w_mul,
+                        double w_add) {
+    return guarded([&] {
+        need(c && d_in && d_out, "null argument");
+        const mk::ParamSet &ps = c->eng->params();
+        need(nl >= 1 && nl <= ps.L, "nl out of range");
+        need_aligned16({d_in, d_out});
+        const size_t bytes = poly_bytes((unsigned __int128)n_ct * 2, nl, ps.n);
+        need(d_out == d_in || !ranges_meet(d_in, bytes, d_out, bytes), "output partially overlaps the input");
+        const double w[2] = {w_mul, w_add};
+        (void)ps.poly_constants(w, 2, nl);  // the weights' refusals
+        if (!n_ct) return;
+        c->eng->affine(d_in, d_out, n_ct, nl, w_mul, w_add);
+    });
+}
+int mkckks_cheb_tensor_batch(mkckks_ctx *c, const uint64_t *d_a, uint32_t nl_a, const uint64_t *d_b, uint32_t nl_b,
+                             const uint64_t *d_t, uint32_t nl_t, double w, uint64_t *d_out3, uint32_t n_ct, uint32_t nl) {
+    return guarded([&] {
+        need(c && d_a && d_b && d_out3, "null argument");
+        const mk::ParamSet &ps = c->eng->params();
+        need(nl >= 1 && nl <= ps.L, "nl out of range");
+        need(nl_a >= nl && nl_a <= ps.L && nl_b >= nl && nl_b <= ps.L && (!d_t || (nl_t >= nl && nl_t <= ps.L)),
+             "an operand's limb count is outside [nl, L]");
+        need(d_a != d_b || nl_a == nl_b, "the square needs one limb count");
+        need_aligned16({d_a, d_b, d_t, d_out3});
+        const size_t out_bytes = poly_bytes((unsigned __int128)n_ct * 3, nl, ps.n);
+        need(!ranges_meet(d_a, poly_bytes((unsigned __int128)n_ct * 2, nl_a, ps.n), d_out3, out_bytes) &&
+                 !ranges_meet(d_b, poly_bytes((unsigned __int128)n_ct * 2, nl_b, ps.n), d_out3, out_bytes) &&
+                 !(d_t && ranges_meet(d_t, poly_bytes((unsigned __int128)n_ct * 2, nl_t, ps.n), d_out3, out_bytes)),
+             "output overlaps input");
+        (void)ps.poly_constants(&w, 1, nl);  // the weight's refusals
+        if (!n_ct) return;
+        c->eng->cheb_tensor(d_a, nl_a, d_b, nl_b, d_t, nl_t, w, d_out3, n_ct, nl);
+    });
+}
+// every step's weight S_i * S_j / S_{i-j} must fit its level: decided here, so that a ladder never stops half way
+static void need_ladder_weights(const mk::ParamSet &ps, const uint32_t *nlk, const double *sk, uint32_t n_cheb) {
+    for (uint32_t k = 2; k <= n_cheb; ++k) {  // nlk / sk are 0-based: entry k - 1 belongs to T_k
+        const uint32_t i = (k + 1) / 2, j = k - i;
+        const double prod = sk[i - 1] * sk[j - 1];
+        const double w = i != j ? prod / sk[0] : prod;
+        (void)ps.poly_constants(&w, 1, nlk[i - 1]);
+    }
+}
+int mkckks_cheb_ladder_batch(mkckks_ctx *c, const uint64_t *d_u, const uint64_t *d_rlk, uint64_t *d_out, uint32_t n_ct,
+                             uint32_t nl, uint32_t n_cheb, double scale_in, uint32_t *h_nl_out, double *h_scale_out) {
+    return guarded([&] {
+        need(c && d_u && d_rlk && d_out, "null argument");
+        const mk::ParamSet &ps = c->eng->params();
+        need(nl >= 1 && nl <= ps.L, "nl out of range");
+        need(n_cheb >= 1 && n_cheb <= 64, "n must be in [1, 64]");
+        need(scale_in > 0 && std::isfinite(scale_in), "scale must be positive and finite");
+        std::vector<uint32_t> nlk(n_cheb);
+        std::vector<double> sk(n_cheb);
+        ps.power_ladder(nl, n_cheb, scale_in, nlk.data(), sk.data());
+        need_ladder_weights(ps, nlk.data(), sk.data(), n_cheb);
+        need_aligned16({d_u, d_out});
+        const size_t out_bytes = ladder_bytes(nlk.data(), n_cheb, n_ct, ps.n);
+        need(!ranges_meet(d_u, poly_bytes((unsigned __int128)n_ct * 2, nl, ps.n), d_out, out_bytes), "output overlaps input");
+        need(!ranges_meet(d_rlk, poly_bytes((unsigned __int128)ps.beta * 2, ps.D, ps.n), d_out, out_bytes), "output overlaps the key");
+        need(n_cheb < 2 || ps.num_parts(nl) <= 6, "more than 6 key-switch digits unsupported");
+        if (h_nl_out) std::memcpy(h_nl_out, nlk.data(), n_cheb * sizeof(uint32_t));
+        if (h_scale_out) std::memcpy(h_scale_out, sk.data(), n_cheb * sizeof(double));
+        if (!n_ct) return;
+        c->eng->cheb_ladder(d_u, d_rlk, d_out, n_ct, nl, n_cheb, scale_in);
+    });
+}
+int mkckks_cheb_weights(const mkckks_ctx *c, const double *h_coef, uint32_t degree, uint32_t nl, double scale_in, double *h_w,
+                        double *scale_out) {
+    return guarded([&] {
+        need(c && h_coef && h_w && scale_out, "null argument");
+        const mk::ParamSet &ps = c->eng->params();
+        const mk::PolyPlan p = ps.poly_plan(degree, nl);
+        std::vector<double> w((size_t)p.B * p.G);
+        *scale_out = ps.cheb_weights(h_coef, degree, nl, scale_in, w.data());
+        std::memcpy(h_w, w.data(), w.size() * sizeof(double));
+    });
+}
+int mkckks_cheb_eval_batch(mkckks_ctx *c, const uint64_t *d_ct, const uint64_t *d_rlk, const double *h_coef, uint32_t degree,
+                           double a, double b, uint64_t *d_out, uint32_t n_ct, uint32_t nl, double scale_in, double *scale_out) {
+    return guarded([&] {
+        need(c && d_ct && d_rlk && h_coef && d_out, "null argument");
+        const mk::ParamSet &ps = c->eng->params();
+        need(std::isfinite(a) && std::isfinite(b) && a < b, "the interval needs finite a < b");
+        need(nl >= 1 && nl <= ps.L, "nl out of range");
+        need(scale_in > 0 && std::isfinite(scale_in), "scale must be positive and finite");
+        const bool mapped = !(a == -1.0 && b == 1.0);
+        const uint32_t nl_u = mapped ? nl - 1 : nl;
+        mk::PolyPlan p{};
+        try {
+            if (mapped && nl_u < 1) throw std::invalid_argument("degree " + std::to_string(degree) + " needs at least 3 limbs");
+            p = ps.poly_plan(degree, nl_u);
+        } catch (const std::invalid_argument &e) {
+            if (!mapped) throw;
+            throw std::invalid_argument(std::string(e.what()) + " (the map of [a, b] onto [-1, 1] spends one of the input's " +
+                                        std::to_string(nl) + ")");
+        }
+        const double scale_u = mapped ? ps.sf.at(ps.L - nl_u) : scale_in;
+        if (mapped) {
+            const double sigma1 = scale_u * (double)ps.moduli[nl - 1];
+            const double w[2] = {2.0 / (b - a) * (sigma1 / scale_in), -(a + b) / (b - a) * sigma1};
+            (void)ps.poly_constants(w, 2, nl);
+        }
+        std::vector<double> w((size_t)p.B * p.G);
+        const double s_out = ps.cheb_weights(h_coef, degree, nl_u, scale_u, w.data());
+        (void)ps.poly_constants(w.data(), p.B * p.G, p.nl_T);
+        uint32_t nlx[mk::POLY_MAX_B], nly[mk::POLY_MAX_B];
+        double sx[mk::POLY_MAX_B], sy[mk::POLY_MAX_B];
+        ps.power_ladder(nl_u, p.B, scale_u, nlx, sx);
+        need_ladder_weights(ps, nlx, sx, p.B);
+        ps.power_ladder(nlx[p.B - 1], p.G - 1, sx[p.B - 1], nly, sy);
+        need_ladder_weights(ps, nly, sy, p.G - 1);
+        need_aligned16({d_ct, d_out});
+        const size_t out_bytes = poly_bytes((unsigned __int128)n_ct * 2, p.nl_out, ps.n);
+        need(!ranges_meet(d_ct, poly_bytes((unsigned __int128)n_ct * 2, nl, ps.n), d_out, out_bytes), "output overlaps input");
+        need(!ranges_meet(d_rlk, poly_bytes((unsigned __int128)ps.beta * 2, ps.D, ps.n), d_out, out_bytes), "output overlaps the key");
+        need(ps.num_parts(nl) <= 6, "more than 6 key-switch digits unsupported");
+        if (scale_out) *scale_out = s_out;
+        if (!n_ct) return;
+        c->eng->cheb_eval(d_ct, d_rlk, h_coef, degree, a, b, d_out, n_ct, nl, scale_in);
+    });
+}
 // ---- collective evaluation keys of a joint key: every refusal is decided here, before a device is asked for
 int mkckks_evk_sum(mkckks_ctx *c, const uint64_t *in, uint64_t *out, uint32_t n_parties, uint32_t n_keys) {
     return guarded([&] {

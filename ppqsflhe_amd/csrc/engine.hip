@@ -25,6 +25,7 @@
 #include "lintrans_kernels.hpp"
 #include "bsgs_kernels.hpp"
 #include "poly_kernels.hpp"
+#include "cheb_kernels.hpp"
 #include "relshare_kernels.hpp"
 #include "sampler_kernels.hpp"
 #include "arith_probe_kernels.hpp"
@@ -633,6 +634,10 @@ Knobs Knobs::from_env() {
     if (const char *e = std::getenv("MKCKKS_POLY_FUSED")) {
         if (!std::strcmp(e, "0")) k.poly_fused = 0;
         else if (!std::strcmp(e, "1")) k.poly_fused = 1;
+    }
+    if (const char *e = std::getenv("MKCKKS_CHEB_FUSED")) {
+        if (!std::strcmp(e, "0")) k.cheb_fused = 0;
+        else if (!std::strcmp(e, "1")) k.cheb_fused = 1;
     }
     if (const char *e = std::getenv("MKCKKS_LT_ORDER")) {
         if (e[0] >= '0' && e[0] <= '2' && !e[1]) k.lt_order = e[0] - '0';
@@ -2149,16 +2154,7 @@ const u64 *Engine::weight_table(const double *w, uint32_t n, uint32_t sf_level) 
             }
         }
     }
-    if (wt_cache_.size() >= 64) {
-        MK_HIP(hipStreamSynchronize(stream_));
-        for (auto &kv : wt_cache_) MK_HIP(hipFree(kv.second));
-        wt_cache_.clear();
-    }
-    u64 *d = nullptr;
-    MK_HIP(hipMalloc(&d, t.size() * sizeof(u64)));
-    wt_cache_[key] = d;
-    MK_HIP(hipMemcpy(d, t.data(), t.size() * sizeof(u64), hipMemcpyHostToDevice));
-    return d;
+    return cache_table(key, t);
 }
 
 void Engine::scale_evk(const u64 *in, u64 *out, uint32_t n_keys, const double *w, uint32_t sf_level) {
@@ -2869,16 +2865,7 @@ const u64 *Engine::poly_table(const double *w, uint32_t B, uint32_t G, uint32_t 
         wt[0] = m[e];
         wt[1] = h_shoup(m[e], ps_.moduli[e % nl_T]);
     }
-    if (wt_cache_.size() >= 64) {
-        MK_HIP(hipStreamSynchronize(stream_));
-        for (auto &kv : wt_cache_) MK_HIP(hipFree(kv.second));
-        wt_cache_.clear();
-    }
-    u64 *d = nullptr;
-    MK_HIP(hipMalloc(&d, t.size() * sizeof(u64)));
-    wt_cache_[key] = d;
-    MK_HIP(hipMemcpy(d, t.data(), t.size() * sizeof(u64), hipMemcpyHostToDevice));
-    return d;
+    return cache_table(key, t);
 }
 
 // words of scratch poly_tensor_core needs: none for the kernel; the composition packs the operands' prefixes and keeps
@@ -3049,6 +3036,276 @@ void Engine::poly_eval(const u64 *ct, const u64 *rlk, const double *coef, uint32
         PolyOpnd bo[POLY_MAX_B - 1] = {}, go[POLY_MAX_B - 1] = {};
         for (uint32_t i = 1; i < B; ++i) bo[i - 1] = PolyOpnd{pwx[i], nlx[i], 0};
         for (uint32_t j = 1; j < G; ++j) go[j - 1] = PolyOpnd{pwy[j], nly[j], 0};
+        poly_tensor_core(bo, go, table, buf + off_out3, B, G, cnt, nl_T, buf + off_comp);
+        relinearize(buf + off_out3, rlk, buf + off_relin, cnt, nl_T);
+        rescale(buf + off_relin, buf + off_resc, cnt, nl_T, nullptr);
+        rescale(buf + off_resc, out + (size_t)done * 2 * p.nl_out * n, cnt, nl_T - 1, nullptr);
+    }
+}
+
+// ---- Chebyshev series ("Chebyshev series"); overlaps and alignment are refused in capi.cpp ---------------------
+
+// A new entry of the weight-table cache, uploaded: the one place where the cache grows and is emptied (weight_table,
+// poly_table, cheb_table and affine_core all end here).  At 64 tables it is emptied: the stream is waited for, so work
+// already enqueued keeps its tables, and EVERY entry is freed.  So no table pointer may be held across another lookup:
+// look a table up immediately before the launch that reads it, after every other lookup the call makes.
+const u64 *Engine::cache_table(const std::string &key, const std::vector<u64> &t) {
+    if (wt_cache_.size() >= 64) {
+        MK_HIP(hipStreamSynchronize(stream_));
+        for (auto &kv : wt_cache_) MK_HIP(hipFree(kv.second));
+        wt_cache_.clear();
+    }
+    u64 *d = nullptr;
+    MK_HIP(hipMalloc(&d, t.size() * sizeof(u64)));
+    wt_cache_[key] = d;
+    MK_HIP(hipMemcpy(d, t.data(), t.size() * sizeof(u64), hipMemcpyHostToDevice));
+    return d;
+}
+
+// Device table of a step's weight, cached per (weight, nl) in the weight-table cache: M' u64[nl] with M' = (q - M mod q)
+// mod q (k_cheb_tensor, k_poly_add_const), then the composition's two weight-table entries [2][nl][WT_WORDS]: 2 and M'
+const u64 *Engine::cheb_table(double w, uint32_t nl) {
+    std::string key((const char *)&w, sizeof(double));
+    key += "@cheb" + std::to_string(nl);
+    auto it = wt_cache_.find(key);
+    if (it != wt_cache_.end()) return it->second;
+    const std::vector<u64> m = ps_.poly_constants(&w, 1, nl);  // throws on a weight that does not fit
+    std::vector<u64> t((size_t)nl * (1 + 2 * WT_WORDS), 0);
+    for (uint32_t l = 0; l < nl; ++l) {
+        const u64 q = ps_.moduli[l], neg = m[l] ? q - m[l] : 0;
+        t[l] = neg;
+        u64 *two = &t[nl + (size_t)l * WT_WORDS], *term = &t[nl + ((size_t)nl + l) * WT_WORDS];
+        two[0] = 2;
+        two[1] = h_shoup(2, q);
+        term[0] = neg;
+        term[1] = h_shoup(neg, q);
+    }
+    return cache_table(key, t);
+}
+
+// words of scratch cheb_step_core needs: none for the kernel; the composition packs the prefixes of a and b and keeps the
+// tensor product and the packed term side by side (the two terms of k_wsum_ct)
+size_t Engine::cheb_step_scratch(uint32_t cnt, uint32_t nl) const {
+    if (knobs_.cheb_fused != 0) return 0;
+    return (size_t)4 * cnt * 2 * nl * ps_.n;
+}
+
+// (d0, d1) -> o01, d2 -> o2 for `cnt` items.  The composition writes packed items: o01_stride = 2 * nl * N, o2_stride = nl * N
+void Engine::cheb_step_core(const u64 *a, uint32_t nl_a, const u64 *b, uint32_t nl_b, const u64 *t, uint32_t nl_t,
+                            const u64 *table, u64 *o01, size_t o01_stride, u64 *o2, size_t o2_stride, uint32_t cnt, uint32_t nl,
+                            u64 *scratch) {
+    const uint32_t n = ps_.n;
+    if (!cnt) return;
+    if (((uintptr_t)a | (uintptr_t)b | (uintptr_t)t | (uintptr_t)o01 | (uintptr_t)o2) & 15)
+        throw std::invalid_argument("ciphertext arrays must be 16-byte aligned");
+    const bool square = a == b;
+    if (cheb_step_fused(square, t != nullptr, knobs_.cheb_fused)) {
+        const ChebArgs c{a, b, t, table, o01, o2, o01_stride, o2_stride, nl_a, nl_b, t ? nl_t : nl, n, nl};
+        const dim3 grid((n / 2 + CHEB_THREADS - 1) / CHEB_THREADS, nl, cnt);
+        if (square && t) k_cheb_tensor<true, true><<<grid, CHEB_THREADS, 0, stream_>>>(c, d_limb_);
+        else if (square) k_cheb_tensor<true, false><<<grid, CHEB_THREADS, 0, stream_>>>(c, d_limb_);
+        else if (t) k_cheb_tensor<false, true><<<grid, CHEB_THREADS, 0, stream_>>>(c, d_limb_);
+        else k_cheb_tensor<false, false><<<grid, CHEB_THREADS, 0, stream_>>>(c, d_limb_);
+        MK_HIP(hipGetLastError());
+        return;
+    }
+    // the composition, from kernels that were there before: packed prefix copies, k_tensor, then 2 * (d0, d1) + M' t by
+    // k_wsum_ct (2 * (d0, d1) and M' onto d0 by k_poly_add_const for the constant), and 2 * d2 by k_wsum_ct in place
+    const size_t poly = (size_t)nl * n, term = (size_t)cnt * 2 * poly;
+    if (o01_stride != 2 * poly || o2_stride != poly) throw std::logic_error("cheb_step_core: the composition writes packed items");
+    u64 *ap = scratch, *bp = ap + term, *s0 = bp + term;
+    const u64 *pa = a, *pb = b;
+    if (nl_a != nl) {
+        k_copy_slots<<<ew_grid(n, nl, 2 * cnt), EW_THREADS, 0, stream_>>>(a, (size_t)nl_a * n, 0, ap, poly, 0, n);
+        pa = ap;
+    }
+    if (square) {
+        pb = pa;
+    } else if (nl_b != nl) {
+        k_copy_slots<<<ew_grid(n, nl, 2 * cnt), EW_THREADS, 0, stream_>>>(b, (size_t)nl_b * n, 0, bp, poly, 0, n);
+        pb = bp;
+    }
+    MK_HIP(hipGetLastError());
+    launch_tensor(pa, pb, 0, 1, s0, 2 * poly, o2, poly, cnt, nl);
+    EwGeom g{n, nl, ps_.L};
+    const u64 *wt = table + nl;
+    if (t) {
+        k_copy_slots<<<ew_grid(n, nl, 2 * cnt), EW_THREADS, 0, stream_>>>(t, (size_t)nl_t * n, 0, s0 + term, poly, 0, n);
+        k_wsum_ct<<<ew_grid(n, 2 * nl, cnt), EW_THREADS, 0, stream_>>>(s0, o01, g, d_limb_, 2 * nl, 2, term, wt, nl, 0);
+    } else {
+        k_wsum_ct<<<ew_grid(n, 2 * nl, cnt), EW_THREADS, 0, stream_>>>(s0, o01, g, d_limb_, 2 * nl, 1, term, wt, nl, 0);
+        k_poly_add_const<<<ew_grid(n, nl, cnt), EW_THREADS, 0, stream_>>>(o01, g, d_limb_, table);
+    }
+    k_wsum_ct<<<ew_grid(n, nl, cnt), EW_THREADS, 0, stream_>>>(o2, o2, g, d_limb_, nl, 1, 0, wt, nl, 0);
+    MK_HIP(hipGetLastError());
+}
+
+void Engine::cheb_tensor(const u64 *a, uint32_t nl_a, const u64 *b, uint32_t nl_b, const u64 *t, uint32_t nl_t, double w,
+                         u64 *out3, uint32_t n_ct, uint32_t nl) {
+    need_device();
+    check_nl(nl);
+    if (!n_ct) return;
+    const uint32_t n = ps_.n;
+    const size_t poly = (size_t)nl * n;
+    const u64 *table = cheb_table(w, nl);
+    constexpr uint32_t MAX_ITEMS = 16384;  // grid.z, and twice as many polynomials in the composition's copies
+    const uint32_t step = std::min(n_ct, MAX_ITEMS);
+    const bool fused = cheb_step_fused(a == b, t != nullptr, knobs_.cheb_fused);
+    // the composition writes packed (d0, d1) and d2: they pass through the poly buffer on their way to out3
+    u64 *buf = fused ? nullptr : poly_buffer((size_t)step * 3 * poly + cheb_step_scratch(step, nl));
+    for (uint32_t done = 0; done < n_ct; done += step) {
+        const uint32_t cnt = std::min(step, n_ct - done);
+        const u64 *pa = a + (size_t)done * 2 * nl_a * n, *pb = a == b ? pa : b + (size_t)done * 2 * nl_b * n;
+        const u64 *pt = t ? t + (size_t)done * 2 * nl_t * n : nullptr;
+        u64 *o = out3 + (size_t)done * 3 * poly;
+        if (fused) {
+            cheb_step_core(pa, nl_a, pb, nl_b, pt, nl_t, table, o, 3 * poly, o + 2 * poly, 3 * poly, cnt, nl, nullptr);
+            continue;
+        }
+        u64 *p01 = buf, *p2 = buf + (size_t)step * 2 * poly;
+        cheb_step_core(pa, nl_a, pb, nl_b, pt, nl_t, table, p01, 2 * poly, p2, poly, cnt, nl, buf + (size_t)step * 3 * poly);
+        k_copy_slots<<<ew_grid(n, 2 * nl, cnt), EW_THREADS, 0, stream_>>>(p01, 2 * poly, 0, o, 3 * poly, 0, n);
+        k_copy_slots<<<ew_grid(n, nl, cnt), EW_THREADS, 0, stream_>>>(p2, poly, 0, o, 3 * poly, 2 * nl, n);
+        MK_HIP(hipGetLastError());
+    }
+}
+
+void Engine::cheb_ladder_core(u64 *const *pw, const uint32_t *nlk, const double *sk, const u64 *rlk, uint32_t cnt, uint32_t n_cheb,
+                              u64 *scratch) {
+    const uint32_t n = ps_.n;
+    if (n_cheb < 2) return;
+    u64 *prod = scratch, *comp = scratch + (size_t)cnt * 2 * nlk[1] * n;
+    u64 *d2 = chunk_buffer((size_t)cnt * nlk[1] * n);
+    for (uint32_t k = 2; k <= n_cheb; ++k) {
+        const uint32_t i = (k + 1) / 2, j = k - i, nli = nlk[i];
+        const size_t poly = (size_t)nli * n;
+        const bool term = i != j;  // T_{i-j} = T_1; else the constant T_0 = 1 with scale 1
+        const double prod_s = sk[i] * sk[j];
+        const double w = term ? prod_s / sk[1] : prod_s;
+        cheb_step_core(pw[i], nli, pw[j], nlk[j], term ? pw[1] : nullptr, nlk[1], cheb_table(w, nli), prod, 2 * poly, d2, poly, cnt,
+                       nli, comp);
+        relin_chunk(d2, poly, rlk, prod, cnt, nli);
+        rescale(prod, pw[k], cnt, nli, nullptr);
+    }
+}
+
+void Engine::cheb_ladder(const u64 *u, const u64 *rlk, u64 *out, uint32_t n_ct, uint32_t nl, uint32_t n_cheb, double scale_in) {
+    need_device();
+    check_nl(nl);
+    std::vector<uint32_t> nlk(n_cheb + 1);
+    std::vector<double> sk(n_cheb + 1);
+    ps_.power_ladder(nl, n_cheb, scale_in, nlk.data() + 1, sk.data() + 1);
+    if (!n_ct) return;
+    const uint32_t n = ps_.n;
+    MK_HIP(hipMemcpyAsync(out, u, (size_t)n_ct * 2 * nl * n * sizeof(u64), hipMemcpyDeviceToDevice, stream_));
+    if (n_cheb < 2) return;
+    const uint32_t chunk = std::min(knobs_.chunk, n_ct);
+    u64 *scratch = poly_buffer((size_t)chunk * 2 * nl * n + cheb_step_scratch(chunk, nl));
+    std::vector<size_t> off(n_cheb + 1, 0);
+    for (uint32_t k = 2; k <= n_cheb; ++k) off[k] = off[k - 1] + (size_t)n_ct * 2 * nlk[k - 1] * n;
+    std::vector<u64 *> pw(n_cheb + 1, nullptr);
+    for (uint32_t done = 0; done < n_ct; done += chunk) {
+        const uint32_t cnt = std::min(chunk, n_ct - done);
+        for (uint32_t k = 1; k <= n_cheb; ++k) pw[k] = out + off[k] + (size_t)done * 2 * nlk[k] * n;
+        cheb_ladder_core(pw.data(), nlk.data(), sk.data(), rlk, cnt, n_cheb, scratch);
+    }
+}
+
+// Device table of an affine map's constants, cached like a step's: Ma u64[nl], then Mc u64[nl]
+void Engine::affine_core(const u64 *in, u64 *out, uint32_t cnt, uint32_t nl, double w_mul, double w_add) {
+    if (!cnt) return;
+    const double w[2] = {w_mul, w_add};
+    std::string key((const char *)w, sizeof(w));
+    key += "@affine" + std::to_string(nl);
+    auto it = wt_cache_.find(key);
+    // poly_constants throws on a weight that does not fit
+    const u64 *table = it != wt_cache_.end() ? it->second : cache_table(key, ps_.poly_constants(w, 2, nl));
+    const dim3 grid((ps_.n / 2 + CHEB_THREADS - 1) / CHEB_THREADS, 2 * nl, cnt);
+    k_affine<<<grid, CHEB_THREADS, 0, stream_>>>(in, out, table, ps_.n, nl, d_limb_);
+    MK_HIP(hipGetLastError());
+}
+
+void Engine::affine(const u64 *in, u64 *out, uint32_t n_ct, uint32_t nl, double w_mul, double w_add) {
+    need_device();
+    check_nl(nl);
+    if (((uintptr_t)in | (uintptr_t)out) & 15) throw std::invalid_argument("ciphertext arrays must be 16-byte aligned");
+    constexpr uint32_t MAX_ITEMS = 32768;  // grid.z
+    for (uint32_t done = 0; done < n_ct; done += MAX_ITEMS) {
+        const size_t off = (size_t)done * 2 * nl * ps_.n;
+        affine_core(in + off, out + off, std::min(MAX_ITEMS, n_ct - done), nl, w_mul, w_add);
+    }
+}
+
+// per chunk, everything but the input and the output in the poly buffer: the mapped input before and after its rescale,
+// T_2 .. T_B of u, T_2 .. T_{G-1} of y = T_B, the ladder's scratch, the outer sum, its relinearisation and the first rescale
+void Engine::cheb_eval(const u64 *ct, const u64 *rlk, const double *coef, uint32_t degree, double a, double b, u64 *out,
+                       uint32_t n_ct, uint32_t nl, double scale_in) {
+    need_device();
+    check_nl(nl);
+    const bool mapped = !(a == -1.0 && b == 1.0);
+    if (mapped && nl < 2) throw std::invalid_argument("the map onto [-1, 1] needs 2 limbs, the input has 1");
+    const uint32_t nl_u = mapped ? nl - 1 : nl;
+    const double scale_u = mapped ? ps_.sf.at(ps_.L - nl_u) : scale_in;
+    const PolyPlan p = ps_.poly_plan(degree, nl_u);
+    std::vector<double> w((size_t)p.B * p.G);
+    ps_.cheb_weights(coef, degree, nl_u, scale_u, w.data());
+    double w_mul = 0.0, w_add = 0.0;
+    if (mapped) {
+        const double alpha = 2.0 / (b - a), beta = -(a + b) / (b - a);
+        const double sigma1 = scale_u * (double)ps_.moduli[nl - 1];
+        w_mul = alpha * (sigma1 / scale_in);
+        w_add = beta * sigma1;
+    }
+    if (!n_ct) return;
+    const uint32_t n = ps_.n, B = p.B, G = p.G, nl_T = p.nl_T;
+    uint32_t nlx[POLY_MAX_B + 1] = {}, nly[POLY_MAX_B] = {};
+    double sx[POLY_MAX_B + 1] = {}, sy[POLY_MAX_B] = {};
+    ps_.power_ladder(nl_u, B, scale_u, nlx + 1, sx + 1);
+    ps_.power_ladder(nlx[B], G - 1, sx[B], nly + 1, sy + 1);
+    const uint32_t chunk = std::min(knobs_.chunk, n_ct);
+    const size_t ctw = (size_t)chunk * 2 * n;  // words of a chunk's ciphertexts per limb
+    size_t words = 0, off_x[POLY_MAX_B + 1] = {}, off_y[POLY_MAX_B] = {};
+    const size_t off_map = words;
+    if (mapped) words += ctw * nl + ctw * nl_u;
+    for (uint32_t k = 2; k <= B; ++k) {
+        off_x[k] = words;
+        words += ctw * nlx[k];
+    }
+    for (uint32_t k = 2; k < G; ++k) {
+        off_y[k] = words;
+        words += ctw * nly[k];
+    }
+    const size_t off_ladder = words;
+    words += ctw * nl_u + cheb_step_scratch(chunk, nl_u);
+    const size_t off_out3 = words;
+    words += (size_t)chunk * 3 * nl_T * n;
+    const size_t off_relin = words;
+    words += ctw * nl_T;
+    const size_t off_resc = words;
+    words += ctw * (nl_T - 1);
+    const size_t off_comp = words;
+    words += poly_tensor_scratch(B, G, chunk, nl_T);
+    u64 *buf = poly_buffer(words);
+    for (uint32_t done = 0; done < n_ct; done += chunk) {
+        const uint32_t cnt = std::min(chunk, n_ct - done);
+        u64 *pwx[POLY_MAX_B + 1] = {}, *pwy[POLY_MAX_B] = {};
+        pwx[1] = const_cast<u64 *>(ct) + (size_t)done * 2 * nl * n;  // read only: the ladder writes pw[k] for k >= 2
+        if (mapped) {
+            u64 *pre = buf + off_map;
+            pwx[1] = pre + ctw * nl;
+            affine_core(ct + (size_t)done * 2 * nl * n, pre, cnt, nl, w_mul, w_add);
+            rescale(pre, pwx[1], cnt, nl, nullptr);
+        }
+        for (uint32_t k = 2; k <= B; ++k) pwx[k] = buf + off_x[k];
+        cheb_ladder_core(pwx, nlx, sx, rlk, cnt, B, buf + off_ladder);
+        pwy[1] = pwx[B];
+        for (uint32_t k = 2; k < G; ++k) pwy[k] = buf + off_y[k];
+        cheb_ladder_core(pwy, nly, sy, rlk, cnt, G - 1, buf + off_ladder);
+        PolyOpnd bo[POLY_MAX_B - 1] = {}, go[POLY_MAX_B - 1] = {};
+        for (uint32_t i = 1; i < B; ++i) bo[i - 1] = PolyOpnd{pwx[i], nlx[i], 0};
+        for (uint32_t j = 1; j < G; ++j) go[j - 1] = PolyOpnd{pwy[j], nly[j], 0};
+        // looked up here, per chunk, behind the map's and the ladders' own lookups: any of them may empty the cache
+        const u64 *table = poly_table(w.data(), B, G, nl_T);
         poly_tensor_core(bo, go, table, buf + off_out3, B, G, cnt, nl_T, buf + off_comp);
         relinearize(buf + off_out3, rlk, buf + off_relin, cnt, nl_T);
         rescale(buf + off_relin, buf + off_resc, cnt, nl_T, nullptr);

@@ -83,6 +83,9 @@ struct Knobs {
     int poly_fused = 2;          // MKCKKS_POLY_FUSED=0/1: poly_tensor as the composition (eval_wsum per giant index on packed prefix
                                  // copies + tensor_sum + the constant column and term) or as k_poly_tensor; default:
                                  // poly_tensor_fused (profiles/poly_ab.txt)
+    int cheb_fused = 2;          // MKCKKS_CHEB_FUSED=0/1: a Chebyshev ladder step before its relinearisation as the composition
+                                 // (packed prefix copies + k_tensor + k_wsum_ct / k_poly_add_const) or as k_cheb_tensor;
+                                 // default: cheb_step_fused (profiles/cheb_ab.txt)
     int bsgs_fused = 1;          // MKCKKS_BSGS_FUSED=0: linear_transform_bsgs as the composition of k_lt_accum (one rotation, an
                                  // all-ones plaintext) per baby and per giant, k_fma and k_automorph; default: k_bsgs_baby,
                                  // k_bsgs_inner, k_bsgs_giant (profiles/lt_bsgs_ab.txt)
@@ -122,6 +125,15 @@ inline uint32_t icol_conv_targets(uint32_t n_fp, uint64_t grid, int mode) {
 // three instances with G = 2, 3, 4 and 8, the largest plan (8, 8) included (profiles/poly_ab.txt); a plan that measures
 // otherwise gets its exception here.
 inline bool poly_tensor_fused(uint32_t /*B*/, uint32_t /*G*/, int mode) {
+    return mode != 0;
+}
+
+// The form a Chebyshev ladder step takes before its relinearisation: true = k_cheb_tensor, false = the composition.  mode
+// 0 / 1 force a form, anything else chooses: the kernel on all four instances (square or general, constant or ciphertext
+// term) -- it reads each operand once where it is and writes each output once, where the composition adds prefix copies
+// and two or three more streaming passes (profiles/cheb_ab.txt); an instance that measures otherwise gets its exception
+// here.
+inline bool cheb_step_fused(bool /*square*/, bool /*term*/, int mode) {
     return mode != 0;
 }
 
@@ -281,6 +293,20 @@ public:
                      u64 *out3, uint32_t B, uint32_t G, uint32_t n_ct, uint32_t nl_T);
     void poly_eval(const u64 *ct, const u64 *rlk, const double *coef, uint32_t degree, u64 *out, uint32_t n_ct, uint32_t nl,
                    double scale_in);
+    // Chebyshev series ("Chebyshev series"; kernels: cheb_kernels.hpp; weights: ParamSet::cheb_weights)
+    //   affine:      out = rint(w_mul) * in + (rint(w_add), 0) as exact integers mod q_t; no rescale; out may be in
+    //   cheb_tensor: out3 = (2 a0 b0 - M t0, 2 (a0 b1 + a1 b0) - M t1, 2 a1 b1), M = rint(w); a, b, t at nl_a, nl_b, nl_t >= nl
+    //                limbs, read in place; t == nullptr is the constant 1; a == b squares
+    //   cheb_ladder: out = T_1 .. T_n of u, packed like the output of powers; T_k = rescale(relinearize(cheb_tensor(T_i, T_j,
+    //                T_{i-j}))) with i = ceil(k / 2), j = k - i, weight S_i * S_j / S_{i-j}
+    //   cheb_eval:   the affine map of [a, b] onto [-1, 1] and its rescale (skipped for (-1, 1)), the ladder on u up to T_B,
+    //                the ladder on T_B up to G - 1, cheb_weights, the outer sum of poly_eval, relinearize, rescale twice
+    void affine(const u64 *in, u64 *out, uint32_t n_ct, uint32_t nl, double w_mul, double w_add);
+    void cheb_tensor(const u64 *a, uint32_t nl_a, const u64 *b, uint32_t nl_b, const u64 *t, uint32_t nl_t, double w, u64 *out3,
+                     uint32_t n_ct, uint32_t nl);
+    void cheb_ladder(const u64 *u, const u64 *rlk, u64 *out, uint32_t n_ct, uint32_t nl, uint32_t n, double scale_in);
+    void cheb_eval(const u64 *ct, const u64 *rlk, const double *coef, uint32_t degree, double a, double b, u64 *out,
+                   uint32_t n_ct, uint32_t nl, double scale_in);
     // collective evaluation keys of a joint key ("collective evaluation keys"; kernels: relshare_kernels.hpp)
     //   evk_sum:     out[k] = sum_p in[p][k] on all D limbs; in u64[n_parties][n_keys][beta][2][D][N]; out may be in[0]
     //   relin_share: share[j][c] = key1[j][c] * sk + NTT(e_c[j]) on all D limbs; key1, share u64[beta][2][D][N], sk u64[D][N],
@@ -340,6 +366,17 @@ private:
     size_t poly_tensor_scratch(uint32_t B, uint32_t G, uint32_t cnt, uint32_t nl_T) const;
     void poly_tensor_core(const PolyOpnd *baby, const PolyOpnd *giant, const u64 *table, u64 *out3, uint32_t B, uint32_t G,
                           uint32_t cnt, uint32_t nl_T, u64 *scratch);
+    // Chebyshev ladder: the table of a step's weight (cheb_table), the step before its relinearisation (cheb_step_core;
+    // scratch: cheb_step_scratch words, none for the kernel) and the ladder on one chunk (sk[k]: the scale of T_k; scratch:
+    // cnt * 2 * nlk[1] * N words for the product + cheb_step_scratch(cnt, nlk[1]))
+    const u64 *cache_table(const std::string &key, const std::vector<u64> &t);
+    const u64 *cheb_table(double w, uint32_t nl);
+    size_t cheb_step_scratch(uint32_t cnt, uint32_t nl) const;
+    void cheb_step_core(const u64 *a, uint32_t nl_a, const u64 *b, uint32_t nl_b, const u64 *t, uint32_t nl_t, const u64 *table,
+                        u64 *o01, size_t o01_stride, u64 *o2, size_t o2_stride, uint32_t cnt, uint32_t nl, u64 *scratch);
+    void cheb_ladder_core(u64 *const *pw, const uint32_t *nlk, const double *sk, const u64 *rlk, uint32_t cnt, uint32_t n,
+                          u64 *scratch);
+    void affine_core(const u64 *in, u64 *out, uint32_t cnt, uint32_t nl, double w_mul, double w_add);
     // p_scaled: the P targets' constants carry ModDown's scale (ParamSet::modup_table_pscaled; the merged n-client flow)
     const DevConv &modup_conv(uint32_t nl, uint32_t part, bool p_scaled = false);
     const DevConv &moddown_conv(uint32_t nl);

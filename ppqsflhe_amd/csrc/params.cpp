@@ -503,4 +503,25 @@ std::vector<u64> ParamSet::poly_constants(const double *w, uint32_t count, uint3
     return out;
 }
 
+// ---- Chebyshev series: T_{jB+i} = 2 T_i T_{jB} - T_{(j-1)B+(B-i)} for j >= 1, 0 < i < B, applied from the top block down
+
+double ParamSet::cheb_weights(const double *coef, uint32_t degree, uint32_t nl, double scale_in, double *w) const {
+    const PolyPlan p = poly_plan(degree, nl);
+    for (uint32_t k = 0; k <= degree; ++k)
+        if (!std::isfinite(coef[k])) throw std::invalid_argument("coefficient " + std::to_string(k) + " is not finite");
+    const uint32_t B = p.B, G = p.G;
+    std::vector<double> c((size_t)B * G, 0.0), m((size_t)B * G, 0.0);
+    std::copy(coef, coef + degree + 1, c.begin());
+    for (uint32_t j = G - 1; j >= 1; --j) {
+        for (uint32_t i = B - 1; i >= 1; --i) {
+            m[j * B + i] = 2.0 * c[j * B + i];
+            c[(j - 1) * B + (B - i)] -= c[j * B + i];
+        }
+        m[j * B] = c[j * B];
+    }
+    for (uint32_t i = 0; i < B; ++i) m[i] = c[i];
+    // B * G - 1 has the plan of `degree`: B is the smallest power of two with B^2 >= degree + 1, so (B / 2)^2 < B * G
+    return poly_weights(m.data(), B * G - 1, nl, scale_in, w);
+}
+
 }  // namespace mk

@@ -118,6 +118,11 @@ struct ParamSet {
     PolyPlan poly_plan(uint32_t degree, uint32_t nl) const;
     double poly_weights(const double *coef, uint32_t degree, uint32_t nl, double scale_in, double *w) const;
     std::vector<u64> poly_constants(const double *w, uint32_t count, uint32_t nl_T) const;
+    // Chebyshev series (include/mkckks.h: "Chebyshev series"): p(u) = sum_k c_k T_k(u) as sum_j sum_i m_{j,i} T_i T_{jB}.
+    //   cheb_weights: the top-down block rewrite of c into m[G][B] in the header's fixed order, then poly_weights on m with
+    //                 the plan, limbs and scale of u (the Chebyshev ladder has the power ladder's limbs and scales);
+    //                 returns S_out.  Throws on a non-finite coefficient and on everything poly_plan refuses
+    double cheb_weights(const double *coef, uint32_t degree, uint32_t nl, double scale_in, double *w) const;
 };
 
 }  // namespace mk
