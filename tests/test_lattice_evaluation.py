@@ -1,4 +1,5 @@
-"""The evaluation entry points on every parameter region of tests/test_parameter_lattice.py's TABLE.
+"""The evaluation entry points up to the linear transforms on every parameter region of tests/test_parameter_lattice.py's
+TABLE; polynomial and Chebyshev evaluation, which came after them, run on the same table in tests/test_lattice_poly.py.
 
 The feature tests of the plaintext products, the weighted aggregation, rotations, ciphertext products, collective keys, the
 share protocols and the linear transforms run on the seven CONFIGS shapes of tests/test_gpu_parity.py, which all have one

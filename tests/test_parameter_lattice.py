@@ -16,7 +16,8 @@ sides decode the same integers, so the bound does not depend on the scale.  Inpu
 step are computed once per entry (`ks_case`) and shared with the switch tests.
 
 The entry points added since (plaintext products, weighted aggregation, rotations, ciphertext products, collective keys,
-the share protocols, linear transforms) run on the same table in tests/test_lattice_evaluation.py."""
+the share protocols, linear transforms) run on the same table in tests/test_lattice_evaluation.py; polynomial and Chebyshev
+evaluation (poly_tensor, cheb_tensor, affine, the two ladders, poly_eval and cheb_eval) in tests/test_lattice_poly.py."""
 import numpy as np
 import pytest
 
